@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- pass 1 of `pregraph` (k-mer extraction + hash-set insert) on synthetic reads resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]      (N > 1: launched by torch.distributed.run)
 
 One step = one full pass of the hot path over the workload: empty the k-mer set, then extract and insert every
 k-mer occurrence of every read -- exactly the device work `call_pregraph` does for pass 1: K1 per batch (for N > 1:
 pg_count_reads_sharded = cut + route by owner, RCCL all-to-all, append) and pg_finalize (K2: count every partition,
 -d filter, linear marks, coverage histogram).  Reads are generated on the GPU before the timed region and stay
-resident in HBM; FASTQ parsing and PCIe are not in `value`.  Next to it, measured once outside the timed steps and
-reported in the same JSON line: the export + sort hand-over, a PCIe-inclusive pass (pinned host batches, copies
+resident in HBM; FASTQ parsing and PCIe are not in `value`.  A plain run sets up, warms up, times the steps and prints
+the line (with `roofline` from the timed steps' own events and the host-side conservation checks of the last one).
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).  Only with --full, measured once outside
+the timed steps and reported in the same JSON line: the device-side conservation checks (export digest, K3's last
+put), the export + sort hand-over, a PCIe-inclusive pass (pinned host batches, copies
 overlapped with the kernels), and `whole_command` -- the `SOAPdenovo-63mer pregraph` executable on a FASTQ prefix of
 the same read distribution written to local disk, its stages, and byte equality of its five files with the
-reference binary's (oracle/_ref), whose own timings are the `cpu_baseline`.
+reference binary's (oracle/_ref), whose own timings are the `cpu_baseline`; the passes at K = 127, of configs[1] and
+of trimmed reads (`k127`, `k31_config1`, `ragged`); the big whole-command legs (big_command).
 Workload = BASELINE.json configs[2] ("C. elegans-scale 200M x 150 bp synthetic, K=63, 1xMI355X"), the
 configuration the metric (K = 63) is quoted on; per-GPU work is fixed as N grows (weak scaling).
 Prints ONE JSON line on rank 0.
@@ -78,6 +82,103 @@ def library_source_sha():
         h.update(f.encode())
         h.update(open(os.path.join(ROOT, "soapdenovo2_amd", "csrc", f), "rb").read())
     return h.hexdigest()[:16]
+
+
+DUMP_SAMPLE_ROWS = 500_000          # --dump-outputs: distinct k-mers the sample aims at
+DUMP_MAX_BYTES = 60_000_000         # --dump-outputs: all files together (float64)
+
+
+def _s64(x):
+    return x - (1 << 64) if x >= 1 << 63 else x
+
+
+def _hip_runtime():
+    """The HIP runtime this process already runs on (torch's; the library shares it, api.lib())."""
+    import ctypes
+    path = next(l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64.so" in l)
+    hip = ctypes.CDLL(path)
+    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    hip.hipMemcpyAsync.restype = ctypes.c_int
+    return hip
+
+
+def sample_threshold(expected):
+    """A record is sampled when the top 24 bits of its key hash are below this: set by the arguments (the expected distinct count) only."""
+    return max(1, min(1 << 24, int(DUMP_SAMPLE_ROWS / max(expected, 1.0) * (1 << 24) + 0.5)))
+
+
+def key_hash(torch, recs, nw):
+    """Multiplicative hash of the key words of records [m, nw + 2] (int64, wrapping) -> its top 24 bits."""
+    c1, c2 = _s64(0x9E3779B97F4A7C15), _s64(0xBF58476D1CE4E5B9)
+    h = recs[:, 0] * c1
+    for w in range(1, nw):
+        h = (h ^ recs[:, w]) * c2
+    h = (h ^ torch.bitwise_right_shift(h, 31)) * c1
+    return torch.bitwise_right_shift(h, 40) & 0xFFFFFF
+
+
+def records_to_f64(rec, nw):
+    """uint64 records [m, nw + 2] -> rows in key order, each word as two float64 columns (high, low 32 bits: exact)."""
+    if len(rec):
+        rec = rec[np.lexsort([rec[:, w] for w in reversed(range(nw))])]
+    hi = (rec >> np.uint64(32)).astype(np.float64)
+    lo = (rec & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    return np.stack([hi, lo], axis=2).reshape(len(rec), 2 * rec.shape[1])
+
+
+def dump_outputs(torch, api, kc, engine, out_dir, expected, rank, dist=None):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step (after pg_finalize), as float64 .npy files:
+      coverage_histogram.npy   [256]  pg_finalize's coverage histogram (summed over the ranks);
+      kmer_records_sample.npy  [m, 2 * (nw + 2)]  a fixed sample of the distinct k-mers' records (key words, cnt word,
+                               set << 56 | first ordinal), rows in key order, each 64-bit word as (high, low) 32 bits.
+    A record is in the sample when a hash of its key words falls below sample_threshold(expected): the sample depends on the set
+    computed and the arguments, not on the order a build keeps its export array in, so two builds can be compared file for file."""
+    import ctypes as C
+    nw, rw = kc.nw, kc.nw + 2
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream()
+    hist = np.asarray(kc._last_hist, dtype=np.uint64).copy()
+    torch.cuda.synchronize()
+    owned, hip, buf = None, None, None
+    ptr, got = C.c_void_p(0), C.c_uint64(0)
+    if engine == 2:                                # the export array in place (valid until the next reset)
+        api._check(api.lib().pg_export_peek(kc.h, C.byref(ptr), C.byref(got)), "pg_export_peek")
+        base, n = ptr.value or 0, got.value
+        hip = _hip_runtime()
+    else:
+        n = kc.distinct()
+        owned = torch.empty(max(n, 1) * rw, dtype=torch.int64, device=dev)
+        api._check(api.lib().pg_export(kc.h, owned.data_ptr(), n, C.byref(got), kc._stream()), "pg_export")
+        base, n = owned.data_ptr(), got.value
+    thr = sample_threshold(expected)
+    chunk = 1 << 22
+    parts = []
+    for lo in range(0, n, chunk):
+        m = min(chunk, n - lo)
+        if owned is None:
+            if buf is None:
+                buf = torch.empty(min(chunk, n) * rw, dtype=torch.int64, device=dev)
+            rc = hip.hipMemcpyAsync(C.c_void_p(buf.data_ptr()), C.c_void_p(base + lo * rw * 8), m * rw * 8, 3, C.c_void_p(stream.cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"hipMemcpyAsync of the export array failed: error {rc}")
+            recs = buf[: m * rw].view(m, rw)
+        else:
+            recs = owned[lo * rw: (lo + m) * rw].view(m, rw)
+        parts.append(recs[key_hash(torch, recs, nw) < thr].cpu())       # (.cpu() waits: buf is free again)
+    sample = torch.cat(parts).numpy().view(np.uint64) if parts else np.zeros((0, rw), dtype=np.uint64)
+    del buf, owned
+    if dist is not None:
+        every = [None] * dist.get_world_size()
+        dist.all_gather_object(every, (hist, sample))
+        hist = sum(h for h, _ in every)
+        sample = np.concatenate([s for _, s in every])
+    if rank != 0:
+        return
+    out = records_to_f64(sample, nw)
+    out = out[: max(0, DUMP_MAX_BYTES - hist.nbytes) // (out.shape[1] * 8)]    # (the expected count was far too low: the first rows in key order)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "coverage_histogram.npy"), hist.astype(np.float64))
+    np.save(os.path.join(out_dir, "kmer_records_sample.npy"), out)
 
 
 def md5_outputs(prefix):
@@ -432,6 +533,10 @@ def main():
     ap.add_argument("--engine", type=int, default=2, help="2 = super-k-mer partitions counted in LDS (default), 1 = one DRAM-resident set")
     ap.add_argument("--comm", default="nccl", help="nccl (RCCL over xGMI) or gloo (test only: exchange staged through the host)")
     ap.add_argument("--share-gpu", action="store_true", help="test only: every rank uses cuda:0")
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline: device-side conservation checks, the whole-command legs and the "
+                                                        "reference's CPU baseline, the hand-over and PCIe-inclusive pass, the K = 127 / configs[1] / ragged passes "
+                                                        "(the --no-* switches above trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
 
     import torch
@@ -449,7 +554,7 @@ def main():
     # device_context_s 2.5 - 4 s; on its own 0.03 s) -- that is the neighbour's cost, not the command's.  Nothing of this touches
     # the timed region below.
     commands = {}
-    if world == 1 and args.engine == 2 and not args.no_cpu_baseline and args.whole_reads > 0:
+    if args.full and world == 1 and args.engine == 2 and not args.no_cpu_baseline and args.whole_reads > 0:
         # the reference's workers each scan the whole k-mer buffer (prlHashReads.c:79-90), so its pass 1 stops scaling long before a
         # 100+-core host is used up (-p 256 was slower than -p 16 in round 1); it runs at the same -p as the executable, which also
         # makes its files comparable byte for byte
@@ -626,9 +731,10 @@ def main():
     distinct = kc.distinct()                       # also raises if the set overflowed
     # ---- conservation check on the TIMED result (milliseconds; every rank, summed): the coverage histogram adds up to the
     # distinct k-mers, the nodes' coverage fields add up to the k-mer occurrences that went in (exact while no node
-    # saturates at 255, a lower bound otherwise), the latest put any set saw is the last k-mer of the last read
+    # saturates at 255, a lower bound otherwise), the latest put any set saw is the last k-mer of the last read.  The histogram's checks
+    # cost no device work; the export digest and K3's last put run only with --full.
     hist_t, _ = kc._last_hist, None
-    chk = kc.checksum() if engine == 2 else None
+    chk = kc.checksum() if engine == 2 and args.full else None
     cons_local = [int(hist_t.sum()), int((hist_t * np.arange(256, dtype=np.uint64)).sum()), int(hist_t[255]),
                   int(chk[6]) if chk is not None else -1, int(chk[7]) if chk is not None else -1, distinct]
     if world > 1:
@@ -636,7 +742,7 @@ def main():
         dist.all_reduce(t)
         cons_local = [int(x) for x in t.tolist()]
         distinct = cons_local[5]
-    last_timed = kc.last_put() if engine == 2 else None           # K3: a second expansion of every record (untimed)
+    last_timed = kc.last_put() if engine == 2 and args.full else None     # K3: a second expansion of every record (untimed)
     max_last = int(last_timed.max()) if last_timed is not None else -1
     if world > 1 and last_timed is not None:
         t = torch.tensor([max_last], dtype=torch.int64, device=dev)
@@ -656,10 +762,12 @@ def main():
     }
     conservation["ok"] = all(v is not False for v in conservation.values())
     digest_timed = [int(x) for x in chk[:6]] if chk is not None else None
+    if args.dump_outputs:                          # before anything below resets or takes the context
+        dump_outputs(torch, api, kc, engine, args.dump_outputs, expected * world, rank, dist if world > 1 else None)
 
     # ---- outside the timed steps (N = 1): the hand-over call_pregraph does after pass 1, and a PCIe-inclusive pass
     extras, st_snapshot = {}, None
-    if world == 1 and engine == 2 and not args.no_extras:
+    if args.full and world == 1 and engine == 2 and not args.no_extras:
         # (c) one pass with the batches coming from pinned host memory: two device buffers, copies on their own stream
         nb = min(args.batch_reads, n_reads)
         host = torch.empty(n_reads * wpr + 8, dtype=torch.int64, pin_memory=True)      # the whole packed input, page-locked
@@ -721,8 +829,8 @@ def main():
         api.hip_free(ws)
 
     k127 = k31 = ragged = None
-    want_ragged = world == 1 and engine == 2 and args.ragged_min_len > 0 and (not args.no_extras or args.ragged)
-    want_k127 = world == 1 and engine == 2 and K <= 63 and L >= 128 and not args.no_extras and not args.no_k127
+    want_ragged = args.full and world == 1 and engine == 2 and args.ragged_min_len > 0 and (not args.no_extras or args.ragged)
+    want_k127 = args.full and world == 1 and engine == 2 and K <= 63 and L >= 128 and not args.no_extras and not args.no_k127
     st_final = None
     if want_ragged or want_k127:
         st_final = st_snapshot if extras else kc.stats()

@@ -5,7 +5,7 @@
 #   tests[:<pytest -k expression>]   the -m gpu suite (or a subset)
 #   poison[:<pytest -k expression>]  the -m gpu suite (or a subset) with PG_ARENA_POISON=1: every arena block filled with 0xA5 as it is cut
 #   smoke                            __graft_entry__.smoke()
-#   bench[:<extra bench.py args>]    one bench.py line -> bench<i>.json (default arguments = the driver's run)
+#   bench[:<extra bench.py args>]    one `bench.py --full` line (headline + every leg) -> bench<i>.json
 #   stats[:<bench args>]             rocprofv3 --kernel-trace --stats of a kernels-only bench run -> kernel_stats<i>.csv
 #   pmc:<counters>[:<bench args>]    one rocprofv3 --pmc pass (comma-separated counters) of a short kernels-only run -> pmc<i>_*.csv
 #   phases[:<bench args>]            K2's phase cycles from the -DPG_MEASURE library (SOAPDENOVO2_AMD_LIB=..._measure.so, PG_K2_TIMERS=1)
@@ -21,7 +21,7 @@ O=gpurun_out/$TAG; mkdir -p "$O"
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
 i=0
-KERNELS_ONLY="--no-cpu-baseline --no-extras"
+KERNELS_ONLY="--full --no-cpu-baseline --no-extras"
 for step in "$@"; do
     i=$((i + 1))
     kind=${step%%:*}; arg=""; [ "$kind" != "$step" ] && arg=${step#*:}
@@ -36,7 +36,7 @@ for step in "$@"; do
     smoke)
         timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke$i.log" 2>&1; echo "[$i] smoke rc=$? $(tail -1 "$O/smoke$i.log")";;
     bench)
-        timeout 1500 python bench.py ${arg//,/ } > "$O/bench$i.json" 2> "$O/bench$i.err"; echo "[$i] bench rc=$?"
+        timeout 1500 python bench.py --full ${arg//,/ } > "$O/bench$i.json" 2> "$O/bench$i.err"; echo "[$i] bench rc=$?"
         python scripts/bench_digest.py "$O/bench$i.json";;
     stats)
         rm -rf /tmp/prof_$i; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$i -o s -- python bench.py $KERNELS_ONLY --no-k127 ${arg//,/ } > "$O/stats$i.json" 2> "$O/stats$i.err"; echo "[$i] stats rc=$?"

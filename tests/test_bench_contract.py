@@ -51,3 +51,27 @@ def test_every_whole_command_leg_has_its_expectation_in_profiles():
         j = json.load(open(os.path.join(ROOT, "profiles", f)))
         assert set(j["md5"]) >= {"kmerFreq", "preGraphBasic", "vertex", "preArc", "edge"}, f
         assert j.get("reference_wall_s", 0) > 100 and {"reads", "read_len", "genome", "err", "seed", "kmer", "sets", "a_gb"} <= set(j["workload"]), f
+
+
+def test_dumped_sample_is_exact_and_independent_of_the_export_order():
+    """--dump-outputs: a record is sampled by a hash of its key words against a threshold the arguments set, rows come out in key order, and every
+    64-bit word survives as two float64 columns -- so two builds that compute the same set write the same file, whatever order their export
+    array is in."""
+    import numpy as np
+    import torch
+    b = _bench()
+    rng = np.random.default_rng(5)
+    for nw in (2, 4):
+        rec = rng.integers(0, 1 << 62, size=(60000, nw + 2), dtype=np.int64).view(np.uint64) * np.uint64(3)
+        thr = b.sample_threshold(6 * b.DUMP_SAMPLE_ROWS)            # (a sixth of the records)
+        assert 0 < thr < 1 << 24 and b.sample_threshold(1) == 1 << 24 and b.sample_threshold(1e12) >= 1
+        t = torch.from_numpy(rec.view(np.int64))
+        keep = (b.key_hash(torch, t, nw) < thr).numpy()
+        assert 0.1 < keep.mean() < 0.25
+        perm = rng.permutation(len(rec))
+        keep_p = (b.key_hash(torch, t[perm], nw) < thr).numpy()
+        a, c = b.records_to_f64(rec[keep], nw), b.records_to_f64(rec[perm][keep_p], nw)
+        assert a.dtype == np.float64 and a.shape == (keep.sum(), 2 * (nw + 2)) and np.array_equal(a, c)
+        back = (a[:, 0::2].astype(np.uint64) << np.uint64(32)) | a[:, 1::2].astype(np.uint64)
+        want = rec[keep]
+        assert np.array_equal(back, want[np.lexsort([want[:, w] for w in reversed(range(nw))])])

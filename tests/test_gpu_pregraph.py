@@ -1061,7 +1061,7 @@ def test_cli_switches_do_not_change_the_files(golden, tmp_path, name, toggle):
 
 
 def test_bench_two_ranks_share_the_gpu_over_gloo(tmp_path):
-    """The N > 1 bench path end to end without an 8-GPU node: `torch.distributed.run --nproc-per-node 2 bench.py --gpus 2 --share-gpu
+    """The N > 1 bench path end to end without an 8-GPU node: `torch.distributed.run --nproc-per-node 2 bench.py --full --gpus 2 --share-gpu
     --comm gloo` -- two PROCESSES, one rank each, both on this GPU; the library's own pipelined pg_count_reads_sharded (cut, flags,
     records of round i travelling while batch i + 1 is cut, appends) over the host-staged transport (pg_comm_create_host + gloo
     all-to-all), every occurrence conserved across the ranks, and the line carries the exchange's time, volume and the owner rule."""
@@ -1070,7 +1070,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo(tmp_path):
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--comm", "gloo", "--reads", "2000000", "--batch-reads", "500000", "--steps", "2", "--warmup", "1"]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--comm", "gloo", "--reads", "2000000", "--batch-reads", "500000", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -1081,6 +1081,31 @@ def test_bench_two_ranks_share_the_gpu_over_gloo(tmp_path):
     ex = j["exchange"]
     assert ex["transport"] == "host" and ex["rounds_per_step"] == 4 and ex["host_waits_per_round"] <= 1.5, ex      # one host wait a round (two in the first)
     assert "minimizer partition mod 2" in j["config"]["parallelism"] and "reference set id mod 2" in j["config"]["parallelism"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): the headline keys, --steps timed steps, none of the --full legs; --dump-outputs writes the last timed
+    step's coverage histogram and its sample of the distinct k-mers as float64 .npy under 64 MB -- the same files whatever --steps / --warmup."""
+    import json, sys
+    outs = []
+    for steps, warm in ((2, 1), (1, 0)):
+        d = tmp_path / f"dump{steps}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm), "--reads", "2000000",
+               "--genome", "4600000", "--batch-reads", "500000", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert j["steps"] == steps and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "reads/s" and j["higher_is_better"] is True
+        assert j["conservation"]["ok"] and not {"whole_command", "cpu_baseline", "k127", "k31_config1", "ragged", "pass1_hand_over"} & set(j)
+        files = sorted(os.listdir(d))
+        assert files == ["coverage_histogram.npy", "kmer_records_sample.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        hist, rec = np.load(d / files[0]), np.load(d / files[1])
+        assert hist.dtype == rec.dtype == np.float64 and hist.shape == (256,)
+        assert int(hist.sum()) == j["config"]["distinct_kmers"] and int((hist * np.arange(256)).sum()) == j["conservation"]["sum_of_coverage_histogram"]
+        assert rec.shape[1] == 8 and 0 < len(rec) < j["config"]["distinct_kmers"]
+        outs.append((hist, rec))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
 
 
 def test_suite_subset_on_poisoned_arena_blocks():
