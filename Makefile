@@ -1,4 +1,4 @@
-# Builds libsoapdenovo2_amd.so (C ABI of include/soapdenovo2_amd.h) and the two pregraph executables for gfx950.
+# Builds libsoapdenovo2_amd.so (C ABI of include/soapdenovo2_amd.h) and the two pregraph / map executables for gfx950.
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC    := soapdenovo2_amd/csrc
@@ -23,8 +23,8 @@ else
 O       := o
 LIBNAME := libsoapdenovo2_amd.so
 endif
-HOSTOBJ := $(CSRC)/host_graph.$(O) $(CSRC)/host_reads.$(O) $(CSRC)/call_pregraph.$(O) $(CSRC)/host_skm.$(O) $(CSRC)/host_emu.$(O) $(CSRC)/host_plan.$(O) $(CSRC)/arena.$(O)
-DEVOBJ  := $(CSRC)/pregraph_kernels.$(O) $(CSRC)/partition_kernels.$(O) $(CSRC)/graph_kernels.$(O) $(CSRC)/sort_records.$(O) $(CSRC)/exchange.$(O)
+HOSTOBJ := $(CSRC)/host_graph.$(O) $(CSRC)/host_reads.$(O) $(CSRC)/call_pregraph.$(O) $(CSRC)/host_skm.$(O) $(CSRC)/host_emu.$(O) $(CSRC)/host_plan.$(O) $(CSRC)/arena.$(O) $(CSRC)/call_map.$(O) $(CSRC)/map_host.$(O)
+DEVOBJ  := $(CSRC)/pregraph_kernels.$(O) $(CSRC)/partition_kernels.$(O) $(CSRC)/graph_kernels.$(O) $(CSRC)/sort_records.$(O) $(CSRC)/exchange.$(O) $(CSRC)/map_kernels.$(O)
 HDRS    := $(wildcard $(CSRC)/*.hpp) include/soapdenovo2_amd.h
 
 ifeq ($(MEASURE),1)

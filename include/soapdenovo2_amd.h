@@ -58,6 +58,19 @@ const char *pg_version(void);
 int call_pregraph(int argc, char **argv);
 int call_pregraph_127mer(int argc, char **argv);
 
+/* The `map` stage: same signature, argv grammar ("s:g:K:p:k:h:f"), output files and exit behaviour as the reference's
+ * `int call_align(int argc, char **argv)` (standardPregraph/map.c:94; reached from main.c for `map`):
+ *   map -s configFile -g inputGraph [-f] [-p n_cpu] [-k kmer_R2C] [-h contig_total_length]
+ * Reads <g>.contig, <g>.ContigIndex, <g>.preGraphBasic; writes <g>.readOnContig.gz, <g>.readInGap.gz, <g>.peGrads and with -f
+ * <g>.shortreadInGap.gz, <g>.PEreadOnContig.gz (prlHashCtg.c, prlRead2Ctg.c).  -p only decides the reference's leftover bits in the
+ * 2-bit read images of readInGap / PEreadOnContig, which are reproduced.  The contig k-mer index and the read -> contig decision run
+ * on the first HIP device of SOAPDENOVO2_AMD_DEVICES (or SOAPDENOVO2_AMD_DEVICE, default 0).  Long-read libraries (asm_flags=4,
+ * prlLongRead2Ctg) are refused with a message and a nonzero return before anything is written.
+ * call_align        = behaviour of the SOAPdenovo-63mer binary (map.c:call_align built without MER127)
+ * call_align_127mer = behaviour of the SOAPdenovo-127mer binary (map.c:call_align built with MER127) */
+int call_align(int argc, char **argv);
+int call_align_127mer(int argc, char **argv);
+
 /* ------------------------------------------------------------------------------------------------
  * Common record type: one distinct canonical k-mer after pass 1.
  *   key[0..nw)  k-mer words, most significant first (nw = 2 for the 63-mer flavour, 4 for the 127-mer one)
@@ -517,6 +530,17 @@ int pg_host_emu_clip_tips(const uint64_t *records, uint64_t n_records, const uin
  * the 127-mer build) as the graph stages' lookups and both device layouts compute it: by a precomputed reciprocal of the size
  * instead of the compiler's 64-bit `%` (csrc/graph_lookup.hpp: ModConst, rem128).  keys = n x (mer127 ? 4 : 2) words. */
 int pg_host_emu_home_slots(const uint64_t *keys, uint64_t n, int mer127, uint64_t size, uint64_t *out);
+
+/* The `map` stage's two operators on caller-owned host arrays, for tests: the contig k-mer index of n_ctg contigs (each of K + 2 bases
+ * or more, packed with pg_pack_read, contig i at ctg_words + ctg_off[i], ctg_off[n_ctg] = words in all; its k-mers carry ctg_ids[i])
+ * and one batch of reads mapped with it (parse1read with ALIGNLEN = align_len).  id_len / id_bal = length and bal_edge of every
+ * contig id (basicContigInfo, prlRead2Ctg.c:727-770), n_ids entries.  Per read: contig id after getTwinCtg (0 = not mapped),
+ * position, orientation ('+' / '-'; 0 when not mapped) and footprint.  device >= 0: the HIP kernels on that device; device = -1:
+ * their host twin (the same table and the same decision code). */
+int pg_map_reads(int device, int K, int mer127, const uint64_t *ctg_words, const uint64_t *ctg_off, const int32_t *ctg_len_bases,
+                 const uint32_t *ctg_ids, uint64_t n_ctg, const int32_t *id_len, const int8_t *id_bal, uint32_t n_ids,
+                 const uint64_t *read_words, const uint64_t *read_off, const int32_t *read_len, uint64_t n_reads, int align_len,
+                 uint32_t *out_ctg, int32_t *out_pos, uint8_t *out_orien, uint8_t *out_footprint);
 
 #ifdef __cplusplus
 }

@@ -4,8 +4,8 @@ Python is plumbing here (tests, bench.py, the multi-GPU launcher): the product i
 the SOAPdenovo-63mer / SOAPdenovo-127mer executables next to it.  There is no Python or CPU fallback for the
 device operators: if the library is missing, or no HIP device is usable, the calls raise.
 
-Mirrors the reference's entry point `int call_pregraph(int argc, char **argv)`
-(standardPregraph/pregraph.c:62) as :func:`call_pregraph`.
+Mirrors the reference's entry points `int call_pregraph(int argc, char **argv)` (standardPregraph/pregraph.c:62) as
+:func:`call_pregraph` and `int call_align(int argc, char **argv)` (standardPregraph/map.c:94) as :func:`call_map`.
 """
 from __future__ import annotations
 
@@ -59,6 +59,10 @@ def lib() -> C.CDLL:
     L.pg_version.restype = C.c_char_p
     L.call_pregraph.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.call_pregraph_127mer.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
+    L.call_align.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
+    L.call_align_127mer.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
+    L.pg_map_reads.argtypes = [C.c_int, C.c_int, C.c_int, u64p, u64p, u64p, u64p, C.c_uint64, u64p, u64p, C.c_uint32,
+                               u64p, u64p, u64p, C.c_uint64, C.c_int, u64p, u64p, u64p, u64p]
     L.pg_packed_words.restype = C.c_size_t
     L.pg_packed_words.argtypes = [C.c_uint32]
     L.pg_pack_read.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -168,6 +172,7 @@ EXPORTED_SYMBOLS = [
     "pg_exchange_gather_records", "pg_count_reads_sharded", "pg_host_skm_cut", "pg_host_skm_expand",
     "pg_host_emu_layout_static", "pg_graph_begin_device", "pg_host_emu_clip_tips", "pg_exchange_regroup_by_set", "pg_comm_regroup_stats", "pg_graph_begin_sharded", "pg_host_regroup_plan", "pg_host_bam_pair_state", "pg_device_scratch_offer", "pg_device_scratch_withdraw", "pg_host_emu_layout_growable", "pg_exchange_regroup_by_set_ws", "pg_host_edge_file_in_background", "pg_graph_add_packed_device", "pg_host_emu_home_slots", "pg_comm_pipeline_stats", "pg_comm_create_host", "pg_comm_flush",
     "pg_set_read_len_bound", "pg_graph_add_packed_device_ragged", "pg_expect", "pg_host_plan_memory", "pg_create_planned", "pg_graph_add_packed_device_segments",
+    "call_align", "call_align_127mer", "pg_map_reads",
 ]
 
 
@@ -208,6 +213,47 @@ def call_pregraph(args: Sequence[str], mer127: bool = False, in_process: bool = 
         fn = lib().call_pregraph_127mer if mer127 else lib().call_pregraph
         return fn(len(argv), arr)
     return subprocess.run([binary(mer127), "pregraph"] + [str(a) for a in args]).returncode
+
+
+def call_map(args: Sequence[str], mer127: bool = False, in_process: bool = False, env=None) -> int:
+    """`map <args>` (the reference's call_align, standardPregraph/map.c:94); args as for the reference, e.g.
+    ["-s", cfg, "-g", prefix, "-p", "8", "-f"].  Runs the executable in a child process unless in_process=True."""
+    if in_process:
+        argv = [b"map"] + [str(a).encode() for a in args]
+        arr = (C.c_char_p * (len(argv) + 1))(*argv, None)
+        fn = lib().call_align_127mer if mer127 else lib().call_align
+        return fn(len(argv), arr)
+    return subprocess.run([binary(mer127), "map"] + [str(a) for a in args], env=env).returncode
+
+
+def _pack_many(seqs):
+    """pg_pack_read's layout for a list of base-code arrays: (words, word offsets [n + 1], lengths)."""
+    lens = np.array([len(s) for s in seqs], dtype=np.int32)
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum((lens.astype(np.uint64) + 31) // 32)
+    words = np.zeros(int(off[-1]) + 1, dtype=np.uint64)
+    for i, s in enumerate(seqs):
+        s = np.asarray(s, dtype=np.uint64) & np.uint64(3)
+        pos = np.arange(len(s))
+        np.bitwise_or.at(words, off[i] + (pos >> 5).astype(np.uint64), s << (np.uint64(62) - np.uint64(2) * (pos & 31).astype(np.uint64)))
+    return words, off, lens
+
+
+def map_reads(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, mer127: bool = False, device: int = 0):
+    """The `map` stage's index + read kernel on one batch (pg_map_reads): contigs (base-code arrays, each of K + 2 bases or more) with
+    their ids, the length / bal_edge of every contig id, reads (base-code arrays).  device = -1 runs the host twin.  Returns
+    (ctg, pos, orien, footprint) arrays, one entry a read."""
+    cw, co, cl = _pack_many(contigs)
+    rw, ro, rl = _pack_many(reads)
+    ids = np.ascontiguousarray(ctg_ids, dtype=np.uint32)
+    il = np.ascontiguousarray(id_len, dtype=np.int32)
+    ib = np.ascontiguousarray(id_bal, dtype=np.int8)
+    n = len(reads)
+    ctg = np.zeros(n, np.uint32); pos = np.zeros(n, np.int32); ori = np.zeros(n, np.uint8); fp = np.zeros(n, np.uint8)
+    p = lambda a: a.ctypes.data
+    _check(lib().pg_map_reads(device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
+                              p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp)), "pg_map_reads")
+    return ctg, pos, ori, fp
 
 
 # ---------------------------------------------------------------------------------------------------------

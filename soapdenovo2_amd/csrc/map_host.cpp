@@ -1,0 +1,156 @@
+// map_host.cpp -- host twin of map_kernels.hip: the same contig k-mer index (map_index.hpp) built by one thread, the same per-read
+// decision (map_decide.hpp) over host threads.  What the CPU tests run, and the device path's yardstick (pg_map_reads, device = -1).
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/soapdenovo2_amd.h"
+#include "extract.hpp"
+#include "host_reads.hpp"
+#include "map_index.hpp"
+
+void pg_set_error(const std::string& s);
+
+namespace pg {
+namespace {
+
+template <int NW>
+struct HostIndex {
+    std::vector<uint64_t> tab;
+    uint64_t mask = 0;
+    void build(const MapContigs& c, int K) {
+        constexpr int SW = map_slot_words<NW>();
+        const uint64_t slots = map_table_slots(c.n_kmers);
+        mask = slots - 1;
+        tab.assign(slots * SW, 0);
+        const Kmer<NW> filter = kmer_filter<NW>(K);
+        for (size_t i = 0; i < c.len.size(); i++) {
+            const uint64_t* rd = c.words.data() + c.off[i];
+            const int nk = c.len[i] - K + 1;
+            Kmer<NW> word = read_kmer<NW>(rd, 0, K, filter), bal = kmer_rc<NW>(word, K);
+            for (int j = 0; j < nk; j++) {
+                if (j) kmer_roll<NW>(word, bal, read_base(rd, j + K - 1), K, filter);
+                const bool sm = kmer_less<NW>(word, bal);
+                const Kmer<NW>& ck = sm ? word : bal;
+                uint64_t e = map_home<NW>(ck, mask);
+                for (;;) {
+                    uint64_t* sl = tab.data() + e * SW;
+                    if (sl[NW + 1] == MAP_EMPTY) {
+                        for (int q = 0; q < NW; q++) sl[q] = ck.w[q];
+                        sl[NW] = map_hit(c.id[i], (uint32_t)j, sm ? 0 : 1, 0);
+                        sl[NW + 1] = MAP_ONCE;
+                        break;
+                    }
+                    bool eq = true;
+                    for (int q = 0; q < NW; q++) eq = eq && sl[q] == ck.w[q];
+                    if (eq) { sl[NW + 1] = MAP_DELETED; break; }
+                    e = (e + 1) & mask;
+                }
+            }
+        }
+    }
+    uint64_t find(const Kmer<NW>& ck, bool sm) const {
+        constexpr int SW = map_slot_words<NW>();
+        uint64_t e = map_home<NW>(ck, mask);
+        for (;;) {
+            const uint64_t* sl = tab.data() + e * SW;
+            if (sl[NW + 1] == MAP_EMPTY) return 0;
+            bool eq = true;
+            for (int q = 0; q < NW; q++) eq = eq && sl[q] == ck.w[q];
+            if (eq) return sl[NW + 1] == MAP_DELETED ? 0 : sl[NW] | ((uint64_t)(sm ? 1 : 0) << 32);
+            e = (e + 1) & mask;
+        }
+    }
+};
+
+template <int NW>
+class HostMapEngine : public MapEngine {
+public:
+    explicit HostMapEngine(int K) : K_(K) {}
+    int build(const MapContigs& c, const int32_t* ctg_len, const int8_t* bal, uint32_t n_ids) override {
+        len_.assign(ctg_len, ctg_len + n_ids);
+        bal_.assign(bal, bal + n_ids);
+        idx_.build(c, K_);
+        return PG_OK;
+    }
+    int map(const MapBatch& b, int align_len, MapOut* out) override {
+        const MapCtgs ctgs{len_.data(), bal_.data(), (uint32_t)len_.size()};
+        const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)host_threads(0), (b.n + 1023) / 1024));
+        auto body = [&](int t) {
+            std::vector<uint64_t> row;
+            const Kmer<NW> filter = kmer_filter<NW>(K_);
+            for (uint64_t r = b.n * t / nt; r < b.n * (t + 1) / nt; r++) {
+                const int len = b.len[r];
+                const int nk = len >= K_ + 1 ? len - K_ + 1 : 0;
+                row.assign((size_t)nk, 0);
+                if (nk) {
+                    const uint64_t* rd = b.words + b.off[r];
+                    Kmer<NW> word = read_kmer<NW>(rd, 0, K_, filter), bal = kmer_rc<NW>(word, K_);
+                    for (int j = 0; j < nk; j++) {
+                        if (j) kmer_roll<NW>(word, bal, read_base(rd, j + K_ - 1), K_, filter);
+                        const bool sm = kmer_less<NW>(word, bal);
+                        row[(size_t)j] = idx_.find(sm ? word : bal, sm);
+                    }
+                }
+                const uint64_t* p = row.data();
+                out[r] = map_decide([p](int j) { return p[j]; }, nk, K_, map_multi(len, align_len, K_), ctgs);
+            }
+        };
+        std::vector<std::thread> th;
+        for (int t = 1; t < nt; t++) th.emplace_back(body, t);
+        body(0);
+        for (auto& x : th) x.join();
+        return PG_OK;
+    }
+
+private:
+    int K_;
+    HostIndex<NW> idx_;
+    std::vector<int32_t> len_;
+    std::vector<int8_t> bal_;
+};
+
+}  // namespace
+
+std::unique_ptr<MapEngine> map_engine_host(int K, int nw) {
+    if (nw == 2) return std::unique_ptr<MapEngine>(new HostMapEngine<2>(K));
+    return std::unique_ptr<MapEngine>(new HostMapEngine<4>(K));
+}
+
+}  // namespace pg
+
+// pg_map_reads (include/soapdenovo2_amd.h): one index, one batch
+extern "C" int pg_map_reads(int device, int K, int mer127, const uint64_t* ctg_words, const uint64_t* ctg_off, const int32_t* ctg_len_bases,
+                            const uint32_t* ctg_ids, uint64_t n_ctg, const int32_t* id_len, const int8_t* id_bal, uint32_t n_ids,
+                            const uint64_t* read_words, const uint64_t* read_off, const int32_t* read_len, uint64_t n_reads, int align_len,
+                            uint32_t* out_ctg, int32_t* out_pos, uint8_t* out_orien, uint8_t* out_footprint) {
+    const int nw = mer127 ? 4 : 2;
+    if (K < 1 || K > (mer127 ? 127 : 63)) { pg_set_error("pg_map_reads: K out of range"); return PG_EINVAL; }
+    pg::MapContigs c;
+    c.off.assign(ctg_off, ctg_off + n_ctg + 1);
+    c.len.assign(ctg_len_bases, ctg_len_bases + n_ctg);
+    c.id.assign(ctg_ids, ctg_ids + n_ctg);
+    c.words.assign(ctg_words, ctg_words + (n_ctg ? ctg_off[n_ctg] : 0));
+    c.words.resize(c.words.size() + 8, 0);
+    for (uint64_t i = 0; i < n_ctg; i++) {
+        if (c.len[i] < K + 2) { pg_set_error("pg_map_reads: the index takes contigs of K + 2 bases or more only"); return PG_EINVAL; }
+        c.n_kmers += (uint64_t)(c.len[i] - K + 1);
+    }
+    std::unique_ptr<pg::MapEngine> e = device < 0 ? pg::map_engine_host(K, nw) : pg::map_engine_device(device, K, nw);
+    if (!e) return PG_ENODEV;
+    int rc = e->build(c, id_len, id_bal, n_ids);
+    if (rc) return rc;
+    std::vector<uint64_t> words(read_words, read_words + (n_reads ? read_off[n_reads] : 0)), koff(n_reads + 1, 0);
+    words.resize(words.size() + 8, 0);
+    for (uint64_t r = 0; r < n_reads; r++) koff[r + 1] = koff[r] + (read_len[r] >= K + 1 ? (uint64_t)(read_len[r] - K + 1) : 0);
+    std::vector<pg::MapOut> out(n_reads);
+    rc = e->map(pg::MapBatch{words.data(), words.size(), read_off, read_len, koff.data(), n_reads}, align_len, out.data());
+    if (rc) return rc;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        out_ctg[r] = out[r].ctg; out_pos[r] = out[r].pos; out_orien[r] = out[r].orien; out_footprint[r] = out[r].footprint;
+    }
+    return PG_OK;
+}

@@ -1,0 +1,79 @@
+// map_index.hpp -- the contig k-mer index of the `map` stage and the two engines that map reads with it (device: map_kernels.hip,
+// host twin: map_host.cpp).
+//
+// The reference (prlContig2nodes, prlHashCtg.c:345-467) puts every canonical K-mer of every contig of K + 2 bases or more into its k-mer
+// sets: the first put keeps (contig id, position, twin), a second put of the same key marks it deleted (singleKmer, :131-155), and a deleted
+// key reads as "no node" (searchKmer, prlRead2Ctg.c:233-246).  Which put comes first only matters for keys that end up deleted, so the
+// index does not depend on insertion order, on -p, or on the sets' layout: here it is one open-addressing table, built fully in parallel.
+//   slot = NW key words | value | state        value = map_hit(ctg, pos, twin, 0) (map_decide.hpp)
+//   state: 0 empty, 1 claimed (key being written), 2 one put, 3 two puts or more (deleted)
+#pragma once
+#include <stdint.h>
+#include <memory>
+#include <vector>
+
+#include "kmer.hpp"
+#include "map_decide.hpp"
+
+namespace pg {
+
+template <int NW> PG_HD constexpr int map_slot_words() { return NW + 2; }
+constexpr uint64_t MAP_EMPTY = 0, MAP_CLAIMED = 1, MAP_ONCE = 2, MAP_DELETED = 3;
+
+// home slot of a canonical key (splitmix64's finaliser over the words)
+template <int NW>
+PG_HD uint64_t map_home(const Kmer<NW>& k, uint64_t mask) {
+    uint64_t h = 0x9E3779B97F4A7C15ULL;
+#pragma unroll
+    for (int i = 0; i < NW; i++) {
+        h ^= k.w[i] + 0x9E3779B97F4A7C15ULL + (h << 6) + (h >> 2);
+        h ^= h >> 30; h *= 0xBF58476D1CE4E5B9ULL;
+        h ^= h >> 27; h *= 0x94D049BB133111EBULL;
+        h ^= h >> 31;
+    }
+    return h & mask;
+}
+
+// slots of the table for n k-mers: a power of two, at most half full
+inline uint64_t map_table_slots(uint64_t n_kmers) {
+    uint64_t s = 1024;
+    while (s < 2 * n_kmers) s <<= 1;
+    return s;
+}
+
+// Contigs as the index takes them: those of K + 2 bases or more, packed with pg_pack_read's layout (every contig on a word boundary,
+// `words` padded with NW + 1 zero words), with the id each one's k-mers carry (getID of the name, or the ordinal; prlHashCtg.c:436).
+struct MapContigs {
+    std::vector<uint64_t> words;
+    std::vector<uint64_t> off;            // [n + 1] word offsets
+    std::vector<int32_t> len;
+    std::vector<uint32_t> id;
+    uint64_t n_kmers = 0;
+};
+
+// A batch of reads, packed the same way; kmer_off[r] = k-mers of the reads before r (reads shorter than K + 1 have none).
+struct MapBatch {
+    const uint64_t* words;
+    uint64_t n_words;
+    const uint64_t* off;
+    const int32_t* len;
+    const uint64_t* kmer_off;             // [n + 1]
+    uint64_t n;
+};
+
+class MapEngine {
+public:
+    virtual ~MapEngine() {}
+    // build the index of `c`; ctg_len / bal = basicContigInfo's arrays, indexed by contig id (n_ids entries)
+    virtual int build(const MapContigs& c, const int32_t* ctg_len, const int8_t* bal, uint32_t n_ids) = 0;
+    // map a batch: out[r] = parse1read of read r with the batch's ALIGNLEN
+    virtual int map(const MapBatch& b, int align_len, MapOut* out) = 0;
+    // seconds spent building the index / in the read kernel (device: measured by events), for the stage's report
+    double t_index = 0, t_kernel = 0, t_copy = 0;
+};
+
+// K and the flavour (nw = 2: the 63-mer build, 4: the 127-mer build)
+std::unique_ptr<MapEngine> map_engine_device(int device, int K, int nw);
+std::unique_ptr<MapEngine> map_engine_host(int K, int nw);
+
+}  // namespace pg

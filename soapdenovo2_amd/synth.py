@@ -101,6 +101,43 @@ def write_fastq(path: str, codes: np.ndarray, name_prefix: str = "r") -> None:
         f.write(blob)
 
 
+def paired_codes(genome_len: int, n_pairs: int, read_len: int, ins: int, err: float, seed: int, genome=None):
+    """Paired-end reads off one random genome: fragments of `ins` bases (uniform start, strand flipped with p=0.5); mate 1 = the
+    fragment's first read_len bases, mate 2 = the reverse complement of its last read_len bases.  Returns (mate1, mate2), each an
+    (n_pairs, read_len) uint8 array of base codes."""
+    rng = np.random.default_rng(seed)
+    g = rng.integers(0, 4, size=genome_len, dtype=np.uint8) if genome is None else np.asarray(genome, dtype=np.uint8)
+    ins = max(ins, read_len)
+    starts = rng.integers(0, len(g) - ins, size=n_pairs, dtype=np.int64)
+    frag = g[starts[:, None] + np.arange(ins, dtype=np.int64)[None, :]]
+    flip = rng.random(n_pairs) < 0.5
+    frag = np.where(flip[:, None], (frag[:, ::-1] ^ 2), frag).astype(np.uint8)
+    m1 = frag[:, :read_len]
+    m2 = (frag[:, ins - read_len:][:, ::-1] ^ 2).astype(np.uint8)
+    out = []
+    for m in (m1, m2):
+        if err > 0:
+            mask = rng.random(m.shape) < err
+            shift = rng.integers(1, 4, size=m.shape, dtype=np.uint8)
+            m = np.where(mask, (m + shift) & 3, m).astype(np.uint8)
+        out.append(np.ascontiguousarray(m))
+    return out[0], out[1]
+
+
+def write_fastq_pair(path1: str, path2: str, mate1, mate2, name_prefix: str = "p", fasta: bool = False,
+                     lower_every: int = 0, n_every: int = 0, dot_every: int = 0) -> None:
+    """Write two mate files (FASTQ, or FASTA with fasta=True) with names `<prefix><i>/1` and `<prefix><i>/2`.  mate1 / mate2 are
+    lists (or 2-D arrays) of base-code arrays, one read each, of any lengths.  lower_every / n_every / dot_every as in
+    _fastq_blob: every n-th read in lower case, with an 'N' or a '.'."""
+    for path, mates, tag in ((path1, mate1, b"/1"), (path2, mate2, b"/2")):
+        names = [name_prefix.encode() + str(i).encode() + tag for i in range(len(mates))]
+        chunks = _fastq_blob(list(mates), names, lower_every, n_every, dot_every)
+        if fasta:
+            chunks = [b">" + c.split(b"\n")[0][1:] + b"\n" + c.split(b"\n")[1] + b"\n" for c in chunks]
+        with open(path, "wb") as f:
+            f.write(b"".join(chunks))
+
+
 def write_fastq_fast(path: str, codes: np.ndarray) -> None:
     """write_fastq for millions of reads: fixed-width names (`@r000000123`), one numpy block, no Python loop."""
     n, L = codes.shape
