@@ -35,6 +35,7 @@ extern "C" {
 #define PG_ENOMEM (-3)   /* host or device allocation failed, or table full and cannot grow */
 #define PG_EIO (-4)      /* file error */
 #define PG_ESTATE (-5)   /* call order violated */
+#define PG_ESPIN (-6)    /* a device lane gave up waiting on another lane's unfinished write (bounded spin); nothing was produced */
 
 const char *pg_last_error(void);
 const char *pg_version(void);
@@ -541,6 +542,15 @@ int pg_map_reads(int device, int K, int mer127, const uint64_t *ctg_words, const
                  const uint32_t *ctg_ids, uint64_t n_ctg, const int32_t *id_len, const int8_t *id_bal, uint32_t n_ids,
                  const uint64_t *read_words, const uint64_t *read_off, const int32_t *read_len, uint64_t n_reads, int align_len,
                  uint32_t *out_ctg, int32_t *out_pos, uint8_t *out_orien, uint8_t *out_footprint);
+
+/* pg_map_reads that also returns what the read kernel left for every k-mer of the batch, for tests: kmer_off[r] (n_reads + 1 entries) =
+ * k-mers of the reads before r (a read shorter than K + 1 has none), and rows[kmer_off[r] + j] = the hit word of k-mer j of read r
+ * (csrc/map_decide.hpp: 0 for an absent or deleted key, else id | (pos << 2 | twin << 1 | smaller) << 32).  rows must hold
+ * sum(max(0, len - K + 1) over reads of K + 1 bases or more) words.  device >= 0: the device's hit buffer copied back. */
+int pg_map_hits(int device, int K, int mer127, const uint64_t *ctg_words, const uint64_t *ctg_off, const int32_t *ctg_len_bases,
+                const uint32_t *ctg_ids, uint64_t n_ctg, const int32_t *id_len, const int8_t *id_bal, uint32_t n_ids,
+                const uint64_t *read_words, const uint64_t *read_off, const int32_t *read_len, uint64_t n_reads, int align_len,
+                uint32_t *out_ctg, int32_t *out_pos, uint8_t *out_orien, uint8_t *out_footprint, uint64_t *rows, uint64_t *kmer_off);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,7 @@ def lib() -> C.CDLL:
     L.call_align_127mer.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
     L.pg_map_reads.argtypes = [C.c_int, C.c_int, C.c_int, u64p, u64p, u64p, u64p, C.c_uint64, u64p, u64p, C.c_uint32,
                                u64p, u64p, u64p, C.c_uint64, C.c_int, u64p, u64p, u64p, u64p]
+    L.pg_map_hits.argtypes = list(L.pg_map_reads.argtypes) + [u64p, u64p]
     L.pg_packed_words.restype = C.c_size_t
     L.pg_packed_words.argtypes = [C.c_uint32]
     L.pg_pack_read.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -172,7 +173,7 @@ EXPORTED_SYMBOLS = [
     "pg_exchange_gather_records", "pg_count_reads_sharded", "pg_host_skm_cut", "pg_host_skm_expand",
     "pg_host_emu_layout_static", "pg_graph_begin_device", "pg_host_emu_clip_tips", "pg_exchange_regroup_by_set", "pg_comm_regroup_stats", "pg_graph_begin_sharded", "pg_host_regroup_plan", "pg_host_bam_pair_state", "pg_device_scratch_offer", "pg_device_scratch_withdraw", "pg_host_emu_layout_growable", "pg_exchange_regroup_by_set_ws", "pg_host_edge_file_in_background", "pg_graph_add_packed_device", "pg_host_emu_home_slots", "pg_comm_pipeline_stats", "pg_comm_create_host", "pg_comm_flush",
     "pg_set_read_len_bound", "pg_graph_add_packed_device_ragged", "pg_expect", "pg_host_plan_memory", "pg_create_planned", "pg_graph_add_packed_device_segments",
-    "call_align", "call_align_127mer", "pg_map_reads",
+    "call_align", "call_align_127mer", "pg_map_reads", "pg_map_hits",
 ]
 
 
@@ -254,6 +255,25 @@ def map_reads(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, m
     _check(lib().pg_map_reads(device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
                               p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp)), "pg_map_reads")
     return ctg, pos, ori, fp
+
+
+def map_hits(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, mer127: bool = False, device: int = 0):
+    """map_reads that also returns the hit word of every k-mer (pg_map_hits): (ctg, pos, orien, footprint, rows, kmer_off); read r's hit
+    words are rows[kmer_off[r]:kmer_off[r + 1]] (csrc/map_decide.hpp gives their layout; 0 = absent or deleted key)."""
+    cw, co, cl = _pack_many(contigs)
+    rw, ro, rl = _pack_many(reads)
+    ids = np.ascontiguousarray(ctg_ids, dtype=np.uint32)
+    il = np.ascontiguousarray(id_len, dtype=np.int32)
+    ib = np.ascontiguousarray(id_bal, dtype=np.int8)
+    n = len(reads)
+    ctg = np.zeros(n, np.uint32); pos = np.zeros(n, np.int32); ori = np.zeros(n, np.uint8); fp = np.zeros(n, np.uint8)
+    n_k = int(sum(max(0, int(l) - K + 1) for l in rl if l >= K + 1))
+    rows = np.full(n_k + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)         # (every word must be written: 0 is an answer)
+    koff = np.zeros(n + 1, np.uint64)
+    p = lambda a: a.ctypes.data
+    _check(lib().pg_map_hits(device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
+                             p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp), p(rows), p(koff)), "pg_map_hits")
+    return ctg, pos, ori, fp, rows[:n_k], koff
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -76,7 +76,7 @@ public:
         idx_.build(c, K_);
         return PG_OK;
     }
-    int map(const MapBatch& b, int align_len, MapOut* out) override {
+    int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out) override {
         const MapCtgs ctgs{len_.data(), bal_.data(), (uint32_t)len_.size()};
         const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)host_threads(0), (b.n + 1023) / 1024));
         auto body = [&](int t) {
@@ -96,6 +96,7 @@ public:
                     }
                 }
                 const uint64_t* p = row.data();
+                if (rows_out && nk) memcpy(rows_out + b.kmer_off[r], p, (size_t)nk * sizeof(uint64_t));
                 out[r] = map_decide([p](int j) { return p[j]; }, nk, K_, map_multi(len, align_len, K_), ctgs);
             }
         };
@@ -122,13 +123,14 @@ std::unique_ptr<MapEngine> map_engine_host(int K, int nw) {
 
 }  // namespace pg
 
-// pg_map_reads (include/soapdenovo2_amd.h): one index, one batch
-extern "C" int pg_map_reads(int device, int K, int mer127, const uint64_t* ctg_words, const uint64_t* ctg_off, const int32_t* ctg_len_bases,
-                            const uint32_t* ctg_ids, uint64_t n_ctg, const int32_t* id_len, const int8_t* id_bal, uint32_t n_ids,
-                            const uint64_t* read_words, const uint64_t* read_off, const int32_t* read_len, uint64_t n_reads, int align_len,
-                            uint32_t* out_ctg, int32_t* out_pos, uint8_t* out_orien, uint8_t* out_footprint) {
+// pg_map_reads / pg_map_hits (include/soapdenovo2_amd.h): one index, one batch
+static int map_one_batch(const char* who, int device, int K, int mer127, const uint64_t* ctg_words, const uint64_t* ctg_off,
+                         const int32_t* ctg_len_bases, const uint32_t* ctg_ids, uint64_t n_ctg, const int32_t* id_len, const int8_t* id_bal,
+                         uint32_t n_ids, const uint64_t* read_words, const uint64_t* read_off, const int32_t* read_len, uint64_t n_reads,
+                         int align_len, uint32_t* out_ctg, int32_t* out_pos, uint8_t* out_orien, uint8_t* out_footprint, uint64_t* rows,
+                         uint64_t* kmer_off) {
     const int nw = mer127 ? 4 : 2;
-    if (K < 1 || K > (mer127 ? 127 : 63)) { pg_set_error("pg_map_reads: K out of range"); return PG_EINVAL; }
+    if (K < 1 || K > (mer127 ? 127 : 63)) { pg_set_error(std::string(who) + ": K out of range"); return PG_EINVAL; }
     pg::MapContigs c;
     c.off.assign(ctg_off, ctg_off + n_ctg + 1);
     c.len.assign(ctg_len_bases, ctg_len_bases + n_ctg);
@@ -136,7 +138,7 @@ extern "C" int pg_map_reads(int device, int K, int mer127, const uint64_t* ctg_w
     c.words.assign(ctg_words, ctg_words + (n_ctg ? ctg_off[n_ctg] : 0));
     c.words.resize(c.words.size() + 8, 0);
     for (uint64_t i = 0; i < n_ctg; i++) {
-        if (c.len[i] < K + 2) { pg_set_error("pg_map_reads: the index takes contigs of K + 2 bases or more only"); return PG_EINVAL; }
+        if (c.len[i] < K + 2) { pg_set_error(std::string(who) + ": the index takes contigs of K + 2 bases or more only"); return PG_EINVAL; }
         c.n_kmers += (uint64_t)(c.len[i] - K + 1);
     }
     std::unique_ptr<pg::MapEngine> e = device < 0 ? pg::map_engine_host(K, nw) : pg::map_engine_device(device, K, nw);
@@ -146,11 +148,30 @@ extern "C" int pg_map_reads(int device, int K, int mer127, const uint64_t* ctg_w
     std::vector<uint64_t> words(read_words, read_words + (n_reads ? read_off[n_reads] : 0)), koff(n_reads + 1, 0);
     words.resize(words.size() + 8, 0);
     for (uint64_t r = 0; r < n_reads; r++) koff[r + 1] = koff[r] + (read_len[r] >= K + 1 ? (uint64_t)(read_len[r] - K + 1) : 0);
+    if (kmer_off) memcpy(kmer_off, koff.data(), (n_reads + 1) * sizeof(uint64_t));
     std::vector<pg::MapOut> out(n_reads);
-    rc = e->map(pg::MapBatch{words.data(), words.size(), read_off, read_len, koff.data(), n_reads}, align_len, out.data());
+    rc = e->map(pg::MapBatch{words.data(), words.size(), read_off, read_len, koff.data(), n_reads}, align_len, out.data(), rows);
     if (rc) return rc;
     for (uint64_t r = 0; r < n_reads; r++) {
         out_ctg[r] = out[r].ctg; out_pos[r] = out[r].pos; out_orien[r] = out[r].orien; out_footprint[r] = out[r].footprint;
     }
     return PG_OK;
+}
+
+extern "C" int pg_map_reads(int device, int K, int mer127, const uint64_t* ctg_words, const uint64_t* ctg_off, const int32_t* ctg_len_bases,
+                            const uint32_t* ctg_ids, uint64_t n_ctg, const int32_t* id_len, const int8_t* id_bal, uint32_t n_ids,
+                            const uint64_t* read_words, const uint64_t* read_off, const int32_t* read_len, uint64_t n_reads, int align_len,
+                            uint32_t* out_ctg, int32_t* out_pos, uint8_t* out_orien, uint8_t* out_footprint) {
+    return map_one_batch("pg_map_reads", device, K, mer127, ctg_words, ctg_off, ctg_len_bases, ctg_ids, n_ctg, id_len, id_bal, n_ids,
+                         read_words, read_off, read_len, n_reads, align_len, out_ctg, out_pos, out_orien, out_footprint, nullptr, nullptr);
+}
+
+extern "C" int pg_map_hits(int device, int K, int mer127, const uint64_t* ctg_words, const uint64_t* ctg_off, const int32_t* ctg_len_bases,
+                           const uint32_t* ctg_ids, uint64_t n_ctg, const int32_t* id_len, const int8_t* id_bal, uint32_t n_ids,
+                           const uint64_t* read_words, const uint64_t* read_off, const int32_t* read_len, uint64_t n_reads, int align_len,
+                           uint32_t* out_ctg, int32_t* out_pos, uint8_t* out_orien, uint8_t* out_footprint, uint64_t* rows,
+                           uint64_t* kmer_off) {
+    if (!rows || !kmer_off) { pg_set_error("pg_map_hits: rows and kmer_off are required"); return PG_EINVAL; }
+    return map_one_batch("pg_map_hits", device, K, mer127, ctg_words, ctg_off, ctg_len_bases, ctg_ids, n_ctg, id_len, id_bal, n_ids,
+                         read_words, read_off, read_len, n_reads, align_len, out_ctg, out_pos, out_orien, out_footprint, rows, kmer_off);
 }

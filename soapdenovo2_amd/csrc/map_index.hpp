@@ -66,8 +66,9 @@ public:
     virtual ~MapEngine() {}
     // build the index of `c`; ctg_len / bal = basicContigInfo's arrays, indexed by contig id (n_ids entries)
     virtual int build(const MapContigs& c, const int32_t* ctg_len, const int8_t* bal, uint32_t n_ids) = 0;
-    // map a batch: out[r] = parse1read of read r with the batch's ALIGNLEN
-    virtual int map(const MapBatch& b, int align_len, MapOut* out) = 0;
+    // map a batch: out[r] = parse1read of read r with the batch's ALIGNLEN.  rows_out (tests, pg_map_hits): when not null, receives
+    // the batch's hit words, read r's at rows_out + kmer_off[r] (kmer_off[n] entries)
+    virtual int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out = nullptr) = 0;
     // seconds spent building the index / in the read kernel (device: measured by events), for the stage's report
     double t_index = 0, t_kernel = 0, t_copy = 0;
 };

@@ -5,7 +5,8 @@
 //                     table of map_index.hpp.  A new key is claimed with a CAS on its state word, its words are written, and the state is
 //                     published with a release store; a lane that meets a claimed slot tries the same slot again on its next trip round the
 //                     loop (no lane waits inside a branch for another lane of its own wavefront).  An equal key moves the state to
-//                     "deleted", so the table is a function of the contigs alone.
+//                     "deleted", so the table is a function of the contigs alone.  The trips a lane spends on one claimed slot are capped
+//                     (MAP_SPIN_CAP): a lane that gives up raises a device flag, and build() fails instead of the card hanging.
 //   map_read_kernel   a lane per read: roll, canonicalise, probe; every k-mer's hit word goes to the read's row of the batch's hit buffer
 //                     (the reference's nodeBuffer), then map_decide (map_decide.hpp) picks the contig from the row.
 // Both wait for random 32- / 48-byte slot reads of a table that is many times the L2: the bound is HBM random-access latency and rate,
@@ -25,6 +26,9 @@ void pg_set_error(const std::string& s);
 namespace pg {
 
 constexpr int MAP_ITEM = 64;                      // k-mers of a contig a lane of the index build rolls through
+// Trips round map_insert's loop a lane may spend on one claimed slot before it gives up.  A claim is held for NW + 1 stores; the most any
+// lane needed in the homopolymer / tandem-repeat contention case on an MI355X is in DESIGN.md's map section, and this is > 1000 times it.
+constexpr uint32_t MAP_SPIN_CAP = 1u << 20;
 
 #define MAP_HIP(call)                                                                                   \
     do {                                                                                                \
@@ -40,9 +44,10 @@ __device__ __forceinline__ uint64_t map_state_acquire(const uint64_t* p) {
 }
 
 template <int NW>
-__device__ __forceinline__ void map_insert(uint64_t* tab, uint64_t mask, const Kmer<NW>& k, uint64_t value) {
+__device__ __forceinline__ void map_insert(uint64_t* tab, uint64_t mask, const Kmer<NW>& k, uint64_t value, uint32_t* gave_up) {
     constexpr int SW = map_slot_words<NW>();
     uint64_t e = map_home<NW>(k, mask);
+    uint32_t waits = 0;                            // trips spent on slot e while it was claimed
     for (;;) {
         uint64_t* sl = tab + e * SW;
         uint64_t* st = sl + NW + 1;
@@ -57,7 +62,10 @@ __device__ __forceinline__ void map_insert(uint64_t* tab, uint64_t mask, const K
             }
             continue;                              // somebody claimed it first: look again
         }
-        if (s == MAP_CLAIMED) continue;            // its key is still being written
+        if (s == MAP_CLAIMED) {                    // its key is still being written
+            if (++waits > MAP_SPIN_CAP) { atomicOr(gave_up, 1u); return; }
+            continue;
+        }
         bool eq = true;
 #pragma unroll
         for (int i = 0; i < NW; i++) eq = eq && sl[i] == k.w[i];
@@ -66,6 +74,7 @@ __device__ __forceinline__ void map_insert(uint64_t* tab, uint64_t mask, const K
             return;
         }
         e = (e + 1) & mask;
+        waits = 0;
     }
 }
 
@@ -73,7 +82,7 @@ template <int NW>
 __global__ __launch_bounds__(256) void map_index_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
                                                         const int32_t* __restrict__ len, const uint32_t* __restrict__ ids,
                                                         const uint32_t* __restrict__ item_ctg, const uint32_t* __restrict__ item_j0,
-                                                        uint64_t n_items, int K, uint64_t* tab, uint64_t mask) {
+                                                        uint64_t n_items, int K, uint64_t* tab, uint64_t mask, uint32_t* gave_up) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_items) return;
     const uint32_t c = item_ctg[t];
@@ -88,7 +97,7 @@ __global__ __launch_bounds__(256) void map_index_kernel(const uint64_t* __restri
     for (int j = j0; j < j1; j++) {
         if (j > j0) kmer_roll<NW>(word, bal, read_base(rd, j + K - 1), K, filter);
         const bool sm = kmer_less<NW>(word, bal);
-        map_insert<NW>(tab, mask, sm ? word : bal, map_hit(id, (uint32_t)j, sm ? 0 : 1, 0));   // twin = 0 when the contig's strand is canonical
+        map_insert<NW>(tab, mask, sm ? word : bal, map_hit(id, (uint32_t)j, sm ? 0 : 1, 0), gave_up);   // twin = 0 when the contig's strand is canonical
     }
 }
 
@@ -162,7 +171,7 @@ public:
     ~DeviceMapEngine() override {
         if (!ready_) return;
         (void)hipSetDevice(dev_);
-        tab_.release(); len_.release(); bal_.release(); rwords_.release(); roff_.release(); rlen_.release(); rkoff_.release();
+        tab_.release(); flag_.release(); len_.release(); bal_.release(); rwords_.release(); roff_.release(); rlen_.release(); rkoff_.release();
         rows_.release(); out_.release();
         if (st_) (void)hipStreamDestroy(st_);
         if (e0_) (void)hipEventDestroy(e0_);
@@ -193,7 +202,7 @@ public:
         ctgs_ = MapCtgs{len_.p, bal_.p, n_ids};
         slots_ = map_table_slots(c.n_kmers);
         const int SW = nw_ + 2;
-        if ((rc = tab_.reserve(slots_ * SW))) return rc;
+        if ((rc = tab_.reserve(slots_ * SW)) || (rc = flag_.reserve(1))) return rc;
         // the contigs go through the read buffers; the work items are (contig, first k-mer) stretches of MAP_ITEM k-mers
         std::vector<uint32_t> item_c, item_j;
         for (size_t i = 0; i < n_ctg; i++)
@@ -206,6 +215,7 @@ public:
             (rc = d_off.reserve(n_ctg + 1)) || (rc = d_len.reserve(n_ctg))) return rc;
         MAP_HIP(hipEventRecord(e0_, st_));
         MAP_HIP(hipMemsetAsync(tab_.p, 0, slots_ * SW * sizeof(uint64_t), st_));
+        MAP_HIP(hipMemsetAsync(flag_.p, 0, sizeof(uint32_t), st_));
         if (n_items) {
             MAP_HIP(hipMemcpyAsync(d_ic.p, item_c.data(), n_items * 4, hipMemcpyHostToDevice, st_));
             MAP_HIP(hipMemcpyAsync(d_ij.p, item_j.data(), n_items * 4, hipMemcpyHostToDevice, st_));
@@ -214,19 +224,26 @@ public:
             MAP_HIP(hipMemcpyAsync(d_off.p, c.off.data(), (n_ctg + 1) * 8, hipMemcpyHostToDevice, st_));
             MAP_HIP(hipMemcpyAsync(d_len.p, c.len.data(), n_ctg * 4, hipMemcpyHostToDevice, st_));
             const dim3 grid((unsigned)((n_items + 255) / 256)), block(256);
-            if (nw_ == 2) hipLaunchKernelGGL((map_index_kernel<2>), grid, block, 0, st_, d_w.p, d_off.p, d_len.p, d_id.p, d_ic.p, d_ij.p, n_items, K_, tab_.p, slots_ - 1);
-            else hipLaunchKernelGGL((map_index_kernel<4>), grid, block, 0, st_, d_w.p, d_off.p, d_len.p, d_id.p, d_ic.p, d_ij.p, n_items, K_, tab_.p, slots_ - 1);
+            if (nw_ == 2) hipLaunchKernelGGL((map_index_kernel<2>), grid, block, 0, st_, d_w.p, d_off.p, d_len.p, d_id.p, d_ic.p, d_ij.p, n_items, K_, tab_.p, slots_ - 1, flag_.p);
+            else hipLaunchKernelGGL((map_index_kernel<4>), grid, block, 0, st_, d_w.p, d_off.p, d_len.p, d_id.p, d_ic.p, d_ij.p, n_items, K_, tab_.p, slots_ - 1, flag_.p);
             MAP_HIP(hipGetLastError());
         }
         MAP_HIP(hipEventRecord(e1_, st_));
+        uint32_t gave_up = 0;
+        MAP_HIP(hipMemcpyAsync(&gave_up, flag_.p, sizeof gave_up, hipMemcpyDeviceToHost, st_));
         MAP_HIP(hipStreamSynchronize(st_));
         float ms = 0;
         MAP_HIP(hipEventElapsedTime(&ms, e0_, e1_));
         t_index += ms * 1e-3;
         d_ic.release(); d_ij.release(); d_id.release(); d_w.release(); d_off.release(); d_len.release();
+        if (gave_up) {
+            pg_set_error("map: the index build gave up on a claimed slot after " + std::to_string(MAP_SPIN_CAP) +
+                         " trips (the slot's key was never published); the index is not complete");
+            return PG_ESPIN;
+        }
         return PG_OK;
     }
-    int map(const MapBatch& b, int align_len, MapOut* out) override {
+    int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out) override {
         if (!b.n) return PG_OK;
         MAP_HIP(hipSetDevice(dev_));
         int rc;
@@ -245,6 +262,7 @@ public:
         MAP_HIP(hipGetLastError());
         MAP_HIP(hipEventRecord(e1_, st_));
         MAP_HIP(hipMemcpyAsync(out, out_.p, b.n * sizeof(MapOut), hipMemcpyDeviceToHost, st_));
+        if (rows_out && n_k) MAP_HIP(hipMemcpyAsync(rows_out, rows_.p, n_k * sizeof(uint64_t), hipMemcpyDeviceToHost, st_));
         MAP_HIP(hipStreamSynchronize(st_));
         float ms = 0;
         MAP_HIP(hipEventElapsedTime(&ms, e0_, e1_));
@@ -266,6 +284,7 @@ private:
     uint64_t slots_ = 0;
     MapCtgs ctgs_{nullptr, nullptr, 0};
     DevBuf<uint64_t> tab_, rwords_, roff_, rkoff_, rows_;
+    DevBuf<uint32_t> flag_;                         // raised by a lane of the index build that gave up on a claimed slot
     DevBuf<int32_t> len_, rlen_;
     DevBuf<int8_t> bal_;
     DevBuf<MapOut> out_;
