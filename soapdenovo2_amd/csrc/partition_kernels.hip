@@ -580,7 +580,11 @@ __global__ __launch_bounds__(THREADS) void skm_count_kernel(E2Dev e, int D, SetP
     constexpr bool ADAPT = NW == 4;
     bool dd_on = true;
     uint32_t dd_rec = 0, dd_rep = 0;
+#if defined(PG_MEASURE) && defined(PG_K2_DD_PCT)
+    constexpr uint32_t dd_pct = PG_K2_DD_PCT;                             // (the A/B of the cut-off: make MEASURE=1 XDEF=PG_K2_DD_PCT=85; 100 = never stop)
+#else
     constexpr uint32_t dd_pct = 70u;
+#endif
     // stage the window's records: 16 bytes per lane and step; the header word as it is, every payload word high dword first
     auto p_stage = [&](auto gs_, int gtid, int nb, int cl, uint32_t w0, uint32_t wn) {
         constexpr int GS = decltype(gs_)::value;
@@ -652,14 +656,33 @@ __global__ __launch_bounds__(THREADS) void skm_count_kernel(E2Dev e, int D, SetP
         uint32_t* const rlb = rl2[nb];
         bool is_rep = (uint32_t)gtid < wn;
         if (is_rep && (!ADAPT || dd_on)) {
-            const uint32_t* me = rlb + PAD + gtid * RD;
-            uint32_t w[RD - 1];
-            w[0] = me[0] & ((1u << SKM_ORD_SHIFT) - 1);                    // n, has_left, has_right
+            // A staged record is PIECES 16-byte pieces at a 16-byte-aligned place: [hdr lo, hdr hi, d0, d1] [d2 .. d5] [d6 .. d9] ...; its
+            // nb = n + K - 1 + flanks bases fill d0 .. d(ceil(nb / 16) - 1), i.e. the first (nb + 95) / 64 pieces.  n and the flank bits are
+            // in hdr lo, which is compared first: two records that agree there have the same pieces filled, and agreeing in those pieces
+            // too makes them the same record -- the pieces behind hold no base (zeros: skm_make_record).  Only the filled pieces are read,
+            // hashed and compared; the first NP_MIN hold bases in every record of this K and are read without asking.  (A piece is compared
+            // whole: bits behind the last base that differed would keep two copies apart, which costs time, not the result.)
+            constexpr uint32_t IDM = (1u << SKM_ORD_SHIFT) - 1;               // n, has_left, has_right
+            constexpr int NP_MIN = KS ? ((KS + 95) >> 6 < PIECES ? (KS + 95) >> 6 : PIECES) : 1;
+            // (volatile: one ds_read_b128 a piece -- left to itself the compiler drops the dwords nobody looks at and reads the rest as b32 / 2 x b64 pairs, which
+            //  cost the LDS four times the cycles of the 16-byte read)
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            typedef const volatile u32x4 __attribute__((address_space(3))) lds_piece;
+            lds_piece* me = (lds_piece*)(rlb + PAD + gtid * RD);
+            u32x4 w[PIECES];
+            w[0] = me[0];
 #pragma unroll
-            for (int q = 1; q < RD - 1; q++) w[q] = me[q + 1];
+            for (int j = 1; j < NP_MIN; j++) w[j] = me[j];
+            const uint32_t id = w[0].x & IDM;
+            const uint32_t np = ((id >> 2) + (uint32_t)K - 1u + ((id >> 1) & 1u) + (id & 1u) + 95u) >> 6;   // (more than PIECES: a header no cutter writes; all pieces then)
+#pragma unroll
+            for (int j = NP_MIN; j < PIECES; j++) if (np > (uint32_t)j) w[j] = me[j];
             uint32_t hsh = 0x9E3779B1u;                                       // rotate-xor fold, one multiplicative finish
+            auto fold = [&](uint32_t x) { hsh = alignbit32(hsh, hsh, 27u) ^ x; };
+            fold(id); fold(w[0].z); fold(w[0].w);
 #pragma unroll
-            for (int q = 0; q < RD - 1; q++) hsh = alignbit32(hsh, hsh, 27u) ^ w[q];
+            for (int j = 1; j < PIECES; j++)
+                if (j < NP_MIN || np > (uint32_t)j) { fold(w[j].x); fold(w[j].y); fold(w[j].z); fold(w[j].w); }
             hsh *= 0x85EBCA6Bu;
             hsh ^= hsh >> 15;
             uint32_t sl = hsh & (DT - 1);
@@ -676,13 +699,17 @@ __global__ __launch_bounds__(THREADS) void skm_count_kernel(E2Dev e, int D, SetP
                 }
                 if ((v & ~1023u) != tag) { sl = (sl + 1) & (DT - 1); continue; }
                 v &= 1023u;
-                const uint32_t* it = rlb + PAD + (v - 1) * RD;
-                bool same = (it[0] & ((1u << SKM_ORD_SHIFT) - 1)) == w[0];
+                lds_piece* it = (lds_piece*)(rlb + PAD + (v - 1) * RD);
+                u32x4 r[PIECES];                                              // all the reads first: one round trip, not one a piece
 #pragma unroll
-                for (int q = 1; q < RD - 1; q++) same = same && it[q + 1] == w[q];
-                if (same) {
+                for (int j = 0; j < PIECES; j++) if (j < NP_MIN || np > (uint32_t)j) r[j] = it[j];
+                uint32_t diff = ((r[0].x & IDM) ^ id) | (r[0].z ^ w[0].z) | (r[0].w ^ w[0].w);
+#pragma unroll
+                for (int j = 1; j < PIECES; j++)
+                    if (j < NP_MIN || np > (uint32_t)j) diff |= (r[j].x ^ w[j].x) | (r[j].y ^ w[j].y) | (r[j].z ^ w[j].z) | (r[j].w ^ w[j].w);
+                if (diff == 0) {
                     atomicAdd(&dcount[v - 1], 1u);
-                    atomicMin((unsigned long long*)it, *(const unsigned long long*)me);
+                    atomicMin((unsigned long long*)(rlb + PAD + (v - 1) * RD), ((unsigned long long)w[0].y << 32) | w[0].x);
                     is_rep = false;
                     break;
                 }

@@ -138,6 +138,11 @@ PG_HD void skm_split_read(const uint64_t* rd, int len, const SkmGeom& g, Emit&& 
 
 // ---- records ---------------------------------------------------------------------------------------------
 // Fill `rec[0..rw)` for the run [j0, j0 + n) of a read of `len` bases whose first k-mer has ordinal ord0.
+// The tail is zero: every payload bit behind the record's last base (n + K - 1 + flanks of them) is 0, in the last filled word and in
+// the words behind it.  This function and tile_make_record (skm_tile.hpp) are the only places a record is made -- the serial and the
+// tiled cutter, routed or not, and the host twin all call one of them; skm_ingest_kernel copies records as they arrive -- so equal runs
+// give equal words.  The counting kernel's search for copies needs no more than that: it looks at the pieces that hold bases, and a
+// record that came in with a dirty tail would at worst not be merged with its copies (tests/test_k2_dedupe_edges.py).
 template <int PW>
 PG_HD void skm_make_record(const uint64_t* rd, int len, int j0, int n, uint64_t ord0, const SkmGeom& g, uint64_t* rec) {
     const int has_left = j0 > 0, has_right = (j0 + n - 1 + g.K) < len;
