@@ -66,7 +66,8 @@ int call_pregraph_127mer(int argc, char **argv);
  * <g>.shortreadInGap.gz, <g>.PEreadOnContig.gz (prlHashCtg.c, prlRead2Ctg.c).  -p only decides the reference's leftover bits in the
  * 2-bit read images of readInGap / PEreadOnContig, which are reproduced.  The contig k-mer index and the read -> contig decision run
  * on the first HIP device of SOAPDENOVO2_AMD_DEVICES (or SOAPDENOVO2_AMD_DEVICE, default 0).  Long-read libraries (asm_flags=4,
- * prlLongRead2Ctg) are refused with a message and a nonzero return before anything is written.
+ * prlLongRead2Ctg) are refused with a message and a nonzero return before anything is written, unless SOAPDENOVO2_AMD_MAP_LONG=1
+ * is set: then the long-read pass runs first and writes <g>.longReadInGap and, with -f, <g>.RlongReadInGap.
  * call_align        = behaviour of the SOAPdenovo-63mer binary (map.c:call_align built without MER127)
  * call_align_127mer = behaviour of the SOAPdenovo-127mer binary (map.c:call_align built with MER127) */
 int call_align(int argc, char **argv);
@@ -551,6 +552,22 @@ int pg_map_hits(int device, int K, int mer127, const uint64_t *ctg_words, const 
                 const uint32_t *ctg_ids, uint64_t n_ctg, const int32_t *id_len, const int8_t *id_bal, uint32_t n_ids,
                 const uint64_t *read_words, const uint64_t *read_off, const int32_t *read_len, uint64_t n_reads, int align_len,
                 uint32_t *out_ctg, int32_t *out_pos, uint8_t *out_orien, uint8_t *out_footprint, uint64_t *rows, uint64_t *kmer_off);
+
+/* One batch of the long-read pass (prlLongRead2Ctg, prlRead2Ctg.c:1080): pg_map_hits' arguments and answers, computed on the device by
+ * the wave-per-read kernel (csrc/map_kernels.hip: map_read_wave_kernel) instead of the lane-per-read one.  rows and kmer_off may each
+ * be null.  device = -1: the host twin, as for pg_map_reads. */
+int pg_map_long_reads(int device, int K, int mer127, const uint64_t *ctg_words, const uint64_t *ctg_off, const int32_t *ctg_len_bases,
+                      const uint32_t *ctg_ids, uint64_t n_ctg, const int32_t *id_len, const int8_t *id_bal, uint32_t n_ids,
+                      const uint64_t *read_words, const uint64_t *read_off, const int32_t *read_len, uint64_t n_reads, int align_len,
+                      uint32_t *out_ctg, int32_t *out_pos, uint8_t *out_orien, uint8_t *out_footprint, uint64_t *rows,
+                      uint64_t *kmer_off);
+/* Distinct contig ids of one read that the wave-per-read kernel's table in LDS holds.  A read with more is answered exactly all the
+ * same, in passes over classes of ids; tests place reads on both sides of this number. */
+int pg_map_wave_ids(int mer127);
+/* What the wave-per-read kernel reported for this process's last pg_map_long_reads call on a device, for tests and measurements:
+ * out[0] = reads whose ids did not fit the table (answered in passes), out[1] = distinct ids summed over the reads with k-mers.
+ * Both are 0 after a host-twin call. */
+void pg_map_long_last_stats(uint64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -64,6 +64,10 @@ def lib() -> C.CDLL:
     L.pg_map_reads.argtypes = [C.c_int, C.c_int, C.c_int, u64p, u64p, u64p, u64p, C.c_uint64, u64p, u64p, C.c_uint32,
                                u64p, u64p, u64p, C.c_uint64, C.c_int, u64p, u64p, u64p, u64p]
     L.pg_map_hits.argtypes = list(L.pg_map_reads.argtypes) + [u64p, u64p]
+    L.pg_map_long_reads.argtypes = list(L.pg_map_hits.argtypes)
+    L.pg_map_wave_ids.argtypes = [C.c_int]
+    L.pg_map_long_last_stats.argtypes = [u64p]
+    L.pg_map_long_last_stats.restype = None
     L.pg_packed_words.restype = C.c_size_t
     L.pg_packed_words.argtypes = [C.c_uint32]
     L.pg_pack_read.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -173,7 +177,7 @@ EXPORTED_SYMBOLS = [
     "pg_exchange_gather_records", "pg_count_reads_sharded", "pg_host_skm_cut", "pg_host_skm_expand",
     "pg_host_emu_layout_static", "pg_graph_begin_device", "pg_host_emu_clip_tips", "pg_exchange_regroup_by_set", "pg_comm_regroup_stats", "pg_graph_begin_sharded", "pg_host_regroup_plan", "pg_host_bam_pair_state", "pg_device_scratch_offer", "pg_device_scratch_withdraw", "pg_host_emu_layout_growable", "pg_exchange_regroup_by_set_ws", "pg_host_edge_file_in_background", "pg_graph_add_packed_device", "pg_host_emu_home_slots", "pg_comm_pipeline_stats", "pg_comm_create_host", "pg_comm_flush",
     "pg_set_read_len_bound", "pg_graph_add_packed_device_ragged", "pg_expect", "pg_host_plan_memory", "pg_create_planned", "pg_graph_add_packed_device_segments",
-    "call_align", "call_align_127mer", "pg_map_reads", "pg_map_hits",
+    "call_align", "call_align_127mer", "pg_map_reads", "pg_map_hits", "pg_map_long_reads", "pg_map_wave_ids", "pg_map_long_last_stats",
 ]
 
 
@@ -274,6 +278,40 @@ def map_hits(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, me
     _check(lib().pg_map_hits(device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
                              p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp), p(rows), p(koff)), "pg_map_hits")
     return ctg, pos, ori, fp, rows[:n_k], koff
+
+
+def map_long_reads(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, mer127: bool = False, device: int = 0,
+                   want_hits: bool = False):
+    """One batch of the long-read pass (pg_map_long_reads): the wave-per-read kernel on `device`, the host twin with device = -1.
+    Arguments as map_reads; returns what map_reads returns, or what map_hits returns with want_hits=True."""
+    cw, co, cl = _pack_many(contigs)
+    rw, ro, rl = _pack_many(reads)
+    ids = np.ascontiguousarray(ctg_ids, dtype=np.uint32)
+    il = np.ascontiguousarray(id_len, dtype=np.int32)
+    ib = np.ascontiguousarray(id_bal, dtype=np.int8)
+    n = len(reads)
+    ctg = np.zeros(n, np.uint32); pos = np.zeros(n, np.int32); ori = np.zeros(n, np.uint8); fp = np.zeros(n, np.uint8)
+    n_k = int(sum(max(0, int(l) - K + 1) for l in rl if l >= K + 1))
+    rows = np.full(n_k + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if want_hits else None
+    koff = np.zeros(n + 1, np.uint64) if want_hits else None
+    p = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pg_map_long_reads(device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
+                                   p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp), p(rows), p(koff)), "pg_map_long_reads")
+    return (ctg, pos, ori, fp, rows[:n_k], koff) if want_hits else (ctg, pos, ori, fp)
+
+
+def map_long_last_stats():
+    """(reads answered in passes, distinct ids summed over the reads) of the last map_long_reads call on a device
+    (pg_map_long_last_stats); (0, 0) after a host-twin call."""
+    out = np.zeros(2, dtype=np.uint64)
+    lib().pg_map_long_last_stats(out.ctypes.data)
+    return int(out[0]), int(out[1])
+
+
+def map_wave_ids(mer127: bool = False) -> int:
+    """Distinct contig ids of a read that the wave-per-read kernel's LDS table holds (pg_map_wave_ids); reads with more are answered
+    in passes, with the same result."""
+    return int(lib().pg_map_wave_ids(1 if mer127 else 0))
 
 
 # ---------------------------------------------------------------------------------------------------------

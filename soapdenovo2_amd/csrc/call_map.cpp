@@ -3,7 +3,8 @@
 //   map -s lib.cfg -g prefix [-f] [-p n_cpu] [-k kmer_R2C] [-h contig_total_length]
 //
 // Reads <prefix>.contig, .ContigIndex and .preGraphBasic; writes <prefix>.readOnContig.gz, .readInGap.gz, .peGrads and, with -f,
-// .shortreadInGap.gz and .PEreadOnContig.gz -- for the same -p, the reference's files (the .gz ones after decompression).
+// .shortreadInGap.gz and .PEreadOnContig.gz -- for the same -p, the reference's files (the .gz ones after decompression).  With the
+// long-read pass: <prefix>.longReadInGap and, with -f, .RlongReadInGap, byte for byte.
 //
 // Layout of the stage:
 //   1. the contigs of K + 2 bases or more are read (readseq1by1 semantics) and packed; the device builds the k-mer index (map_kernels.hip)
@@ -14,8 +15,13 @@
 //   3. a batch is packed (pg_pack_read's layout) and mapped by the read kernel, a lane a read
 //   4. recordAlldgn (:627-725) runs on the host in read order; the text and binary records are deflated by host threads, one gzip
 //      member per few megabytes (the same rule as .edge.gz)
-// Not here: long-read libraries (asm_flags=4, prlLongRead2Ctg) are refused before anything is written; one GPU (the first of
-// SOAPDENOVO2_AMD_DEVICES).  SOAPDENOVO2_AMD_MAP_HOST=1 runs the host twin of the index and the read kernel instead (the CPU tests).
+//   5. with SOAPDENOVO2_AMD_MAP_LONG=1 the long-read pass (prlLongRead2Ctg, prlRead2Ctg.c:1080-1298) runs between 1. and 2.: the
+//      libraries with asm_flags=4 are read one read at a time (pairs = 0: f= and q= files too), mapped a lane a read, or a wavefront
+//      a read with SOAPDENOVO2_AMD_MAP_LONG_KERNEL=wave (lane is the default until the two are measured), and the
+//      footprinted ones written to <prefix>.longReadInGap and, with -f, <prefix>.RlongReadInGap (plain files)
+// Not here: without that switch a config with a long-read library (asm_flags=4) is refused before anything is written; one GPU (the
+// first of SOAPDENOVO2_AMD_DEVICES).  SOAPDENOVO2_AMD_MAP_HOST=1 runs the host twin of the index and the read kernels instead (the CPU
+// tests).
 #include <getopt.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -208,13 +214,15 @@ void reverse2k(char* s, int n) {                                    // readseq1b
 
 struct PeInfo { int insertS; long long PE_bound; int rank, pair_num_cut; };
 
-// read1seqInLib with pairs = 1, asm_ctg = 0 (readseq1by1.c:1037-1244), over the libs of parse_lib_config (sorted by avg_ins as
-// scan_libInfo leaves them, lib.c:505)
+// read1seqInLib (readseq1by1.c:1037-1244) over the libs of parse_lib_config (sorted by avg_ins as scan_libInfo leaves them, lib.c:505):
+// with pairs = 1, asm_ctg = 0 for the short reads, with pairs = 0, asm_ctg = 4 for the long-read pass (long_pass).  max_len_all =
+// maxReadLen4all; line_buf_len = the maxReadLen that decides whether gStr is there (prlRead2Ctg.c:826-829, :1133-1136)
 class LibReader {
 public:
-    LibReader(const LibConfig& cfg, int max_len_all) : cfg_(cfg), all_(max_len_all), st_(cfg.libs.size()) {
+    LibReader(const LibConfig& cfg, int max_len_all, int line_buf_len, bool long_pass = false)
+        : cfg_(cfg), all_(max_len_all), long_(long_pass), st_(cfg.libs.size()) {
         max_len_ = all_;
-        line_len_ = 5000 < all_ ? -1 : 5000;                        // gStr (prlRead2Ctg.c:826-829): lines of maxReadLen + 1 then
+        line_len_ = 5000 < line_buf_len ? -1 : 5000;                // with gStr: lines of maxReadLen + 1
     }
     long long n_solexa = 0, readNumBack = 0;
     std::vector<PeInfo> pes;
@@ -244,7 +252,7 @@ public:
             libNo = (int)i;
             if (i < nl && cfg_.libs[i].rd_len_cutoff > 0) max_len_ = std::min(cfg_.libs[i].rd_len_cutoff, all_);
             else max_len_ = all_;
-            if (i != prevLib && readNumBack < n_solexa) {          // insert size bookkeeping (:1092-1103)
+            if (!long_ && i != prevLib && readNumBack < n_solexa) { // insert size bookkeeping (:1092-1103), pairs only
                 const LibInfo& P = cfg_.libs[prevLib];
                 pes.push_back(PeInfo{P.avg_ins, n_solexa, P.rank, P.pair_num_cut});
                 readNumBack = n_solexa;
@@ -291,17 +299,22 @@ private:
     };
     int ll() const { return line_len_ > 0 ? line_len_ : max_len_ + 1; }
     size_t files_of(const LibInfo& L, int type) const {
-        switch (type) { case 1: return L.f1.size(); case 2: return L.q1.size(); case 3: return L.p.size(); case 4: return L.b.size(); }
+        switch (type) {
+        case 1: return L.f1.size(); case 2: return L.q1.size(); case 3: return L.p.size(); case 4: return L.b.size();
+        case 5: return L.f.size(); case 6: return L.q.size();
+        }
         return 0;
     }
-    // nextValidIndex (readseq1by1.c:595-674) with pair = 1, asm_ctg = 0: libs with asm_flags 2 or 3; f1/f2, q1/q2, p, b (no f=, q=)
+    // nextValidIndex (readseq1by1.c:595-674).  pair = 1, asm_ctg = 0: libs with asm_flags 2 or 3; f1/f2, q1/q2, p, b (no f=, q=).
+    // pair = 0, asm_ctg = 4: libs with asm_flags 4; f= and q= files after those
     size_t next_valid(size_t i) {
+        const int last = long_ ? 6 : 4;
         while (i < cfg_.libs.size()) {
             const LibInfo& L = cfg_.libs[i];
-            if (L.asm_flag != 2 && L.asm_flag != 3) { i++; continue; }
+            if (long_ ? L.asm_flag != 4 : (L.asm_flag != 2 && L.asm_flag != 3)) { i++; continue; }
             Lib& S = st_[i];
-            if (S.type <= 4 && (size_t)S.index < files_of(L, S.type)) return i;
-            if (S.type < 4) { S.type++; S.index = 0; }
+            if (S.type <= last && (size_t)S.index < files_of(L, S.type)) return i;
+            if (S.type < last) { S.type++; S.index = 0; }
             else i++;
         }
         return i;
@@ -317,8 +330,8 @@ private:
             S.fp1.reset(new LineIn(a));
             S.fp2.reset(new LineIn(b));
             S.paired = 1;
-        } else if (S.type == 3) {
-            const std::string a = trim(L.p[S.index]);
+        } else if (S.type == 3 || S.type == 5 || S.type == 6) {
+            const std::string a = trim(S.type == 3 ? L.p[S.index] : S.type == 5 ? L.f[S.index] : L.q[S.index]);
             say(a);
             S.fp1.reset(new LineIn(a));
             S.paired = 0;
@@ -349,6 +362,7 @@ private:
     }
     const LibConfig& cfg_;
     int all_, max_len_, line_len_;
+    bool long_;
     std::vector<Lib> st_;
     std::vector<char> str_;
     int readstate_ = 0, bam_state_ = -3;
@@ -614,6 +628,134 @@ void contig_info(const std::string& prefix, std::vector<int32_t>& len, std::vect
     fclose(fp);
 }
 
+// prlLongRead2Ctg (prlRead2Ctg.c:1080-1298) with recordLongRead and output1read (:456-492, :612-625): the libraries with asm_flags=4,
+// a read at a time, a batch through the engine, the footprinted reads into <prefix>.longReadInGap (and .RlongReadInGap with -f).
+// Returns longReadLen (0: no such library, nothing done, no file), -1 on an engine error.
+int long_pass(const LibConfig& cfg, const Options& o, int K, MapEngine& eng, bool wave, int max_rd_len) {
+    int long_len = 0;                                               // getMaxLongReadLen (lib.c:43-68)
+    bool has = false;
+    for (const LibInfo& L : cfg.libs)
+        if (L.asm_flag == 4) { has = true; long_len = std::max(long_len, L.rd_len_cutoff); }
+    if (!has) return 0;
+    if (long_len <= 0) long_len = max_rd_len;
+    const int max_len_all = std::max(max_rd_len, long_len);         // maxReadLen4all
+    fprintf(stderr, "In file: %s, long read len %d, max name len %d.\n", o.cfg.c_str(), long_len, 256);
+    long long maxReadNum = 100000000LL / (long_len - K + 1 > 0 ? long_len - K + 1 : 1);
+    maxReadNum = maxReadNum % 2 == 0 ? maxReadNum : maxReadNum - 1;
+    // (this repository's own guard: the reference divides by longReadLen - K + 1 as it is and goes on)
+    if (long_len < K || maxReadNum < 2) { fprintf(stderr, "Long read length %d is too small for K = %d.\n", long_len, K); return -1; }
+    FILE* fp1 = fopen((o.prefix + ".longReadInGap").c_str(), "wb");
+    FILE* fp2 = o.fill ? fopen((o.prefix + ".RlongReadInGap").c_str(), "w") : nullptr;
+    if (!fp1 || (o.fill && !fp2)) { fprintf(stderr, "Cannot open %s.longReadInGap. Now exit to system...\n", o.prefix.c_str()); exit(-1); }
+    LibReader rd(cfg, max_len_all, long_len, true);
+    Batch b;
+    b.row = (size_t)max_len_all + 8;
+    const size_t cap = (size_t)std::min<long long>(maxReadNum, 1 << 12);
+    b.seq.resize(cap * b.row);
+    b.len.resize(cap);
+    std::vector<char> rc1((size_t)max_len_all + 8, 0);              // rcSeq[1]: zeroed once, then what the chop and the writes leave
+    std::vector<uint64_t> words, off, koff;
+    std::vector<MapOut> res;
+    std::string out1, out2;
+    long long readCounter = 0, readsInGap = 0;
+    double t_read = 0, t_pack = 0, t_map = 0, t_rec = 0;
+    const double k0 = eng.t_kernel, c0 = eng.t_copy;
+    int align_len = 0, libNo = 0, prevLibNo = -1, type = 0;
+    auto flush = [&]() -> int {
+        const double a = now_s();
+        words.clear(); off.resize(b.n); koff.resize(b.n + 1);
+        koff[0] = 0;
+        for (size_t t = 0; t < b.n; t++) {
+            const int L = b.len[t];
+            off[t] = words.size();
+            const size_t w0 = words.size();
+            words.resize(w0 + ((size_t)L + 31) / 32, 0);
+            const char* s = b.seq.data() + t * b.row;
+            for (int j = 0; j < L; j++) words[w0 + (size_t)(j >> 5)] |= (uint64_t)(s[j] & 3) << (62 - 2 * (j & 31));
+            koff[t + 1] = koff[t] + (L >= K + 1 ? (uint64_t)(L - K + 1) : 0);
+        }
+        words.resize(words.size() + 8, 0);
+        res.resize(b.n);
+        const double c = now_s();
+        const int e = eng.map(MapBatch{words.data(), words.size(), off.data(), b.len.data(), koff.data(), b.n}, align_len, res.data(), nullptr, wave);
+        if (e) { fprintf(stderr, "map: %s\n", pg_last_error()); return e; }
+        const double d = now_s();
+        // chop thread 0's reverse complements (reads t % p == 0 of K + 1 bases or more), then recordLongRead in read order
+        for (size_t t = 0; t < b.n; t += (size_t)o.p) {
+            const int L = b.len[t];
+            if (L < K + 1) continue;
+            const char* s = b.seq.data() + t * b.row;
+            for (int i = 0; i < L; i++) rc1[(size_t)i] = (char)(s[L - 1 - i] ^ 2);
+        }
+        for (size_t t = 0; t < b.n; t++) {
+            readCounter++;
+            if (!res[t].footprint) continue;
+            readsInGap++;
+            const char* s = b.seq.data() + t * b.row;
+            const int L = b.len[t];
+            for (int i = 0; i < L; i++) {                           // writeChar2tightString (seq.c:81-107)
+                char& byte = rc1[(size_t)(i / 4)];
+                const int sh = 6 - 2 * (i % 4);
+                byte = (char)((byte & ~(3 << sh)) | ((s[i] & 3) << sh));
+            }
+            put_bin(out1, L); put_bin(out1, (int32_t)res[t].ctg); put_bin(out1, res[t].pos);
+            out1.append(rc1.data(), (size_t)(L / 4 + 1));
+            if (o.fill && L > 0) {                                  // insSizeArray[t] = 18 < 2000 always
+                char h[128];
+                out2.append(h, (size_t)snprintf(h, sizeof h, ">%d\t%d\t%d\t%c\t%d\t%d\n", L, (int)res[t].ctg, res[t].pos, (char)res[t].orien, 18, 0));
+                for (int i = 0; i < L; i++) out2.push_back("ACTG"[s[i] & 3]);
+                out2.push_back('\n');
+            }
+        }
+        fwrite(out1.data(), 1, out1.size(), fp1);
+        if (fp2) fwrite(out2.data(), 1, out2.size(), fp2);
+        out1.clear(); out2.clear();
+        t_pack += c - a; t_map += d - c; t_rec += now_s() - d;
+        b.n = 0;
+        return 0;
+    };
+    double r0 = now_s();
+    for (;;) {
+        if (b.n == b.len.size()) {
+            const size_t nc = std::min<size_t>((size_t)maxReadNum, b.len.size() * 2);
+            b.seq.resize(nc * b.row); b.len.resize(nc);
+        }
+        int L = 0;
+        if (!rd.next(b.seq.data() + b.n * b.row, L, libNo, type)) break;
+        if (type == -1) {                                           // a bad BAM pair goes back (:1184-1196)
+            if (b.n) b.n--;
+            rd.n_solexa -= 2;
+            continue;
+        }
+        b.len[b.n] = L;
+        if (libNo != prevLibNo) {                                   // :1198-1204
+            prevLibNo = libNo;
+            align_len = std::max(cfg.libs[(size_t)libNo].map_len, 35);
+            fprintf(stderr, "Map_len %d.\n", align_len);
+        }
+        b.n++;
+        if ((long long)b.n == maxReadNum) {
+            t_read += now_s() - r0;
+            if (flush()) { fclose(fp1); if (fp2) fclose(fp2); return -1; }
+            r0 = now_s();
+        }
+    }
+    t_read += now_s() - r0;
+    if (b.n) {
+        if (flush()) { fclose(fp1); if (fp2) fclose(fp2); return -1; }
+        fprintf(stderr, "Output %lld out of %lld (%.1f)%% reads in gaps.\n", readsInGap, readCounter, (float)readsInGap / readCounter * 100);
+    }
+    fclose(fp1);
+    if (fp2) fclose(fp2);
+    fprintf(stderr, "%d reads deleted.\n", 0);
+    if (env_user("PG_HOST_VERBOSE"))
+        fprintf(stderr, "[map long] %s kernel: %lld reads, parse %.3fs, pack %.3fs, map %.3fs (kernel %.6fs, copies %.3fs), record %.3fs; "
+                        "reads done in passes %llu, distinct ids %llu\n",
+                wave ? "wave" : "lane", readCounter, t_read, t_pack, t_map, eng.t_kernel - k0, eng.t_copy - c0, t_rec,
+                (unsigned long long)eng.n_passes, (unsigned long long)eng.n_ids);
+    return long_len;
+}
+
 int run_map(int argc, char** argv, bool mer127) {
     const double t_start = now_s();
     fprintf(stderr, "\n********************\nMap\n********************\n\n");
@@ -655,12 +797,19 @@ int run_map(int argc, char** argv, bool mer127) {
     fprintf(stderr, "Kmer size: %d.\n", K);
 
     const LibConfig cfg = parse_lib_config(o.cfg.c_str());
-    for (const LibInfo& L : cfg.libs)
-        if (L.asm_flag == 4) {
-            fprintf(stderr, "Long-read libraries (asm_flags=4) are not supported by this map stage; run the reference binary for this "
-                            "config.  Nothing was written.\n");
-            return 2;
-        }
+    const bool long_on = env_on(env_user("SOAPDENOVO2_AMD_MAP_LONG"));
+    bool long_wave = false;
+    if (const char* e = long_on ? env_user("SOAPDENOVO2_AMD_MAP_LONG_KERNEL") : nullptr) {
+        long_wave = !strcmp(e, "wave");
+        if (!long_wave && strcmp(e, "lane")) { fprintf(stderr, "SOAPDENOVO2_AMD_MAP_LONG_KERNEL is lane or wave, not %s.\n", e); return 1; }
+    }
+    if (!long_on)
+        for (const LibInfo& L : cfg.libs)
+            if (L.asm_flag == 4) {
+                fprintf(stderr, "Long-read libraries (asm_flags=4) are not supported by this map stage; run the reference binary for this "
+                                "config.  Nothing was written.  SOAPDENOVO2_AMD_MAP_LONG=1 turns the long-read pass on.\n");
+                return 2;
+            }
     fprintf(stderr, "Contig length cutoff: %d.\n", K + 2);
 
     // 1. the index
@@ -682,7 +831,7 @@ int run_map(int argc, char** argv, bool mer127) {
         if (!eng) { fprintf(stderr, "map: %s\n", pg_last_error()); return 1; }
     }
     const double t1 = now_s();
-    const int max_all = cfg.max_rd_len ? cfg.max_rd_len : 100;                  // prlRead2Ctg.c:796-806: maxReadLen4all
+    const int max_all = cfg.max_rd_len ? cfg.max_rd_len : 100;                  // prlRead2Ctg.c:796-799: maxReadLen
     fprintf(stderr, "In file: %s, max seq len %d, max name len %d\n", o.cfg.c_str(), max_all, 256);
     contig_info(o.prefix, clen, cbal);
     int rc = eng->build(contigs, clen.data(), cbal.data(), (uint32_t)clen.size());
@@ -690,6 +839,19 @@ int run_map(int argc, char** argv, bool mer127) {
     { MapContigs none; std::swap(contigs, none); }
     const double t2 = now_s();
     fprintf(stderr, "Time spent on graph construction: %ds.\n\n", (int)(t2 - t0));
+
+    // 5. the long reads (map.c:129-133).  What they leave for the short pass is maxReadLen4all (prlRead2Ctg.c:803-806), which .peGrads'
+    // header prints.  The short reads themselves stay cut at max_rd_len: the reference would cut them at maxReadLen4all, into buffers of
+    // max_rd_len bytes, so a longer short read is past what it defines (and rows of maxReadLen4all bytes for every short read of a
+    // batch would be gigabytes for nothing)
+    int max_len_all = max_all;
+    if (long_on) {
+        const int long_len = long_pass(cfg, o, K, *eng, long_wave, max_all);
+        if (long_len < 0) return 1;
+        max_len_all = std::max(max_all, long_len);
+        fprintf(stderr, "Time spent on aligning long reads: %ds.\n\n", (int)(now_s() - t2));
+    }
+    const double t2b = now_s();
 
     // 2. - 4. the reads
     long long maxReadNum = 100000000LL / (max_all - K + 1);
@@ -704,7 +866,7 @@ int run_map(int argc, char** argv, bool mer127) {
     }
     Recorder rec{o, K, on_ctg, in_gap, short_gap.get(), pe_on.get(), std::vector<char>((size_t)max_all + 8, 0)};
     on_ctg.buf += "read\tcontig\tpos\n";
-    LibReader rd(cfg, max_all);
+    LibReader rd(cfg, max_all, max_all);
     Batch b;
     b.row = (size_t)max_all + 8;
     const size_t cap = (size_t)std::min<long long>(maxReadNum, 1 << 22);
@@ -784,7 +946,7 @@ int run_map(int argc, char** argv, bool mer127) {
     {
         FILE* fo2 = fopen((o.prefix + ".peGrads").c_str(), "w");
         if (!fo2) { fprintf(stderr, "Cannot open %s.peGrads. Now exit to system...\n", o.prefix.c_str()); exit(-1); }
-        fprintf(fo2, "grads&num: %d\t%lld\t%d\n", (int)rd.pes.size(), rd.n_solexa, max_all);
+        fprintf(fo2, "grads&num: %d\t%lld\t%d\n", (int)rd.pes.size(), rd.n_solexa, max_len_all);
         if (!rd.pes.empty()) fprintf(stderr, "%d pe insert size, the largest boundary is %lld.\n\n", (int)rd.pes.size(), rd.pes.back().PE_bound);
         else fprintf(stderr, "No paired reads found.\n");
         for (const PeInfo& p : rd.pes) fprintf(fo2, "%d\t%lld\t%d\t%d\n", p.insertS, p.PE_bound, p.rank, p.pair_num_cut);
@@ -793,7 +955,7 @@ int run_map(int argc, char** argv, bool mer127) {
     in_gap.close();
     if (o.fill) { short_gap->close(); pe_on->close(); }
     const double t4 = now_s();
-    fprintf(stderr, "Time spent on aligning reads: %ds.\n\n", (int)(t3 - t2));
+    fprintf(stderr, "Time spent on aligning reads: %ds.\n\n", (int)(t3 - t2b));
     if (env_user("PG_HOST_VERBOSE"))
         fprintf(stderr, "[map] contigs %.3fs, index %.3fs (device %.3fs), reads: parse %.3fs, pack %.3fs, map %.3fs (kernel %.3fs, copies %.3fs), "
                         "record %.3fs, files %.3fs (deflate waits %.3fs); whole stage %.3fs\n",

@@ -47,6 +47,27 @@ PG_HD int map_multi(int len, int align_len, int K) {
     return alldgn - K + 1 < 2 ? 2 : alldgn - K + 1;
 }
 
+// The tail of parse1read (:328-360) for a read that maps: h = the hit word of the chosen id's first hit, best = that k-mer's index in the
+// read, counter2 = the ids that count towards the footprint.  Shared by map_decide, the wave-per-read kernel and the host twin.
+PG_HD MapOut map_place(uint64_t h, int best, int K, int counter2, const MapCtgs& ctgs) {
+    MapOut o{0, 0, 0, 0};
+    o.footprint = counter2 > 1 ? 1 : 0;
+    const uint32_t contig = (uint32_t)h, i = (uint32_t)best + 1;
+    const uint32_t hi = (uint32_t)(h >> 32), pos = hi >> 2;
+    const int twin = (int)((hi >> 1) & 1), smaller = (int)(hi & 1);
+    const uint32_t ctg_len = contig < ctgs.n ? (uint32_t)ctgs.len[contig] : 0u;
+    if (twin == smaller) {                                         // unsigned arithmetic as the reference's (:351)
+        o.orien = '-';
+        o.ctg = contig + (uint32_t)(contig < ctgs.n ? (int)ctgs.bal[contig] : 1) - 1u;      // getTwinCtg, attachPEinfo.c:666
+        o.pos = (int32_t)(ctg_len - pos - (uint32_t)K - i + 1u);
+    } else {
+        o.orien = '+';
+        o.ctg = contig;
+        o.pos = (int32_t)(pos - i + 1u);
+    }
+    return o;
+}
+
 // row(j) = hit word of k-mer j, nk = number of k-mers (0 for reads shorter than K + 1)
 template <typename Row>
 PG_HD MapOut map_decide(const Row& row, int nk, int K, int multi, const MapCtgs& ctgs) {
@@ -96,22 +117,7 @@ PG_HD MapOut map_decide(const Row& row, int nk, int K, int multi, const MapCtgs&
         }
     }
     if (!counter) return o;
-    o.footprint = counter2 > 1 ? 1 : 0;
-    const uint64_t h = row(best);
-    const uint32_t contig = (uint32_t)h, i = (uint32_t)best + 1;
-    const uint32_t hi = (uint32_t)(h >> 32), pos = hi >> 2;
-    const int twin = (int)((hi >> 1) & 1), smaller = (int)(hi & 1);
-    const uint32_t ctg_len = contig < ctgs.n ? (uint32_t)ctgs.len[contig] : 0u;
-    if (twin == smaller) {                                         // unsigned arithmetic as the reference's (:351)
-        o.orien = '-';
-        o.ctg = contig + (uint32_t)(contig < ctgs.n ? (int)ctgs.bal[contig] : 1) - 1u;      // getTwinCtg, attachPEinfo.c:666
-        o.pos = (int32_t)(ctg_len - pos - (uint32_t)K - i + 1u);
-    } else {
-        o.orien = '+';
-        o.ctg = contig;
-        o.pos = (int32_t)(pos - i + 1u);
-    }
-    return o;
+    return map_place(row(best), best, K, counter2, ctgs);
 }
 
 }  // namespace pg

@@ -76,7 +76,7 @@ public:
         idx_.build(c, K_);
         return PG_OK;
     }
-    int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out) override {
+    int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out, bool) override {
         const MapCtgs ctgs{len_.data(), bal_.data(), (uint32_t)len_.size()};
         const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)host_threads(0), (b.n + 1023) / 1024));
         auto body = [&](int t) {
@@ -123,12 +123,15 @@ std::unique_ptr<MapEngine> map_engine_host(int K, int nw) {
 
 }  // namespace pg
 
+// what the wave kernel reported for the last pg_map_long_reads call (pg_map_long_last_stats)
+static uint64_t g_long_stats[2] = {0, 0};
+
 // pg_map_reads / pg_map_hits (include/soapdenovo2_amd.h): one index, one batch
 static int map_one_batch(const char* who, int device, int K, int mer127, const uint64_t* ctg_words, const uint64_t* ctg_off,
                          const int32_t* ctg_len_bases, const uint32_t* ctg_ids, uint64_t n_ctg, const int32_t* id_len, const int8_t* id_bal,
                          uint32_t n_ids, const uint64_t* read_words, const uint64_t* read_off, const int32_t* read_len, uint64_t n_reads,
                          int align_len, uint32_t* out_ctg, int32_t* out_pos, uint8_t* out_orien, uint8_t* out_footprint, uint64_t* rows,
-                         uint64_t* kmer_off) {
+                         uint64_t* kmer_off, bool wave = false) {
     const int nw = mer127 ? 4 : 2;
     if (K < 1 || K > (mer127 ? 127 : 63)) { pg_set_error(std::string(who) + ": K out of range"); return PG_EINVAL; }
     pg::MapContigs c;
@@ -150,8 +153,9 @@ static int map_one_batch(const char* who, int device, int K, int mer127, const u
     for (uint64_t r = 0; r < n_reads; r++) koff[r + 1] = koff[r] + (read_len[r] >= K + 1 ? (uint64_t)(read_len[r] - K + 1) : 0);
     if (kmer_off) memcpy(kmer_off, koff.data(), (n_reads + 1) * sizeof(uint64_t));
     std::vector<pg::MapOut> out(n_reads);
-    rc = e->map(pg::MapBatch{words.data(), words.size(), read_off, read_len, koff.data(), n_reads}, align_len, out.data(), rows);
+    rc = e->map(pg::MapBatch{words.data(), words.size(), read_off, read_len, koff.data(), n_reads}, align_len, out.data(), rows, wave);
     if (rc) return rc;
+    if (wave) { g_long_stats[0] = e->n_passes; g_long_stats[1] = e->n_ids; }
     for (uint64_t r = 0; r < n_reads; r++) {
         out_ctg[r] = out[r].ctg; out_pos[r] = out[r].pos; out_orien[r] = out[r].orien; out_footprint[r] = out[r].footprint;
     }
@@ -175,3 +179,17 @@ extern "C" int pg_map_hits(int device, int K, int mer127, const uint64_t* ctg_wo
     return map_one_batch("pg_map_hits", device, K, mer127, ctg_words, ctg_off, ctg_len_bases, ctg_ids, n_ctg, id_len, id_bal, n_ids,
                          read_words, read_off, read_len, n_reads, align_len, out_ctg, out_pos, out_orien, out_footprint, rows, kmer_off);
 }
+
+// prlLongRead2Ctg's batch (prlRead2Ctg.c:1080): the wave-per-read kernel on the device, the host twin's one form with device = -1
+extern "C" int pg_map_long_reads(int device, int K, int mer127, const uint64_t* ctg_words, const uint64_t* ctg_off, const int32_t* ctg_len_bases,
+                                 const uint32_t* ctg_ids, uint64_t n_ctg, const int32_t* id_len, const int8_t* id_bal, uint32_t n_ids,
+                                 const uint64_t* read_words, const uint64_t* read_off, const int32_t* read_len, uint64_t n_reads,
+                                 int align_len, uint32_t* out_ctg, int32_t* out_pos, uint8_t* out_orien, uint8_t* out_footprint,
+                                 uint64_t* rows, uint64_t* kmer_off) {
+    return map_one_batch("pg_map_long_reads", device, K, mer127, ctg_words, ctg_off, ctg_len_bases, ctg_ids, n_ctg, id_len, id_bal, n_ids,
+                         read_words, read_off, read_len, n_reads, align_len, out_ctg, out_pos, out_orien, out_footprint, rows, kmer_off, true);
+}
+
+extern "C" void pg_map_long_last_stats(uint64_t out[2]) { out[0] = g_long_stats[0]; out[1] = g_long_stats[1]; }
+
+extern "C" int pg_map_wave_ids(int) { return pg::map_wave_ids(); }

@@ -68,13 +68,19 @@ public:
     virtual int build(const MapContigs& c, const int32_t* ctg_len, const int8_t* bal, uint32_t n_ids) = 0;
     // map a batch: out[r] = parse1read of read r with the batch's ALIGNLEN.  rows_out (tests, pg_map_hits): when not null, receives
     // the batch's hit words, read r's at rows_out + kmer_off[r] (kmer_off[n] entries)
-    virtual int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out = nullptr) = 0;
-    // seconds spent building the index / in the read kernel (device: measured by events), for the stage's report
+    // wave: the device runs the wave-per-read kernel of the long-read pass (map_read_wave_kernel) instead of the lane-per-read one; the
+    // answers are the same, and the host twin has one form for both
+    virtual int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out = nullptr, bool wave = false) = 0;
+    // seconds spent building the index / in the read kernels (device: measured by events), for the stage's report
     double t_index = 0, t_kernel = 0, t_copy = 0;
+    // the wave kernel's figures: reads whose ids did not fit its LDS table (done in passes), distinct ids summed over the reads with k-mers
+    uint64_t n_passes = 0, n_ids = 0;
 };
 
 // K and the flavour (nw = 2: the 63-mer build, 4: the 127-mer build)
 std::unique_ptr<MapEngine> map_engine_device(int device, int K, int nw);
 std::unique_ptr<MapEngine> map_engine_host(int K, int nw);
+// distinct contig ids of a read that the wave kernel's LDS table holds (more: the read is done in passes)
+int map_wave_ids();
 
 }  // namespace pg

@@ -9,7 +9,10 @@
 //                     (MAP_SPIN_CAP): a lane that gives up raises a device flag, and build() fails instead of the card hanging.
 //   map_read_kernel   a lane per read: roll, canonicalise, probe; every k-mer's hit word goes to the read's row of the batch's hit buffer
 //                     (the reference's nodeBuffer), then map_decide (map_decide.hpp) picks the contig from the row.
-// Both wait for random 32- / 48-byte slot reads of a table that is many times the L2: the bound is HBM random-access latency and rate,
+//   map_read_wave_kernel  a wavefront per read, for long reads (prlLongRead2Ctg, prlRead2Ctg.c:1080): the lanes share the read's k-mers and the
+//                     decision is linear in them, through a per-wave table in LDS keyed by contig id (count, first hit).  Same rows, same
+//                     out[] as map_read_kernel.
+// All three wait for random 32- / 48-byte slot reads of a table that is many times the L2: the bound is HBM random-access latency and rate,
 // not arithmetic.  Memory comes from the device arena (arena.hpp).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -146,6 +149,214 @@ __global__ __launch_bounds__(256) void map_read_kernel(const uint64_t* __restric
     out[r] = map_decide(MapRow{row}, nk, K, map_multi(len, align_len, K), ctgs);
 }
 
+
+// ---- a wavefront per read ----
+// The decision needs, per distinct contig id of the row, the number of hits and the first hit (map_decide.hpp).  A wave gathers them in an
+// open-addressing table in LDS keyed by id: an atomic add for the count, an atomic min over (position << 32 | the hit word's high half)
+// for the first hit -- neither depends on the order the lanes arrive in.  MAP_WAVE_IDS distinct ids fit, in twice as many slots: a lane
+// that meets an empty slot draws a number from the id counter before it claims the slot, and with a number of MAP_WAVE_IDS or more it
+// raises t.over instead.  So never more than MAP_WAVE_IDS slots are taken, every probe ends at an empty or an equal slot, and a read with
+// more ids than that always raises t.over.  (Two lanes that bring the same new id at once both draw; the loser gives its number back.  At
+// exactly MAP_WAVE_IDS ids that can raise t.over too, which costs time and changes no answer.)
+// A read with t.over raised is done again from its row in passes: pass (P, p) takes the ids with id % P == p, P = 2, 4, ...
+// MAP_WAVE_CLASSES, until every class fits; the sums and the winner are the same whatever P is.  Contig ids are the contigs' numbers, so
+// a read of n ids needs P ~ n / MAP_WAVE_IDS.  Ids that agree in their low bits can defeat every P: then the wave runs the reference's
+// own scan over the row, the lanes sharing each inner loop.  That bounds a read's work: 2 * MAP_WAVE_CLASSES passes of nk / 64 row loads
+// a lane, then nk^2 / 32.  There is no workgroup barrier: the four waves of a workgroup share nothing.
+constexpr int MAP_WAVE_IDS = 128;                 // 256 slots x 16 B + 8 B = 4 104 B a wave, 16 416 B a workgroup: 8 workgroups (32 waves,
+constexpr int MAP_WAVE_SLOTS = 2 * MAP_WAVE_IDS;  // the most a CU holds) take 128.25 of the CU's 160 KiB; twice the ids would leave 16 waves
+constexpr int MAP_WAVES = 4;                      // reads of a 256-thread workgroup
+constexpr int MAP_WAVE_CLASSES = 64;              // the most id classes the passes try before the scan
+
+struct MapWaveTable {
+    uint32_t id[MAP_WAVE_SLOTS];
+    uint32_t cnt[MAP_WAVE_SLOTS];
+    unsigned long long first[MAP_WAVE_SLOTS];     // k-mer index << 32 | hit word >> 32 of the id's first hit
+    uint32_t n_ids, over;
+};
+
+// the phases of one wave's LDS work are ordered by the wave's own instruction order; this keeps the compiler from moving LDS accesses
+// across a phase's end
+__device__ __forceinline__ void map_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ void map_wave_clear(MapWaveTable& t, int lane) {
+    for (int q = lane; q < MAP_WAVE_SLOTS; q += 64) { t.id[q] = 0; t.cnt[q] = 0; t.first[q] = ~0ull; }
+    if (lane == 0) { t.n_ids = 0; t.over = 0; }
+    map_wave_sync();
+}
+
+// one hit of k-mer j.  A new id that draws a number past the table's capacity raises t.over instead (the read is then done in passes)
+__device__ __forceinline__ void map_wave_put(MapWaveTable& t, uint64_t hit, int j) {
+    const uint32_t c = (uint32_t)hit;
+    uint32_t e = (c * 2654435761u) >> 16 & (MAP_WAVE_SLOTS - 1);
+    bool drawn = false, placed = false;
+    for (;;) {
+        uint32_t cur = __hip_atomic_load(&t.id[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (cur == 0) {
+            if (!drawn) {
+                if (atomicAdd(&t.n_ids, 1u) >= (uint32_t)MAP_WAVE_IDS) {
+                    __hip_atomic_store(&t.over, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    return;
+                }
+                drawn = true;
+            }
+            cur = atomicCAS(&t.id[e], 0u, c);
+            if (cur == 0) { placed = true; cur = c; }
+        }
+        if (cur == c) break;
+        e = (e + 1) & (MAP_WAVE_SLOTS - 1);        // another id's slot
+    }
+    if (drawn && !placed) atomicSub(&t.n_ids, 1u); // another lane brought the same id first
+    atomicAdd(&t.cnt[e], 1u);
+    atomicMin(&t.first[e], (unsigned long long)(uint32_t)j << 32 | (hit >> 32));
+}
+
+struct MapWaveSum {
+    int counter, counter2;
+    unsigned long long key;                        // count << 32 | ~first index: the largest is the winner
+    uint32_t id, hi;                               // the winner's hit word
+};
+
+// this lane's share of the table into s
+__device__ __forceinline__ void map_wave_collect(const MapWaveTable& t, int lane, int K, int multi, MapWaveSum& s) {
+    for (int q = lane; q < MAP_WAVE_SLOTS; q += 64) {
+        if (!t.id[q]) continue;
+        const uint32_t flag = t.cnt[q];
+        const unsigned long long f = t.first[q];
+        if ((K < 32 && flag >= 2) || K > 32) s.counter2++;
+        if ((int)flag < multi) continue;
+        s.counter++;
+        const unsigned long long key = (unsigned long long)flag << 32 | (0xFFFFFFFFu - (uint32_t)(f >> 32));
+        if (key > s.key) { s.key = key; s.id = t.id[q]; s.hi = (uint32_t)f; }
+    }
+}
+
+template <int NW>
+__global__ __launch_bounds__(256) void map_read_wave_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
+                                                            const int32_t* __restrict__ lens, const uint64_t* __restrict__ koff, uint64_t n,
+                                                            int K, int align_len, const uint64_t* __restrict__ tab, uint64_t mask,
+                                                            MapCtgs ctgs, uint64_t* rows, MapOut* __restrict__ out,
+                                                            unsigned long long* __restrict__ stats) {
+    constexpr int SW = map_slot_words<NW>();
+    __shared__ MapWaveTable tables[MAP_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t r = (uint64_t)blockIdx.x * MAP_WAVES + wave;
+    if (r >= n) return;                            // (no workgroup barrier follows)
+    const int len = lens[r];
+    const int nk = len >= K + 1 ? len - K + 1 : 0;
+    if (!nk) {
+        if (lane == 0) out[r] = MapOut{0, 0, 0, 0};
+        return;
+    }
+    MapWaveTable& t = tables[wave];
+    uint64_t* row = rows + koff[r];
+    const int multi = map_multi(len, align_len, K);
+    map_wave_clear(t, lane);
+    {   // the lookups: a lane rolls through its stretch of the read; every hit goes to the row and to the table
+        const int per = (nk + 63) / 64;
+        const int j0 = lane * per, j1 = nk < j0 + per ? nk : j0 + per;
+        if (j0 < j1) {
+            const uint64_t* rd = words + off[r];
+            const Kmer<NW> filter = kmer_filter<NW>(K);
+            Kmer<NW> word = read_kmer<NW>(rd, j0, K, filter);
+            Kmer<NW> bal = kmer_rc<NW>(word, K);
+            for (int j = j0; j < j1; j++) {
+                if (j > j0) kmer_roll<NW>(word, bal, read_base(rd, j + K - 1), K, filter);
+                const bool sm = kmer_less<NW>(word, bal);
+                const Kmer<NW> ck = sm ? word : bal;
+                uint64_t e = map_home<NW>(ck, mask), hit = 0;
+                for (;;) {
+                    const uint64_t* sl = tab + e * SW;
+                    const uint64_t s = sl[NW + 1];
+                    if (s == MAP_EMPTY) break;
+                    bool eq = true;
+#pragma unroll
+                    for (int i = 0; i < NW; i++) eq = eq && sl[i] == ck.w[i];
+                    if (eq) {
+                        if (s != MAP_DELETED) hit = sl[NW] | ((uint64_t)(sm ? 1 : 0) << 32);
+                        break;
+                    }
+                    e = (e + 1) & mask;
+                }
+                row[j] = hit;
+                if ((uint32_t)hit) map_wave_put(t, hit, j);
+            }
+        }
+    }
+    map_wave_sync();
+    MapWaveSum s{0, 0, 0ull, 0u, 0u};
+    uint32_t n_ids = t.n_ids;
+    const bool over = t.over != 0;
+    if (!over) map_wave_collect(t, lane, K, multi, s);
+    else {
+        __threadfence_block();                     // the row is read back by other lanes than those that wrote it
+        uint32_t P = 1;
+        bool again = true;
+        while (again && P < (uint32_t)MAP_WAVE_CLASSES) {
+            P <<= 1;
+            again = false;
+            s = MapWaveSum{0, 0, 0ull, 0u, 0u};
+            n_ids = 0;
+            for (uint32_t p = 0; p < P; p++) {
+                map_wave_sync();
+                map_wave_clear(t, lane);
+                for (int j = lane; j < nk; j += 64) {
+                    const uint64_t hit = row[j];
+                    if ((uint32_t)hit && ((uint32_t)hit & (P - 1)) == p) map_wave_put(t, hit, j);
+                }
+                map_wave_sync();
+                if (t.over) { again = true; break; }
+                n_ids += t.n_ids;
+                map_wave_collect(t, lane, K, multi, s);
+            }
+        }
+        if (again) {                               // no P gave classes that fit: the reference's scan (:282-326), a wave wide
+            s = MapWaveSum{0, 0, 0ull, 0u, 0u};
+            n_ids = 0;
+            for (int j = 0; j < nk; j++) {
+                const uint64_t h = row[j];
+                const uint32_t c = (uint32_t)h;
+                if (!c) continue;
+                bool seen = false;
+                for (int i0 = 0; i0 < j && !seen; i0 += 64) seen = __any(i0 + lane < j && (uint32_t)row[i0 + lane] == c) != 0;
+                if (seen) continue;
+                int flag = 0;
+                for (int q = j + 1 + lane; q < nk; q += 64) flag += (uint32_t)row[q] == c ? 1 : 0;
+                for (int d = 32; d > 0; d >>= 1) flag += __shfl_xor(flag, d);
+                flag++;
+                n_ids++;
+                if (lane) continue;                // lane 0 keeps the sums; the other lanes add nothing below
+                if ((K < 32 && flag >= 2) || K > 32) s.counter2++;
+                if (flag < multi) continue;
+                s.counter++;
+                const unsigned long long key = (unsigned long long)(uint32_t)flag << 32 | (0xFFFFFFFFu - (uint32_t)j);
+                if (key > s.key) { s.key = key; s.id = c; s.hi = (uint32_t)(h >> 32); }
+            }
+        }
+    }
+    // the wave's sums
+    for (int d = 32; d > 0; d >>= 1) {
+        const int c1 = __shfl_xor(s.counter, d), c2 = __shfl_xor(s.counter2, d);
+        const unsigned long long key = __shfl_xor(s.key, d);
+        const uint32_t id = __shfl_xor(s.id, d), hi = __shfl_xor(s.hi, d);
+        s.counter += c1;
+        s.counter2 += c2;
+        if (key > s.key) { s.key = key; s.id = id; s.hi = hi; }
+    }
+    if (lane == 0) {
+        out[r] = s.counter ? map_place((uint64_t)s.id | (uint64_t)s.hi << 32, (int)(0xFFFFFFFFu - (uint32_t)s.key), K, s.counter2, ctgs)
+                           : MapOut{0, 0, 0, 0};
+        if (stats) {                               // the measurement's figures: reads done in passes, distinct ids
+            if (over) atomicAdd(stats, 1ull);
+            atomicAdd(stats + 1, (unsigned long long)n_ids);
+        }
+    }
+}
+
 namespace {
 
 template <typename T>
@@ -172,7 +383,7 @@ public:
         if (!ready_) return;
         (void)hipSetDevice(dev_);
         tab_.release(); flag_.release(); len_.release(); bal_.release(); rwords_.release(); roff_.release(); rlen_.release(); rkoff_.release();
-        rows_.release(); out_.release();
+        rows_.release(); out_.release(); stats_.release();
         if (st_) (void)hipStreamDestroy(st_);
         if (e0_) (void)hipEventDestroy(e0_);
         if (e1_) (void)hipEventDestroy(e1_);
@@ -243,11 +454,12 @@ public:
         }
         return PG_OK;
     }
-    int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out) override {
+    int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out, bool wave) override {
         if (!b.n) return PG_OK;
         MAP_HIP(hipSetDevice(dev_));
         int rc;
         const uint64_t n_k = b.kmer_off[b.n];
+        if (wave && (rc = stats_.reserve(2))) return rc;
         if ((rc = rwords_.reserve(b.n_words)) || (rc = roff_.reserve(b.n)) || (rc = rlen_.reserve(b.n)) || (rc = rkoff_.reserve(b.n + 1)) ||
             (rc = rows_.reserve(std::max<uint64_t>(n_k, 1))) || (rc = out_.reserve(b.n))) return rc;
         const double c0 = now_s();
@@ -255,15 +467,22 @@ public:
         MAP_HIP(hipMemcpyAsync(roff_.p, b.off, b.n * 8, hipMemcpyHostToDevice, st_));
         MAP_HIP(hipMemcpyAsync(rlen_.p, b.len, b.n * 4, hipMemcpyHostToDevice, st_));
         MAP_HIP(hipMemcpyAsync(rkoff_.p, b.kmer_off, (b.n + 1) * 8, hipMemcpyHostToDevice, st_));
+        if (wave) MAP_HIP(hipMemsetAsync(stats_.p, 0, 2 * sizeof(unsigned long long), st_));
         MAP_HIP(hipEventRecord(e0_, st_));
-        const dim3 grid((unsigned)((b.n + 255) / 256)), block(256);
-        if (nw_ == 2) hipLaunchKernelGGL((map_read_kernel<2>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p);
+        const dim3 grid((unsigned)(wave ? (b.n + MAP_WAVES - 1) / MAP_WAVES : (b.n + 255) / 256)), block(256);
+        if (wave && nw_ == 2) hipLaunchKernelGGL((map_read_wave_kernel<2>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p, stats_.p);
+        else if (wave) hipLaunchKernelGGL((map_read_wave_kernel<4>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p, stats_.p);
+        else if (nw_ == 2) hipLaunchKernelGGL((map_read_kernel<2>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p);
         else hipLaunchKernelGGL((map_read_kernel<4>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p);
         MAP_HIP(hipGetLastError());
         MAP_HIP(hipEventRecord(e1_, st_));
         MAP_HIP(hipMemcpyAsync(out, out_.p, b.n * sizeof(MapOut), hipMemcpyDeviceToHost, st_));
         if (rows_out && n_k) MAP_HIP(hipMemcpyAsync(rows_out, rows_.p, n_k * sizeof(uint64_t), hipMemcpyDeviceToHost, st_));
+        unsigned long long stats[2] = {0, 0};
+        if (wave) MAP_HIP(hipMemcpyAsync(stats, stats_.p, sizeof stats, hipMemcpyDeviceToHost, st_));
         MAP_HIP(hipStreamSynchronize(st_));
+        n_passes += stats[0];
+        n_ids += stats[1];
         float ms = 0;
         MAP_HIP(hipEventElapsedTime(&ms, e0_, e1_));
         t_kernel += ms * 1e-3;
@@ -288,9 +507,12 @@ private:
     DevBuf<int32_t> len_, rlen_;
     DevBuf<int8_t> bal_;
     DevBuf<MapOut> out_;
+    DevBuf<unsigned long long> stats_;              // the wave kernel's two figures
 };
 
 }  // namespace
+
+int map_wave_ids() { return MAP_WAVE_IDS; }
 
 std::unique_ptr<MapEngine> map_engine_device(int device, int K, int nw) {
     std::unique_ptr<DeviceMapEngine> e(new DeviceMapEngine(device, K, nw));
