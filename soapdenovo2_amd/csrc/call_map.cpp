@@ -19,6 +19,9 @@
 //      libraries with asm_flags=4 are read one read at a time (pairs = 0: f= and q= files too), mapped a lane a read, or a wavefront
 //      a read with SOAPDENOVO2_AMD_MAP_LONG_KERNEL=wave (lane is the default until the two are measured), and the
 //      footprinted ones written to <prefix>.longReadInGap and, with -f, <prefix>.RlongReadInGap (plain files)
+// Both passes are one loop (run_pass: batches, the BAM take-back, pack_batch, the engine, the timers); a pass brings what it does when
+// the library changes (on_read) and its recorder (Recorder, LongRecorder; both write through RcSeq1, the model of rcSeq[1]).  The 2-bit
+// packer and the BAM record reader are host_reads.cpp's.
 // Not here: without that switch a config with a long-read library (asm_flags=4) is refused before anything is written; one GPU (the
 // first of SOAPDENOVO2_AMD_DEVICES).  SOAPDENOVO2_AMD_MAP_HOST=1 runs the host twin of the index and the read kernels instead (the CPU
 // tests).
@@ -27,7 +30,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 #include <zlib.h>
 
 #include <algorithm>
@@ -46,12 +48,6 @@ void pg_set_error(const std::string& s);
 
 namespace pg {
 namespace {
-
-double now_s() {
-    timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
-}
 
 inline char base2int(char c) { return (char)((c & 0x06) >> 1); }          // inc/def.h:39
 
@@ -157,56 +153,6 @@ void read1seqfq(LineIn& in, char* seq, int& len, int max_len, int line_len, std:
     len = n;
 }
 
-// ---- b=: one record at a time (read1seqbam, readseq1by1.c:449-592).  host_reads.cpp's BAM reader decodes records the same way but pushes
-// whole files at pregraph's sink (with its take-back delay line); map pulls records one by one and takes pairs back itself
-// (prlRead2Ctg.c:875-888), so it has this small pull reader over the same format.
-class BamIn {
-public:
-    explicit BamIn(const std::string& path) {
-        gz_ = gzopen(path.c_str(), "rb");
-        if (!gz_) { fprintf(stderr, "Cannot open %s. Now exit to system...\n", path.c_str()); exit(-1); }
-        gzbuffer(gz_, 1 << 20);
-        char magic[4];
-        int32_t l_text = 0, n_ref = 0;
-        bool ok = need(magic, 4) && !memcmp(magic, "BAM\1", 4) && need(&l_text, 4) && l_text >= 0 && skip((size_t)l_text) && need(&n_ref, 4) && n_ref >= 0;
-        for (int32_t r = 0; ok && r < n_ref; r++) {
-            int32_t l_name = 0, l_ref = 0;
-            ok = need(&l_name, 4) && l_name >= 0 && skip((size_t)l_name) && need(&l_ref, 4);
-        }
-        if (!ok) { fprintf(stderr, "Cannot read the header.\n"); exit(-1); }
-    }
-    ~BamIn() { close(); }
-    void close() { if (gz_) gzclose(gz_); gz_ = nullptr; }
-    // one record: false = end of file (samread < 0).  flag and the SEQ column's bases (cut to max_len characters) are returned
-    bool next(uint16_t& flag, char* seq, int& n, int max_len) {
-        n = 0;
-        if (!gz_) return false;
-        int32_t block = 0;
-        if (!need(&block, 4) || block < 32) return false;
-        rec_.resize((size_t)block);
-        if (!need(rec_.data(), (size_t)block)) return false;
-        const uint32_t l_read_name = rec_[8];
-        uint16_t n_cigar;
-        int32_t l_seq;
-        memcpy(&n_cigar, rec_.data() + 12, 2); memcpy(&flag, rec_.data() + 14, 2); memcpy(&l_seq, rec_.data() + 16, 4);
-        const size_t seq_at = 32 + (size_t)l_read_name + 4 * (size_t)n_cigar;
-        if (l_seq < 0 || seq_at + ((size_t)l_seq + 1) / 2 > (size_t)block) return false;
-        static const char nt16[] = "=ACMGRSVTWYHKDBN";
-        const int look = std::min((int)l_seq, std::max(max_len, 0));
-        for (int j = 0; j < look; j++) {
-            const char ch = nt16[(rec_[seq_at + (size_t)(j >> 1)] >> ((~j & 1) << 2)) & 0xf];
-            if (ch >= 'A' && ch <= 'Z') seq[n++] = base2int(ch);
-        }
-        return true;
-    }
-
-private:
-    bool need(void* dst, size_t n) { return gzread(gz_, dst, (unsigned)n) == (int)n; }
-    bool skip(size_t n) { char tmp[4096]; while (n) { const size_t k = std::min(n, sizeof tmp); if (!need(tmp, k)) return false; n -= k; } return true; }
-    gzFile gz_ = nullptr;
-    std::vector<uint8_t> rec_;
-};
-
 void reverse2k(char* s, int n) {                                    // readseq1by1.c:788-802
     std::reverse(s, s + n);
     for (int i = 0; i < n; i++) s[i] ^= 2;
@@ -284,7 +230,7 @@ public:
             return true;
         }
         if (T.type == 6) read1seqfq(*T.fp1, seq, len, max_len_, ll(), str_);
-        else if (T.type == 4) read_bam(T, seq, len, type, cfg_.libs[i].asm_flag);
+        else if (T.type == 4) read_bam(T, seq, len, type);
         else readseq1by1(*T.fp1, seq, nm, len, 1, max_len_, ll(), str_);
         if (rev) reverse2k(seq, len);
         if ((T.type != 4 && (len > 0 || !T.fp1->eof())) || (T.type == 4 && (len > 0 || readstate_ >= 0))) { n_solexa++; return true; }
@@ -295,7 +241,7 @@ private:
     struct Lib {
         int type = 1, index = 0, paired = 0;
         std::unique_ptr<LineIn> fp1, fp2;
-        std::unique_ptr<BamIn> fp3;
+        std::unique_ptr<BamReader> fp3;
     };
     int ll() const { return line_len_ > 0 ? line_len_ : max_len_ + 1; }
     size_t files_of(const LibInfo& L, int type) const {
@@ -338,27 +284,21 @@ private:
         } else if (S.type == 4) {
             const std::string a = trim(L.b[S.index]);
             say(a);
-            S.fp3.reset(new BamIn(a));
+            S.fp3.reset(new BamReader(a));
             S.paired = 0;
         }
         S.index++;
     }
-    // read1seqbam's pairing state machine (readseq1by1.c:470-575); map reads only asm_flags 2 / 3 libs, so no record is skipped
-    void read_bam(Lib& T, char* seq, int& len, int& type, int) {
+    // b=: one record (host_reads.hpp's BamReader) through read1seqbam's pairing step; type = -1: the pair is taken back.  map reads only
+    // asm_flags 2 / 3 libs and the long pass asm_flags 4, so no record is skipped
+    void read_bam(Lib& T, char* seq, int& len, int& type) {
         type = 0;
         uint16_t flag = 0;
-        int n = 0;
-        readstate_ = T.fp3->next(flag, seq, n, max_len_) ? 0 : -1;
-        if (readstate_ >= 0) {
-            if (flag & 0x0200) {
-                switch (bam_state_) { case -3: bam_state_ = -2; break; case -2: bam_state_ = 0; break; case -1: bam_state_ = 2; break; default: bam_state_ = -3; }
-            } else {
-                switch (bam_state_) { case -3: bam_state_ = -1; break; case -2: bam_state_ = 1; break; case -1: bam_state_ = 3; break; default: bam_state_ = -3; }
-            }
-            if (bam_state_ == 3) bam_state_ = -3;
-            else if (bam_state_ == 0 || bam_state_ == 1 || bam_state_ == 2) { bam_state_ = -3; type = -1; }
-        } else bam_state_ = -3;
-        len = n;
+        readstate_ = T.fp3->next(flag, (uint8_t*)seq, len, max_len_) ? 0 : -1;
+        if (readstate_ < 0) { bam_state_ = -3; return; }
+        const BamPair pair = bam_pair_step(bam_state_, (flag & 0x0200) != 0);
+        bam_state_ = pair.state;
+        if (pair.take_back) type = -1;
     }
     const LibConfig& cfg_;
     int all_, max_len_, line_len_;
@@ -431,10 +371,64 @@ struct Options {
 
 // ---- the batch: reads as read, their packed images, the kernel's answers and recordAlldgn (prlRead2Ctg.c:627-725) ----
 struct Batch {
-    std::vector<char> seq;                 // read r at r * row
+    std::vector<char> seq;                 // read r at r * row; a row has 8 bytes past the longest read (pack_codes)
     std::vector<int32_t> len, ins;
     size_t row = 0, n = 0;
+    const char* read(size_t t) const { return seq.data() + t * row; }
+    void grow(size_t cap) { seq.resize(cap * row); len.resize(cap); ins.resize(cap); }
 };
+
+// the batch as the engines take it (MapBatch): pg_pack_read's layout, koff[r] = k-mers of the reads before r
+void pack_batch(const Batch& b, int K, std::vector<uint64_t>& words, std::vector<uint64_t>& off, std::vector<uint64_t>& koff) {
+    words.clear(); off.resize(b.n); koff.resize(b.n + 1);
+    koff[0] = 0;
+    for (size_t t = 0; t < b.n; t++) {
+        const int L = b.len[t];
+        off[t] = words.size();
+        words.resize(off[t] + ((size_t)L + 31) / 32);
+        pack_codes((const uint8_t*)b.read(t), L, words.data() + off[t]);
+        koff[t + 1] = koff[t] + (L >= K + 1 ? (uint64_t)(L - K + 1) : 0);
+    }
+    words.resize(words.size() + 8, 0);                              // read_kmer reads NW + 1 words from a k-mer's first word on
+}
+
+// rcSeq[1] of prlRead2Ctg.c: calloc'ed once, maxReadLen bytes, then what the chop stage and the writers leave in it
+struct RcSeq1 {
+    std::vector<char> buf;
+    explicit RcSeq1(int max_len) : buf((size_t)max_len + 8, 0) {}
+    // the chop stage: thread 0 (reads t % p == 0 of K + 1 bases or more) reverse-complements each of its reads into it (chopKmer4read,
+    // :153-231 -- the buffer is rcSeq[threadID] with threadID = 1 for thread 0)
+    void chop(const Batch& b, int K, int p) {
+        for (size_t t = 0; t < b.n; t += (size_t)p) {
+            const int L = b.len[t];
+            if (L < K + 1) continue;
+            const char* s = b.read(t);
+            for (int i = 0; i < L; i++) buf[(size_t)i] = (char)(s[L - 1 - i] ^ 2);
+        }
+    }
+    // the 2-bit image of read t, packed into it with masked writes (writeChar2tightString, seq.c:81-107): L / 4 + 1 bytes, the bits past
+    // the read are what the buffer held before
+    const char* tight(const Batch& b, size_t t) {
+        const char* s = b.read(t);
+        const int L = b.len[t];
+        for (int i = 0; i < L; i++) {
+            char& byte = buf[(size_t)(i / 4)];
+            const int sh = 6 - 2 * (i % 4);
+            byte = (char)((byte & ~(3 << sh)) | ((s[i] & 3) << sh));
+        }
+        return buf.data();
+    }
+};
+
+// the text record of .shortreadInGap and .RlongReadInGap (output1read_gz / output1read, :427-492)
+void put_text_read(std::string& x, const Batch& b, size_t t, int ctg, int pos, char orient, int dh) {
+    const int L = b.len[t];
+    char h[128];
+    x.append(h, (size_t)snprintf(h, sizeof h, ">%d\t%d\t%d\t%c\t%d\t%d\n", L, ctg, pos, orient, b.ins[t], dh));
+    const char* q = b.read(t);
+    for (int i = 0; i < L; i++) x.push_back("ACTG"[q[i] & 3]);
+    x.push_back('\n');
+}
 
 struct Recorder {
     const Options& o;
@@ -443,38 +437,21 @@ struct Recorder {
     GzOut& in_gap;
     GzOut* short_gap;                      // -f
     GzOut* pe_on_ctg;                      // -f
-    std::vector<char> rc1;                 // rcSeq[1] of prlRead2Ctg.c: calloc'ed, maxReadLen bytes
+    RcSeq1 rc1;
     long long readCounter = 0, mapCounter = 0, readsInGap = 0;
     std::vector<uint32_t> ctg;
     std::vector<int32_t> pos;
     std::vector<uint8_t> orien, fp;
 
-    // the 2-bit image of read t, packed into rcSeq[1] with masked writes (writeChar2tightString, seq.c:81-107): the bits past the read
-    // are what the buffer held before
-    void tight(const Batch& b, size_t t) {
-        const char* s = b.seq.data() + t * b.row;
-        const int L = b.len[t];
-        for (int i = 0; i < L; i++) {
-            char& byte = rc1[(size_t)(i / 4)];
-            const int sh = 6 - 2 * (i % 4);
-            byte = (char)((byte & ~(3 << sh)) | ((s[i] & 3) << sh));
-        }
-    }
     void output1read(const Batch& b, size_t t, char orient, int dh) {          // output1read_gz (:427-451)
         const int L = b.len[t];
         readsInGap++;
-        tight(b, t);
         std::string& s = in_gap.buf;
         put_bin(s, L); put_bin(s, (int32_t)ctg[t]); put_bin(s, pos[t]);
-        s.append(rc1.data(), (size_t)(L / 4 + 1));
+        s.append(rc1.tight(b, t), (size_t)(L / 4 + 1));
         in_gap.maybe_flush();
         if (o.fill && b.ins[t] < 2000 && L > 0) {
-            std::string& x = short_gap->buf;
-            char h[128];
-            x.append(h, (size_t)snprintf(h, sizeof h, ">%d\t%d\t%d\t%c\t%d\t%d\n", L, (int)ctg[t], pos[t], orient, b.ins[t], dh));
-            const char* q = b.seq.data() + t * b.row;
-            for (int i = 0; i < L; i++) x.push_back("ACTG"[q[i] & 3]);
-            x.push_back('\n');
+            put_text_read(short_gap->buf, b, t, (int)ctg[t], pos[t], orient, dh);
             short_gap->maybe_flush();
         }
     }
@@ -483,8 +460,7 @@ struct Recorder {
         std::string& s = pe_on_ctg->buf;
         for (size_t r : {t - 1, t}) {
             put_bin(s, b.len[r]); put_bin(s, (int32_t)ctg[r]); put_bin(s, pos[r]); put_bin(s, (char)orien[r]); put_bin(s, b.ins[r]);
-            tight(b, r);
-            s.append(rc1.data(), (size_t)(b.len[r] / 4 + 1));
+            s.append(rc1.tight(b, r), (size_t)(b.len[r] / 4 + 1));
         }
         pe_on_ctg->maybe_flush();
     }
@@ -506,14 +482,7 @@ struct Recorder {
             ctg[t] = out[t].ctg; pos[t] = out[t].pos; fp[t] = out[t].footprint;
             if (out[t].ctg) orien[t] = out[t].orien;
         }
-        // what the chop stage left in rcSeq[1]: thread 0 (reads t % p == 0 of K + 1 bases or more) reverse-complements each of its reads
-        // into it (chopKmer4read, :153-231 -- the buffer is rcSeq[threadID] with threadID = 1 for thread 0)
-        for (size_t t = 0; t < n; t += (size_t)p) {
-            const int L = b.len[t];
-            if (L < K + 1) continue;
-            const char* s = b.seq.data() + t * b.row;
-            for (int i = 0; i < L; i++) rc1[(size_t)i] = (char)(s[L - 1 - i] ^ 2);
-        }
+        rc1.chop(b, K, p);
         std::string& oc = on_ctg.buf;
         char line[96];
         for (size_t t = 0; t < n; t++) {
@@ -592,8 +561,8 @@ void read_contigs(const std::string& prefix, int K, MapContigs& c, long long& nu
         c.id.push_back(contigId > 0 ? (uint32_t)contigId : (uint32_t)i);
         c.len.push_back(len);
         const size_t w0 = c.words.size(), nw = ((size_t)len + 31) / 32;
-        c.words.resize(w0 + nw, 0);
-        for (int j = 0; j < len; j++) c.words[w0 + (size_t)(j >> 5)] |= (uint64_t)(seq[(size_t)j] & 3) << (62 - 2 * (j & 31));
+        c.words.resize(w0 + nw);
+        pack_codes((const uint8_t*)seq.data(), len, c.words.data() + w0);
         c.off.push_back(c.words.size());
         c.n_kmers += (uint64_t)(len - K + 1);
     }
@@ -628,8 +597,102 @@ void contig_info(const std::string& prefix, std::vector<int32_t>& len, std::vect
     fclose(fp);
 }
 
-// prlLongRead2Ctg (prlRead2Ctg.c:1080-1298) with recordLongRead and output1read (:456-492, :612-625): the libraries with asm_flags=4,
-// a read at a time, a batch through the engine, the footprinted reads into <prefix>.longReadInGap (and .RlongReadInGap with -f).
+// recordLongRead and output1read (prlRead2Ctg.c:456-492, :612-625): the footprinted reads into <prefix>.longReadInGap and, with -f,
+// .RlongReadInGap (plain files, written a batch at a time)
+struct LongRecorder {
+    const Options& o;
+    int K;
+    RcSeq1 rc1;
+    FILE* fp1;
+    FILE* fp2;                             // -f
+    long long readCounter = 0, readsInGap = 0;
+    std::string out1, out2;
+    LongRecorder(const Options& opt, int k, int max_len) : o(opt), K(k), rc1(max_len) {
+        fp1 = fopen((o.prefix + ".longReadInGap").c_str(), "wb");
+        fp2 = o.fill ? fopen((o.prefix + ".RlongReadInGap").c_str(), "w") : nullptr;
+        if (!fp1 || (o.fill && !fp2)) { fprintf(stderr, "Cannot open %s.longReadInGap. Now exit to system...\n", o.prefix.c_str()); exit(-1); }
+    }
+    ~LongRecorder() { close(); }
+    void close() {
+        if (fp1) fclose(fp1);
+        if (fp2) fclose(fp2);
+        fp1 = fp2 = nullptr;
+    }
+    void record(const Batch& b, const std::vector<MapOut>& res, int p) {
+        rc1.chop(b, K, p);
+        for (size_t t = 0; t < b.n; t++) {
+            readCounter++;
+            if (!res[t].footprint) continue;
+            readsInGap++;
+            const int L = b.len[t];
+            put_bin(out1, L); put_bin(out1, (int32_t)res[t].ctg); put_bin(out1, res[t].pos);
+            out1.append(rc1.tight(b, t), (size_t)(L / 4 + 1));
+            if (o.fill && L > 0) put_text_read(out2, b, t, (int)res[t].ctg, res[t].pos, (char)res[t].orien, 0);      // insSizeArray[t] = 18 < 2000 always
+        }
+        fwrite(out1.data(), 1, out1.size(), fp1);
+        if (fp2) fwrite(out2.data(), 1, out2.size(), fp2);
+        out1.clear(); out2.clear();
+    }
+};
+
+// ---- one pass over the libraries: the loop of prlRead2Ctg (:865-945) and prlLongRead2Ctg (:1182-1250) ----
+struct PassTimes {
+    double parse = 0, pack = 0, map = 0, record = 0;
+    bool tail = false;                     // the reads ended inside a batch (the reference's summaries are printed behind that batch only)
+};
+
+// Reads come from rd one by one into batches of maxReadNum (the buffers grow up to that from first_cap); a batch is packed, mapped with
+// the ALIGNLEN that stands after its last read, and handed to record(batch, answers).  on_read(lib, first, L, align_len) is the pass's
+// own part: called for every read that is kept (L bases, of library lib; first = the library has changed), it sets ALIGNLEN and returns
+// the read's insert size.  Returns 0, or -1 after an engine error (reported).
+template <typename OnRead, typename Record>
+int run_pass(const LibConfig& cfg, LibReader& rd, int max_len, size_t first_cap, long long maxReadNum, int K, MapEngine& eng, bool wave,
+             OnRead on_read, Record record, PassTimes& tm) {
+    Batch b;
+    b.row = (size_t)max_len + 8;
+    b.grow(std::min((size_t)maxReadNum, first_cap));
+    std::vector<uint64_t> words, off, koff;
+    std::vector<MapOut> res;
+    int align_len = 0, libNo = 0, prevLibNo = -1, type = 0;
+    auto flush = [&]() -> int {
+        const double a = now_s();
+        pack_batch(b, K, words, off, koff);
+        res.resize(b.n);
+        const double c = now_s();
+        const int e = eng.map(MapBatch{words.data(), words.size(), off.data(), b.len.data(), koff.data(), b.n}, align_len, res.data(), nullptr, wave);
+        if (e) { fprintf(stderr, "map: %s\n", pg_last_error()); return -1; }
+        const double d = now_s();
+        record(b, res);
+        tm.pack += c - a; tm.map += d - c; tm.record += now_s() - d;
+        b.n = 0;
+        return 0;
+    };
+    double r0 = now_s();
+    for (;;) {
+        if (b.n == b.len.size()) b.grow(std::min((size_t)maxReadNum, b.len.size() * 2));
+        int L = 0;
+        if (!rd.next(b.seq.data() + b.n * b.row, L, libNo, type)) break;
+        if (type == -1) {                                           // a bad BAM pair goes back (:875-888, :1184-1196)
+            if (b.n) b.n--;
+            rd.n_solexa -= 2;
+            continue;
+        }
+        b.len[b.n] = L;
+        b.ins[b.n] = on_read(cfg.libs[(size_t)libNo], libNo != prevLibNo, L, align_len);
+        prevLibNo = libNo;
+        b.n++;
+        if ((long long)b.n == maxReadNum) {
+            tm.parse += now_s() - r0;
+            if (flush()) return -1;
+            r0 = now_s();
+        }
+    }
+    tm.parse += now_s() - r0;
+    tm.tail = b.n > 0;
+    return tm.tail ? flush() : 0;
+}
+
+// prlLongRead2Ctg (prlRead2Ctg.c:1080-1298): the libraries with asm_flags=4, a read at a time (run_pass), the footprinted reads to LongRecorder.
 // Returns longReadLen (0: no such library, nothing done, no file), -1 on an engine error.
 int long_pass(const LibConfig& cfg, const Options& o, int K, MapEngine& eng, bool wave, int max_rd_len) {
     int long_len = 0;                                               // getMaxLongReadLen (lib.c:43-68)
@@ -644,114 +707,28 @@ int long_pass(const LibConfig& cfg, const Options& o, int K, MapEngine& eng, boo
     maxReadNum = maxReadNum % 2 == 0 ? maxReadNum : maxReadNum - 1;
     // (this repository's own guard: the reference divides by longReadLen - K + 1 as it is and goes on)
     if (long_len < K || maxReadNum < 2) { fprintf(stderr, "Long read length %d is too small for K = %d.\n", long_len, K); return -1; }
-    FILE* fp1 = fopen((o.prefix + ".longReadInGap").c_str(), "wb");
-    FILE* fp2 = o.fill ? fopen((o.prefix + ".RlongReadInGap").c_str(), "w") : nullptr;
-    if (!fp1 || (o.fill && !fp2)) { fprintf(stderr, "Cannot open %s.longReadInGap. Now exit to system...\n", o.prefix.c_str()); exit(-1); }
+    LongRecorder rec(o, K, max_len_all);
     LibReader rd(cfg, max_len_all, long_len, true);
-    Batch b;
-    b.row = (size_t)max_len_all + 8;
-    const size_t cap = (size_t)std::min<long long>(maxReadNum, 1 << 12);
-    b.seq.resize(cap * b.row);
-    b.len.resize(cap);
-    std::vector<char> rc1((size_t)max_len_all + 8, 0);              // rcSeq[1]: zeroed once, then what the chop and the writes leave
-    std::vector<uint64_t> words, off, koff;
-    std::vector<MapOut> res;
-    std::string out1, out2;
-    long long readCounter = 0, readsInGap = 0;
-    double t_read = 0, t_pack = 0, t_map = 0, t_rec = 0;
     const double k0 = eng.t_kernel, c0 = eng.t_copy;
-    int align_len = 0, libNo = 0, prevLibNo = -1, type = 0;
-    auto flush = [&]() -> int {
-        const double a = now_s();
-        words.clear(); off.resize(b.n); koff.resize(b.n + 1);
-        koff[0] = 0;
-        for (size_t t = 0; t < b.n; t++) {
-            const int L = b.len[t];
-            off[t] = words.size();
-            const size_t w0 = words.size();
-            words.resize(w0 + ((size_t)L + 31) / 32, 0);
-            const char* s = b.seq.data() + t * b.row;
-            for (int j = 0; j < L; j++) words[w0 + (size_t)(j >> 5)] |= (uint64_t)(s[j] & 3) << (62 - 2 * (j & 31));
-            koff[t + 1] = koff[t] + (L >= K + 1 ? (uint64_t)(L - K + 1) : 0);
-        }
-        words.resize(words.size() + 8, 0);
-        res.resize(b.n);
-        const double c = now_s();
-        const int e = eng.map(MapBatch{words.data(), words.size(), off.data(), b.len.data(), koff.data(), b.n}, align_len, res.data(), nullptr, wave);
-        if (e) { fprintf(stderr, "map: %s\n", pg_last_error()); return e; }
-        const double d = now_s();
-        // chop thread 0's reverse complements (reads t % p == 0 of K + 1 bases or more), then recordLongRead in read order
-        for (size_t t = 0; t < b.n; t += (size_t)o.p) {
-            const int L = b.len[t];
-            if (L < K + 1) continue;
-            const char* s = b.seq.data() + t * b.row;
-            for (int i = 0; i < L; i++) rc1[(size_t)i] = (char)(s[L - 1 - i] ^ 2);
-        }
-        for (size_t t = 0; t < b.n; t++) {
-            readCounter++;
-            if (!res[t].footprint) continue;
-            readsInGap++;
-            const char* s = b.seq.data() + t * b.row;
-            const int L = b.len[t];
-            for (int i = 0; i < L; i++) {                           // writeChar2tightString (seq.c:81-107)
-                char& byte = rc1[(size_t)(i / 4)];
-                const int sh = 6 - 2 * (i % 4);
-                byte = (char)((byte & ~(3 << sh)) | ((s[i] & 3) << sh));
-            }
-            put_bin(out1, L); put_bin(out1, (int32_t)res[t].ctg); put_bin(out1, res[t].pos);
-            out1.append(rc1.data(), (size_t)(L / 4 + 1));
-            if (o.fill && L > 0) {                                  // insSizeArray[t] = 18 < 2000 always
-                char h[128];
-                out2.append(h, (size_t)snprintf(h, sizeof h, ">%d\t%d\t%d\t%c\t%d\t%d\n", L, (int)res[t].ctg, res[t].pos, (char)res[t].orien, 18, 0));
-                for (int i = 0; i < L; i++) out2.push_back("ACTG"[s[i] & 3]);
-                out2.push_back('\n');
-            }
-        }
-        fwrite(out1.data(), 1, out1.size(), fp1);
-        if (fp2) fwrite(out2.data(), 1, out2.size(), fp2);
-        out1.clear(); out2.clear();
-        t_pack += c - a; t_map += d - c; t_rec += now_s() - d;
-        b.n = 0;
-        return 0;
-    };
-    double r0 = now_s();
-    for (;;) {
-        if (b.n == b.len.size()) {
-            const size_t nc = std::min<size_t>((size_t)maxReadNum, b.len.size() * 2);
-            b.seq.resize(nc * b.row); b.len.resize(nc);
-        }
-        int L = 0;
-        if (!rd.next(b.seq.data() + b.n * b.row, L, libNo, type)) break;
-        if (type == -1) {                                           // a bad BAM pair goes back (:1184-1196)
-            if (b.n) b.n--;
-            rd.n_solexa -= 2;
-            continue;
-        }
-        b.len[b.n] = L;
-        if (libNo != prevLibNo) {                                   // :1198-1204
-            prevLibNo = libNo;
-            align_len = std::max(cfg.libs[(size_t)libNo].map_len, 35);
+    auto on_read = [](const LibInfo& lib, bool first, int, int& align_len) {              // :1198-1206
+        if (first) {
+            align_len = std::max(lib.map_len, 35);
             fprintf(stderr, "Map_len %d.\n", align_len);
         }
-        b.n++;
-        if ((long long)b.n == maxReadNum) {
-            t_read += now_s() - r0;
-            if (flush()) { fclose(fp1); if (fp2) fclose(fp2); return -1; }
-            r0 = now_s();
-        }
-    }
-    t_read += now_s() - r0;
-    if (b.n) {
-        if (flush()) { fclose(fp1); if (fp2) fclose(fp2); return -1; }
-        fprintf(stderr, "Output %lld out of %lld (%.1f)%% reads in gaps.\n", readsInGap, readCounter, (float)readsInGap / readCounter * 100);
-    }
-    fclose(fp1);
-    if (fp2) fclose(fp2);
+        return 18;
+    };
+    PassTimes tm;
+    const int e = run_pass(cfg, rd, max_len_all, 1 << 12, maxReadNum, K, eng, wave, on_read,
+                           [&](const Batch& b, const std::vector<MapOut>& res) { rec.record(b, res, o.p); }, tm);
+    rec.close();
+    if (e) return -1;
+    if (tm.tail)
+        fprintf(stderr, "Output %lld out of %lld (%.1f)%% reads in gaps.\n", rec.readsInGap, rec.readCounter, (float)rec.readsInGap / rec.readCounter * 100);
     fprintf(stderr, "%d reads deleted.\n", 0);
     if (env_user("PG_HOST_VERBOSE"))
         fprintf(stderr, "[map long] %s kernel: %lld reads, parse %.3fs, pack %.3fs, map %.3fs (kernel %.6fs, copies %.3fs), record %.3fs; "
                         "reads done in passes %llu, distinct ids %llu\n",
-                wave ? "wave" : "lane", readCounter, t_read, t_pack, t_map, eng.t_kernel - k0, eng.t_copy - c0, t_rec,
+                wave ? "wave" : "lane", rec.readCounter, tm.parse, tm.pack, tm.map, eng.t_kernel - k0, eng.t_copy - c0, tm.record,
                 (unsigned long long)eng.n_passes, (unsigned long long)eng.n_ids);
     return long_len;
 }
@@ -864,78 +841,24 @@ int run_map(int argc, char** argv, bool mer127) {
         short_gap.reset(new GzOut(o.prefix + ".shortreadInGap.gz", workers));
         pe_on.reset(new GzOut(o.prefix + ".PEreadOnContig.gz", workers));
     }
-    Recorder rec{o, K, on_ctg, in_gap, short_gap.get(), pe_on.get(), std::vector<char>((size_t)max_all + 8, 0)};
+    Recorder rec{o, K, on_ctg, in_gap, short_gap.get(), pe_on.get(), RcSeq1(max_all)};
     on_ctg.buf += "read\tcontig\tpos\n";
     LibReader rd(cfg, max_all, max_all);
-    Batch b;
-    b.row = (size_t)max_all + 8;
-    const size_t cap = (size_t)std::min<long long>(maxReadNum, 1 << 22);
-    b.seq.resize(cap * b.row);
-    b.len.resize(cap);
-    b.ins.resize(cap);
-    std::vector<uint64_t> words, off, koff;
-    std::vector<MapOut> res;
-    double t_read = 0, t_pack = 0, t_map = 0, t_rec = 0;
-    int align_len = 0, insSize = 0, libNo = 0, prevLibNo = -1, type = 0;
-    auto flush = [&]() -> int {
-        const double a = now_s();
-        words.clear(); off.resize(b.n); koff.resize(b.n + 1);
-        koff[0] = 0;
-        for (size_t t = 0; t < b.n; t++) {
-            const int L = b.len[t];
-            off[t] = words.size();
-            const size_t w0 = words.size();
-            words.resize(w0 + ((size_t)L + 31) / 32, 0);
-            const char* s = b.seq.data() + t * b.row;
-            for (int j = 0; j < L; j++) words[w0 + (size_t)(j >> 5)] |= (uint64_t)(s[j] & 3) << (62 - 2 * (j & 31));
-            koff[t + 1] = koff[t] + (L >= K + 1 ? (uint64_t)(L - K + 1) : 0);
-        }
-        words.resize(words.size() + 8, 0);
-        res.resize(b.n);
-        const double c = now_s();
-        const int e = eng->map(MapBatch{words.data(), words.size(), off.data(), b.len.data(), koff.data(), b.n}, align_len, res.data());
-        if (e) { fprintf(stderr, "map: %s\n", pg_last_error()); return e; }
-        const double d = now_s();
-        rec.record(b, res, o.p);
-        t_pack += c - a; t_map += d - c; t_rec += now_s() - d;
-        b.n = 0;
-        return 0;
-    };
-    double r0 = now_s();
-    for (;;) {
-        if (b.n == b.len.size()) {                                  // the buffers grow up to maxReadNum
-            const size_t nc = std::min<size_t>((size_t)maxReadNum, b.len.size() * 2);
-            b.seq.resize(nc * b.row); b.len.resize(nc); b.ins.resize(nc);
-        }
-        int L = 0;
-        if (!rd.next(b.seq.data() + b.n * b.row, L, libNo, type)) break;
-        if (type == -1) {                                           // a bad pair goes back (:875-888)
-            if (b.n) b.n--;
-            rd.n_solexa -= 2;
-            continue;
-        }
-        b.len[b.n] = L;
-        if (libNo != prevLibNo) {                                   // :890-904
-            prevLibNo = libNo;
-            insSize = cfg.libs[(size_t)libNo].avg_ins;
-            align_len = cfg.libs[(size_t)libNo].map_len;
-            align_len = insSize > 1000 ? std::max(align_len, 35) : std::max(align_len, 32);
+    int insSize = 0;
+    auto on_read = [&insSize](const LibInfo& lib, bool first, int L, int& align_len) {   // :890-904
+        if (first) {
+            insSize = lib.avg_ins;
+            align_len = insSize > 1000 ? std::max(lib.map_len, 35) : std::max(lib.map_len, 32);
             fprintf(stderr, "Current insert size is %d, map_len is %d.\n", insSize, align_len);
         }
-        b.ins[b.n] = insSize;
         if (insSize > 1000) align_len = std::max(align_len, L / 2 + 1);
-        b.n++;
-        if ((long long)b.n == maxReadNum) {
-            t_read += now_s() - r0;
-            if ((rc = flush())) return 1;
-            r0 = now_s();
-        }
-    }
-    t_read += now_s() - r0;
-    const bool tail = b.n > 0;
-    if (tail && (rc = flush())) return 1;
+        return insSize;
+    };
+    PassTimes tm;
+    if (run_pass(cfg, rd, max_all, (size_t)1 << 22, maxReadNum, K, *eng, false, on_read,
+                 [&](const Batch& b, const std::vector<MapOut>& res) { rec.record(b, res, o.p); }, tm)) return 1;
     const double t3 = now_s();
-    if (tail) {
+    if (tm.tail) {
         fprintf(stderr, "\nTotal reads         %lld\n", rec.readCounter);
         fprintf(stderr, "Reads in gaps       %lld\n", rec.readsInGap);
         fprintf(stderr, "Ratio               %.1f%%\n", (float)rec.readsInGap / rec.readCounter * 100);
@@ -959,7 +882,7 @@ int run_map(int argc, char** argv, bool mer127) {
     if (env_user("PG_HOST_VERBOSE"))
         fprintf(stderr, "[map] contigs %.3fs, index %.3fs (device %.3fs), reads: parse %.3fs, pack %.3fs, map %.3fs (kernel %.3fs, copies %.3fs), "
                         "record %.3fs, files %.3fs (deflate waits %.3fs); whole stage %.3fs\n",
-                t1 - t0, t2 - t1, eng->t_index, t_read, t_pack, t_map, eng->t_kernel, eng->t_copy, t_rec, t4 - t3,
+                t1 - t0, t2 - t1, eng->t_index, tm.parse, tm.pack, tm.map, eng->t_kernel, eng->t_copy, tm.record, t4 - t3,
                 on_ctg.t_deflate + in_gap.t_deflate, t4 - t_start);
     fprintf(stderr, "Overall time spent on alignment: %dm.\n\n", (int)(t4 - t_start) / 60);
     return 0;

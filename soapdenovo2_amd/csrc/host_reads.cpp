@@ -814,7 +814,8 @@ void ReadSink::on_packed(const uint64_t* words, const int32_t* lens, size_t n, i
 }
 
 // ---- b=: BAM (read1seqbam / read1seqInLibBam, readseq1by1.c:449-592,1248-1280; the loops of prlHashReads.c:408-455 and
-// prlRead2path.c:902-960).  An own reader over zlib: a BAM file is a series of gzip members (BGZF), which gzread() inflates
+// prlRead2path.c:902-960).  An own reader over zlib (BamReader: pregraph's stream_bam below and map's LibReader pull records from it,
+// and both pair them with bam_pair_step, read1seqbam's state machine, readseq1by1.c:470-575): a BAM file is a series of gzip members (BGZF), which gzread() inflates
 // one after the other; inside, the header and then records of block_size bytes (SAM/BAM specification 4.2).  What the
 // reference makes of a record: the SEQ column of its SAM text ("=ACMGRSVTWYHKDBN" per 4-bit code; letters go through
 // base2int, '=' and '*' are no letters and vanish), cut to the lib's read length, reverse_seq applied.
@@ -836,12 +837,12 @@ void ReadSink::on_packed(const uint64_t* words, const int32_t* lens, size_t n, i
 static int g_bam_pair_state = -3;
 int bam_pair_state(bool set, int value) { if (set) g_bam_pair_state = value; return g_bam_pair_state; }
 
-static long long stream_bam(const InputFile& in, ReadSink& sink) {
-    gzFile fp = gzopen(in.path1.c_str(), "rb");
-    if (!fp) { fprintf(stderr, "Cannot open %s. Now exit to system...\n", in.path1.c_str()); exit(-1); }
-    gzbuffer(fp, 1 << 20);
-    auto need = [&](void* dst, size_t n) { return gzread(fp, dst, (unsigned)n) == (int)n; };
-    auto skip = [&](size_t n) { char tmp[4096]; while (n) { const size_t k = std::min(n, sizeof tmp); if (!need(tmp, k)) return false; n -= k; } return true; };
+void pack_codes(const uint8_t* codes, int n, uint64_t* out) { g_pack(codes, n, out); }
+
+BamReader::BamReader(const std::string& path) {
+    gz_ = gzopen(path.c_str(), "rb");
+    if (!gz_) { fprintf(stderr, "Cannot open %s. Now exit to system...\n", path.c_str()); exit(-1); }
+    gzbuffer(gz_, 1 << 20);
     char magic[4];
     int32_t l_text = 0, n_ref = 0;
     bool ok = need(magic, 4) && !memcmp(magic, "BAM\1", 4) && need(&l_text, 4) && l_text >= 0 && skip((size_t)l_text) && need(&n_ref, 4) && n_ref >= 0;
@@ -850,43 +851,67 @@ static long long stream_bam(const InputFile& in, ReadSink& sink) {
         ok = need(&l_name, 4) && l_name >= 0 && skip((size_t)l_name) && need(&l_ref, 4);
     }
     if (!ok) { fprintf(stderr, "Cannot read the header.\n"); exit(-1); }
+}
+void BamReader::close() { if (gz_) gzclose(gz_); gz_ = nullptr; }
+bool BamReader::need(void* dst, size_t n) { return gzread(gz_, dst, (unsigned)n) == (int)n; }
+bool BamReader::skip(size_t n) {
+    char tmp[4096];
+    for (; n; n -= std::min(n, sizeof tmp))
+        if (!need(tmp, std::min(n, sizeof tmp))) return false;
+    return true;
+}
+bool BamReader::next(uint16_t& flag, uint8_t* codes, int& n, int max_len) {
+    n = 0;
+    if (!gz_) return false;
+    int32_t block = 0;
+    if (!need(&block, 4) || block < 32) return false;                // end of file (or a truncated one: samread < 0 ends the file too)
+    rec_.resize((size_t)block);
+    if (!need(rec_.data(), (size_t)block)) return false;
+    const uint32_t l_read_name = rec_[8];
+    uint16_t n_cigar;
+    int32_t l_seq;
+    memcpy(&n_cigar, rec_.data() + 12, 2); memcpy(&flag, rec_.data() + 14, 2); memcpy(&l_seq, rec_.data() + 16, 4);
+    const size_t seq_at = 32 + (size_t)l_read_name + 4 * (size_t)n_cigar;
+    if (l_seq < 0 || seq_at + ((size_t)l_seq + 1) / 2 > (size_t)block) return false;
+    // the SEQ column: l_seq characters ("*" when there are none, which is no letter), the first max_len of them looked at
+    static const char nt16[] = "=ACMGRSVTWYHKDBN";
+    const int look = std::min((int)l_seq, std::max(max_len, 0));
+    for (int j = 0; j < look; j++) {
+        const char ch = nt16[(rec_[seq_at + (size_t)(j >> 1)] >> ((~j & 1) << 2)) & 0xf];
+        if (ch >= 'A' && ch <= 'Z') codes[n++] = (uint8_t)base_code(ch);
+    }
+    return true;
+}
+
+BamPair bam_pair_step(int state, bool qc_fail) {
+    if (qc_fail) {
+        switch (state) { case -3: state = -2; break; case -2: state = 0; break; case -1: state = 2; break; default: state = -3; }
+    } else {
+        switch (state) { case -3: state = -1; break; case -2: state = 1; break; case -1: state = 3; break; default: state = -3; }
+    }
+    if (state == 3) return BamPair{-3, false};                       // a pair of two good mates
+    if (state == 0 || state == 1 || state == 2) return BamPair{-3, true};
+    return BamPair{state, false};                                    // a first mate
+}
+
+static long long stream_bam(const InputFile& in, ReadSink& sink) {
+    BamReader bam(in.path1);
     const int max_len = std::max(in.max_read_len, 1);
     constexpr int BAM_HOLD = 256;
     const size_t row = (size_t)max_len + 8;
-    std::vector<uint8_t> codes(row), held(row * BAM_HOLD), rec;
+    std::vector<uint8_t> codes(row), held(row * BAM_HOLD);
     int held_len[BAM_HOLD];
     int held_head = 0, held_n = 0;                                   // kept-length reads waiting: ring of rows, oldest at held_head
     long long n_records = 0;
-    static const char nt16[] = "=ACMGRSVTWYHKDBN";
-    for (;;) {
-        int32_t block = 0;
-        if (!need(&block, 4) || block < 32) break;                   // end of file (or a truncated one: samread < 0 ends the file too)
-        rec.resize((size_t)block);
-        if (!need(rec.data(), (size_t)block)) break;
-        const uint32_t l_read_name = rec[8];
-        uint16_t n_cigar, flag;
-        int32_t l_seq;
-        memcpy(&n_cigar, rec.data() + 12, 2); memcpy(&flag, rec.data() + 14, 2); memcpy(&l_seq, rec.data() + 16, 4);
-        const size_t seq_at = 32 + (size_t)l_read_name + 4 * (size_t)n_cigar;
-        if (l_seq < 0 || seq_at + ((size_t)l_seq + 1) / 2 > (size_t)block) break;
-        int type = 0;
-        if (flag & 0x0200) {
-            if (in.asm_flag == 1) continue;                          // not a good read: on to the next record
-            switch (g_bam_pair_state) { case -3: g_bam_pair_state = -2; break; case -2: g_bam_pair_state = 0; break; case -1: g_bam_pair_state = 2; break; default: g_bam_pair_state = -3; }
-        } else {
-            switch (g_bam_pair_state) { case -3: g_bam_pair_state = -1; break; case -2: g_bam_pair_state = 1; break; case -1: g_bam_pair_state = 3; break; default: g_bam_pair_state = -3; }
-        }
-        // the SEQ column: l_seq characters ("*" when there are none), the first max_read_len of them looked at
-        int n = 0;
-        const int look = std::min(l_seq == 0 ? 1 : (int)l_seq, max_len);
-        for (int j = 0; j < look && l_seq > 0; j++) {
-            const char ch = nt16[(rec[seq_at + (size_t)(j >> 1)] >> ((~j & 1) << 2)) & 0xf];
-            if (ch >= 'A' && ch <= 'Z') codes[n++] = (uint8_t)base_code(ch);
-        }
-        if (g_bam_pair_state == 3) g_bam_pair_state = -3;
-        else if (g_bam_pair_state == 0 || g_bam_pair_state == 1 || g_bam_pair_state == 2) { g_bam_pair_state = -3; type = -1; }
+    uint16_t flag = 0;
+    int n = 0;
+    while (bam.next(flag, codes.data(), n, max_len)) {
+        const bool qc_fail = (flag & 0x0200) != 0;
+        if (qc_fail && in.asm_flag == 1) continue;                   // not a good read: on to the next record
+        const BamPair pair = bam_pair_step(g_bam_pair_state, qc_fail);
+        g_bam_pair_state = pair.state;
         if (in.reverse) reverse_complement(codes.data(), n);
-        if (type == -1) {                                            // the pair is taken back (prlHashReads.c:412-426)
+        if (pair.take_back) {                                        // prlHashReads.c:412-426
             n_records--;
             if (held_n > 0) held_n--;                                // the last kept read goes again (read_c--)
             continue;
@@ -905,7 +930,6 @@ static long long stream_bam(const InputFile& in, ReadSink& sink) {
     }
     g_bam_pair_state = -3;                                           // end of file, or a truncated one: readseq1by1.c:584-587
     for (; held_n > 0; held_n--, held_head = (held_head + 1) % BAM_HOLD) sink.on_read(held.data() + row * (size_t)held_head, held_len[held_head]);
-    gzclose(fp);
     return n_records;
 }
 

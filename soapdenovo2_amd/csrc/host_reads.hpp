@@ -1,9 +1,12 @@
-// host_reads.hpp -- library config + read ingestion for the pregraph stage (host side).
+// host_reads.hpp -- library config + read ingestion for the pregraph stage (host side), and what the map stage shares with it: the
+// 2-bit packer and the BAM record reader.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
 #include <vector>
+
+struct gzFile_s;
 
 namespace pg {
 
@@ -58,5 +61,32 @@ int host_threads(int n_threads);
 long long stream_reads(const InputFile& in, ReadSink& sink);
 // the BAM reader's pairing state (the reference's static `state`, readseq1by1.c:44); set = true stores `value` first
 int bam_pair_state(bool set, int value);
+
+// codes (one byte a base, 0..3) -> 2 bits a base, 32 bases a word, first base in the top bits (pg_pack_read's layout): (n + 31) / 32
+// words.  `codes` is readable for 8 bytes past n.  With BMI2 eight bases go through one PEXT.
+void pack_codes(const uint8_t* codes, int n, uint64_t* out);
+
+// One b= file, a record at a time (what read1seqbam makes of samread's record, readseq1by1.c:449-592).  The constructor skips the header
+// and exits the process with the reference's messages when the file cannot be opened or is no BAM file.
+class BamReader {
+public:
+    explicit BamReader(const std::string& path);
+    ~BamReader() { close(); }
+    void close();
+    // one record: false = end of file or a truncated file (samread < 0), and after close().  flag = the record's FLAG; codes[0 .. n) = the
+    // letters among the first max_len characters of its SEQ column, as base codes (base2int)
+    bool next(uint16_t& flag, uint8_t* codes, int& n, int max_len);
+
+private:
+    bool need(void* dst, size_t n);
+    bool skip(size_t n);
+    gzFile_s* gz_ = nullptr;
+    std::vector<uint8_t> rec_;
+};
+
+// read1seqbam's pairing step (readseq1by1.c:470-575): records pair up two by two, and a pair with a QC-fail mate (FLAG 0x200) is taken
+// back when its second mate arrives.  state = -3 before a first mate
+struct BamPair { int state; bool take_back; };
+BamPair bam_pair_step(int state, bool qc_fail);
 
 }  // namespace pg

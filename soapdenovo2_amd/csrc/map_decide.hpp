@@ -68,6 +68,12 @@ PG_HD MapOut map_place(uint64_t h, int best, int K, int counter2, const MapCtgs&
     return o;
 }
 
+// a read's row of hit words in memory, as map_decide's Row
+struct MapRow {
+    const uint64_t* p;
+    PG_HD uint64_t operator()(int j) const { return p[j]; }
+};
+
 // row(j) = hit word of k-mer j, nk = number of k-mers (0 for reads shorter than K + 1)
 template <typename Row>
 PG_HD MapOut map_decide(const Row& row, int nk, int K, int multi, const MapCtgs& ctgs) {

@@ -1,5 +1,5 @@
-// map_host.cpp -- host twin of map_kernels.hip: the same contig k-mer index (map_index.hpp) built by one thread, the same per-read
-// decision (map_decide.hpp) over host threads.  What the CPU tests run, and the device path's yardstick (pg_map_reads, device = -1).
+// map_host.cpp -- host twin of map_kernels.hip: the same contig k-mer index (map_index.hpp) built by one thread, the same lookups
+// (map_stretch) and per-read decision (map_decide.hpp) over host threads.  What the CPU tests run, and the device path's yardstick (pg_map_reads, device = -1).
 #include <string.h>
 
 #include <algorithm>
@@ -8,7 +8,6 @@
 #include <vector>
 
 #include "../../include/soapdenovo2_amd.h"
-#include "extract.hpp"
 #include "host_reads.hpp"
 #include "map_index.hpp"
 
@@ -52,18 +51,6 @@ struct HostIndex {
             }
         }
     }
-    uint64_t find(const Kmer<NW>& ck, bool sm) const {
-        constexpr int SW = map_slot_words<NW>();
-        uint64_t e = map_home<NW>(ck, mask);
-        for (;;) {
-            const uint64_t* sl = tab.data() + e * SW;
-            if (sl[NW + 1] == MAP_EMPTY) return 0;
-            bool eq = true;
-            for (int q = 0; q < NW; q++) eq = eq && sl[q] == ck.w[q];
-            if (eq) return sl[NW + 1] == MAP_DELETED ? 0 : sl[NW] | ((uint64_t)(sm ? 1 : 0) << 32);
-            e = (e + 1) & mask;
-        }
-    }
 };
 
 template <int NW>
@@ -81,23 +68,13 @@ public:
         const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)host_threads(0), (b.n + 1023) / 1024));
         auto body = [&](int t) {
             std::vector<uint64_t> row;
-            const Kmer<NW> filter = kmer_filter<NW>(K_);
             for (uint64_t r = b.n * t / nt; r < b.n * (t + 1) / nt; r++) {
                 const int len = b.len[r];
                 const int nk = len >= K_ + 1 ? len - K_ + 1 : 0;
                 row.assign((size_t)nk, 0);
-                if (nk) {
-                    const uint64_t* rd = b.words + b.off[r];
-                    Kmer<NW> word = read_kmer<NW>(rd, 0, K_, filter), bal = kmer_rc<NW>(word, K_);
-                    for (int j = 0; j < nk; j++) {
-                        if (j) kmer_roll<NW>(word, bal, read_base(rd, j + K_ - 1), K_, filter);
-                        const bool sm = kmer_less<NW>(word, bal);
-                        row[(size_t)j] = idx_.find(sm ? word : bal, sm);
-                    }
-                }
-                const uint64_t* p = row.data();
-                if (rows_out && nk) memcpy(rows_out + b.kmer_off[r], p, (size_t)nk * sizeof(uint64_t));
-                out[r] = map_decide([p](int j) { return p[j]; }, nk, K_, map_multi(len, align_len, K_), ctgs);
+                map_stretch<NW>(b.words + b.off[r], 0, nk, K_, idx_.tab.data(), idx_.mask, row.data(), [](uint64_t, int) {});
+                if (rows_out && nk) memcpy(rows_out + b.kmer_off[r], row.data(), (size_t)nk * sizeof(uint64_t));
+                out[r] = map_decide(MapRow{row.data()}, nk, K_, map_multi(len, align_len, K_), ctgs);
             }
         };
         std::vector<std::thread> th;

@@ -1,5 +1,6 @@
-// map_index.hpp -- the contig k-mer index of the `map` stage and the two engines that map reads with it (device: map_kernels.hip,
-// host twin: map_host.cpp).
+// map_index.hpp -- the contig k-mer index of the `map` stage, its read side (map_find: the probe, map_stretch: roll / canonicalise / probe
+// over a stretch of a read's k-mers, shared by both kernels and the host twin) and the two engines that map reads with it (device:
+// map_kernels.hip, host twin: map_host.cpp).  The build side stays with each engine: a CAS protocol on the device, a serial insert on the host.
 //
 // The reference (prlContig2nodes, prlHashCtg.c:345-467) puts every canonical K-mer of every contig of K + 2 bases or more into its k-mer
 // sets: the first put keeps (contig id, position, twin), a second put of the same key marks it deleted (singleKmer, :131-155), and a deleted
@@ -9,9 +10,11 @@
 //   state: 0 empty, 1 claimed (key being written), 2 one put, 3 two puts or more (deleted)
 #pragma once
 #include <stdint.h>
+#include <time.h>
 #include <memory>
 #include <vector>
 
+#include "extract.hpp"
 #include "kmer.hpp"
 #include "map_decide.hpp"
 
@@ -32,6 +35,39 @@ PG_HD uint64_t map_home(const Kmer<NW>& k, uint64_t mask) {
         h ^= h >> 31;
     }
     return h & mask;
+}
+
+// The read-side probe over a finished table (searchKmer, prlRead2Ctg.c:233-246): the hit word of canonical key ck, 0 when the key is not
+// there or is deleted.  sm = the read's own strand is the canonical one (the hit word's `smaller` bit)
+template <int NW>
+PG_HD uint64_t map_find(const uint64_t* tab, uint64_t mask, const Kmer<NW>& ck, bool sm) {
+    constexpr int SW = map_slot_words<NW>();
+    for (uint64_t e = map_home<NW>(ck, mask);; e = (e + 1) & mask) {
+        const uint64_t* sl = tab + e * SW;
+        const uint64_t s = sl[NW + 1];
+        if (s == MAP_EMPTY) return 0;
+        bool eq = true;
+#pragma unroll
+        for (int i = 0; i < NW; i++) eq = eq && sl[i] == ck.w[i];
+        if (eq) return s == MAP_DELETED ? 0 : sl[NW] | ((uint64_t)(sm ? 1 : 0) << 32);
+    }
+}
+
+// k-mers j0 .. j1 - 1 of the packed read rd (chopKmer4read + searchKmer, prlRead2Ctg.c:153-246): roll, canonicalise, probe; row[j] = the
+// hit word, then on_hit(hit, j).  Nothing is read when the stretch is empty
+template <int NW, typename OnHit>
+PG_HD void map_stretch(const uint64_t* rd, int j0, int j1, int K, const uint64_t* tab, uint64_t mask, uint64_t* row, OnHit on_hit) {
+    if (j0 >= j1) return;
+    const Kmer<NW> filter = kmer_filter<NW>(K);
+    Kmer<NW> word = read_kmer<NW>(rd, j0, K, filter);
+    Kmer<NW> bal = kmer_rc<NW>(word, K);
+    for (int j = j0; j < j1; j++) {
+        if (j > j0) kmer_roll<NW>(word, bal, read_base(rd, j + K - 1), K, filter);
+        const bool sm = kmer_less<NW>(word, bal);
+        const uint64_t hit = map_find<NW>(tab, mask, sm ? word : bal, sm);
+        row[j] = hit;
+        on_hit(hit, j);
+    }
 }
 
 // slots of the table for n k-mers: a power of two, at most half full
@@ -60,6 +96,13 @@ struct MapBatch {
     const uint64_t* kmer_off;             // [n + 1]
     uint64_t n;
 };
+
+// the stage's clock: the engines' copy times and call_map.cpp's report
+inline double now_s() {
+    timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+}
 
 class MapEngine {
 public:

@@ -7,8 +7,9 @@
 //                     loop (no lane waits inside a branch for another lane of its own wavefront).  An equal key moves the state to
 //                     "deleted", so the table is a function of the contigs alone.  The trips a lane spends on one claimed slot are capped
 //                     (MAP_SPIN_CAP): a lane that gives up raises a device flag, and build() fails instead of the card hanging.
-//   map_read_kernel   a lane per read: roll, canonicalise, probe; every k-mer's hit word goes to the read's row of the batch's hit buffer
-//                     (the reference's nodeBuffer), then map_decide (map_decide.hpp) picks the contig from the row.
+//   map_read_kernel   a lane per read: roll, canonicalise, probe (map_stretch, map_index.hpp: the loop both read kernels and the host twin
+//                     run); every k-mer's hit word goes to the read's row of the batch's hit buffer (the reference's nodeBuffer), then
+//                     map_decide (map_decide.hpp) picks the contig from the row.
 //   map_read_wave_kernel  a wavefront per read, for long reads (prlLongRead2Ctg, prlRead2Ctg.c:1080): the lanes share the read's k-mers and the
 //                     decision is linear in them, through a per-wave table in LDS keyed by contig id (count, first hit).  Same rows, same
 //                     out[] as map_read_kernel.
@@ -18,10 +19,10 @@
 #include <stdio.h>
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "../../include/soapdenovo2_amd.h"
 #include "arena.hpp"
-#include "extract.hpp"
 #include "map_index.hpp"
 
 void pg_set_error(const std::string& s);
@@ -104,48 +105,17 @@ __global__ __launch_bounds__(256) void map_index_kernel(const uint64_t* __restri
     }
 }
 
-struct MapRow {
-    const uint64_t* p;
-    __device__ __forceinline__ uint64_t operator()(int j) const { return p[j]; }
-};
-
 template <int NW>
 __global__ __launch_bounds__(256) void map_read_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
                                                        const int32_t* __restrict__ lens, const uint64_t* __restrict__ koff, uint64_t n, int K,
                                                        int align_len, const uint64_t* __restrict__ tab, uint64_t mask, MapCtgs ctgs,
                                                        uint64_t* __restrict__ rows, MapOut* __restrict__ out) {
-    constexpr int SW = map_slot_words<NW>();
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const int len = lens[r];
     const int nk = len >= K + 1 ? len - K + 1 : 0;           // prlRead2Ctg.c:159-162
     uint64_t* row = rows + koff[r];
-    if (nk) {
-        const uint64_t* rd = words + off[r];
-        const Kmer<NW> filter = kmer_filter<NW>(K);
-        Kmer<NW> word = read_kmer<NW>(rd, 0, K, filter);
-        Kmer<NW> bal = kmer_rc<NW>(word, K);
-        for (int j = 0; j < nk; j++) {
-            if (j) kmer_roll<NW>(word, bal, read_base(rd, j + K - 1), K, filter);
-            const bool sm = kmer_less<NW>(word, bal);
-            const Kmer<NW> ck = sm ? word : bal;
-            uint64_t e = map_home<NW>(ck, mask), hit = 0;
-            for (;;) {
-                const uint64_t* sl = tab + e * SW;
-                const uint64_t s = sl[NW + 1];
-                if (s == MAP_EMPTY) break;
-                bool eq = true;
-#pragma unroll
-                for (int i = 0; i < NW; i++) eq = eq && sl[i] == ck.w[i];
-                if (eq) {
-                    if (s != MAP_DELETED) hit = sl[NW] | ((uint64_t)(sm ? 1 : 0) << 32);
-                    break;
-                }
-                e = (e + 1) & mask;
-            }
-            row[j] = hit;
-        }
-    }
+    map_stretch<NW>(words + off[r], 0, nk, K, tab, mask, row, [](uint64_t, int) {});
     out[r] = map_decide(MapRow{row}, nk, K, map_multi(len, align_len, K), ctgs);
 }
 
@@ -241,7 +211,6 @@ __global__ __launch_bounds__(256) void map_read_wave_kernel(const uint64_t* __re
                                                             int K, int align_len, const uint64_t* __restrict__ tab, uint64_t mask,
                                                             MapCtgs ctgs, uint64_t* rows, MapOut* __restrict__ out,
                                                             unsigned long long* __restrict__ stats) {
-    constexpr int SW = map_slot_words<NW>();
     __shared__ MapWaveTable tables[MAP_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t r = (uint64_t)blockIdx.x * MAP_WAVES + wave;
@@ -259,33 +228,9 @@ __global__ __launch_bounds__(256) void map_read_wave_kernel(const uint64_t* __re
     {   // the lookups: a lane rolls through its stretch of the read; every hit goes to the row and to the table
         const int per = (nk + 63) / 64;
         const int j0 = lane * per, j1 = nk < j0 + per ? nk : j0 + per;
-        if (j0 < j1) {
-            const uint64_t* rd = words + off[r];
-            const Kmer<NW> filter = kmer_filter<NW>(K);
-            Kmer<NW> word = read_kmer<NW>(rd, j0, K, filter);
-            Kmer<NW> bal = kmer_rc<NW>(word, K);
-            for (int j = j0; j < j1; j++) {
-                if (j > j0) kmer_roll<NW>(word, bal, read_base(rd, j + K - 1), K, filter);
-                const bool sm = kmer_less<NW>(word, bal);
-                const Kmer<NW> ck = sm ? word : bal;
-                uint64_t e = map_home<NW>(ck, mask), hit = 0;
-                for (;;) {
-                    const uint64_t* sl = tab + e * SW;
-                    const uint64_t s = sl[NW + 1];
-                    if (s == MAP_EMPTY) break;
-                    bool eq = true;
-#pragma unroll
-                    for (int i = 0; i < NW; i++) eq = eq && sl[i] == ck.w[i];
-                    if (eq) {
-                        if (s != MAP_DELETED) hit = sl[NW] | ((uint64_t)(sm ? 1 : 0) << 32);
-                        break;
-                    }
-                    e = (e + 1) & mask;
-                }
-                row[j] = hit;
-                if ((uint32_t)hit) map_wave_put(t, hit, j);
-            }
-        }
+        map_stretch<NW>(words + off[r], j0, j1, K, tab, mask, row, [&t](uint64_t hit, int j) {
+            if ((uint32_t)hit) map_wave_put(t, hit, j);
+        });
     }
     map_wave_sync();
     MapWaveSum s{0, 0, 0ull, 0u, 0u};
@@ -435,8 +380,10 @@ public:
             MAP_HIP(hipMemcpyAsync(d_off.p, c.off.data(), (n_ctg + 1) * 8, hipMemcpyHostToDevice, st_));
             MAP_HIP(hipMemcpyAsync(d_len.p, c.len.data(), n_ctg * 4, hipMemcpyHostToDevice, st_));
             const dim3 grid((unsigned)((n_items + 255) / 256)), block(256);
-            if (nw_ == 2) hipLaunchKernelGGL((map_index_kernel<2>), grid, block, 0, st_, d_w.p, d_off.p, d_len.p, d_id.p, d_ic.p, d_ij.p, n_items, K_, tab_.p, slots_ - 1, flag_.p);
-            else hipLaunchKernelGGL((map_index_kernel<4>), grid, block, 0, st_, d_w.p, d_off.p, d_len.p, d_id.p, d_ic.p, d_ij.p, n_items, K_, tab_.p, slots_ - 1, flag_.p);
+            with_nw([&](auto nw) {
+                hipLaunchKernelGGL((map_index_kernel<decltype(nw)::value>), grid, block, 0, st_, d_w.p, d_off.p, d_len.p, d_id.p, d_ic.p, d_ij.p,
+                                   n_items, K_, tab_.p, slots_ - 1, flag_.p);
+            });
             MAP_HIP(hipGetLastError());
         }
         MAP_HIP(hipEventRecord(e1_, st_));
@@ -470,10 +417,13 @@ public:
         if (wave) MAP_HIP(hipMemsetAsync(stats_.p, 0, 2 * sizeof(unsigned long long), st_));
         MAP_HIP(hipEventRecord(e0_, st_));
         const dim3 grid((unsigned)(wave ? (b.n + MAP_WAVES - 1) / MAP_WAVES : (b.n + 255) / 256)), block(256);
-        if (wave && nw_ == 2) hipLaunchKernelGGL((map_read_wave_kernel<2>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p, stats_.p);
-        else if (wave) hipLaunchKernelGGL((map_read_wave_kernel<4>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p, stats_.p);
-        else if (nw_ == 2) hipLaunchKernelGGL((map_read_kernel<2>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p);
-        else hipLaunchKernelGGL((map_read_kernel<4>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p);
+        with_nw([&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            if (wave) hipLaunchKernelGGL((map_read_wave_kernel<NW>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len,
+                                         tab_.p, slots_ - 1, ctgs_, rows_.p, out_.p, stats_.p);
+            else hipLaunchKernelGGL((map_read_kernel<NW>), grid, block, 0, st_, rwords_.p, roff_.p, rlen_.p, rkoff_.p, b.n, K_, align_len, tab_.p,
+                                    slots_ - 1, ctgs_, rows_.p, out_.p);
+        });
         MAP_HIP(hipGetLastError());
         MAP_HIP(hipEventRecord(e1_, st_));
         MAP_HIP(hipMemcpyAsync(out, out_.p, b.n * sizeof(MapOut), hipMemcpyDeviceToHost, st_));
@@ -491,10 +441,11 @@ public:
     }
 
 private:
-    static double now_s() {
-        timespec t;
-        clock_gettime(CLOCK_MONOTONIC, &t);
-        return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+    // f(std::integral_constant<int, NW>) for the engine's flavour: a kernel's argument list is written once
+    template <typename F>
+    void with_nw(F f) const {
+        if (nw_ == 2) f(std::integral_constant<int, 2>{});
+        else f(std::integral_constant<int, 4>{});
     }
     int dev_, K_, nw_;
     bool ready_ = false;

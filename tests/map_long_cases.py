@@ -11,6 +11,8 @@ import os
 
 import numpy as np
 
+from soapdenovo2_amd import synth
+
 import map_cases as M
 import map_edge_cases as E
 import map_model as MM
@@ -262,6 +264,7 @@ CASES = {
     "l31_k25_p8_f":  (False, 31, 25, 8, True, "pairs", "two"),
     "l31_batches":   (False, 31, 0, 3, True, "pairs", "batches"),
     "m127_k75_p3_f": (True, 75, 0, 3, True, "pairs", "nocut"),
+    "l31_bam_p3_f":  (False, 31, 0, 3, True, "pairs", "bam"),
 }
 P_PAIR = ("l31_p1", "l31_p3_f")                             # the same inputs at two -p values: .longReadInGap must differ
 
@@ -337,6 +340,14 @@ def write_long_libs(d, cfg, layout):
         write_fasta(p("long.fa"), long_reads(260, 300, 2400, 48), width=80)
         head = "max_rd_len=2000\n"
         libs = [libs[0], "[LIB]\nasm_flags=4\nmap_len=90\nf=%s\n" % p("long.fa"), libs[1]]
+    elif layout == "bam":
+        # a b= file in the long pass: 13 records pair up two by two, the pair of records 4 and 5 has a QC-fail mate and is taken back
+        # (prlRead2Ctg.c:1184-1196), and the odd count leaves the file ending on a first mate.  The f= file comes after it
+        recs = [(b"b%d" % i, 0x200 if i == 5 else 0, _text(s)) for i, s in enumerate(long_reads(13, 200, 1500, 49))]
+        synth.write_bam(p("long.bam"), recs)
+        write_fasta(p("long.fa"), long_reads(301, 200, 1500, 41), width=70)
+        # (a library with a b= file must give avg_ins: the reference's config check)
+        libs.append("[LIB]\navg_ins=400\nasm_flags=4\nrd_len_cutoff=1000\nmap_len=40\nb=%s\nf=%s\n" % (p("long.bam"), p("long.fa")))
     else:
         raise ValueError(layout)
     with open(cfg, "w") as f:
