@@ -569,6 +569,43 @@ int pg_map_wave_ids(int mer127);
  * Both are 0 after a host-twin call. */
 void pg_map_long_last_stats(uint64_t out[2]);
 
+/* pg_map_reads with the contig k-mer index cut over n_devices ranks by key (csrc/map_index.hpp: map_owner; csrc/map_kernels.hip:
+ * ShardedDeviceMapEngine), for a contig set whose one table does not fit a GPU: rank i runs on GPU devices[i] with a stream of its own,
+ * rank 0 is the lead that merges the ranks' hit rows and decides.  An ordinal may repeat (several ranks on one GPU, as in pregraph's
+ * device list); n_devices = 1 is one rank through the same path.  Every entry -1: the host twin of the cut, n_devices serial tables
+ * (no GPU).  Mixed lists are PG_EINVAL.  Same answers as pg_map_reads, whatever the list. */
+int pg_map_reads_sharded(const int *devices, int n_devices, int K, int mer127, const uint64_t *ctg_words, const uint64_t *ctg_off,
+                         const int32_t *ctg_len_bases, const uint32_t *ctg_ids, uint64_t n_ctg, const int32_t *id_len, const int8_t *id_bal,
+                         uint32_t n_ids, const uint64_t *read_words, const uint64_t *read_off, const int32_t *read_len, uint64_t n_reads,
+                         int align_len, uint32_t *out_ctg, int32_t *out_pos, uint8_t *out_orien, uint8_t *out_footprint);
+/* pg_map_hits over a device list as above: rows = the lead's hit buffer after the merge, the same words as pg_map_hits'. */
+int pg_map_hits_sharded(const int *devices, int n_devices, int K, int mer127, const uint64_t *ctg_words, const uint64_t *ctg_off,
+                        const int32_t *ctg_len_bases, const uint32_t *ctg_ids, uint64_t n_ctg, const int32_t *id_len, const int8_t *id_bal,
+                        uint32_t n_ids, const uint64_t *read_words, const uint64_t *read_off, const int32_t *read_len, uint64_t n_reads,
+                        int align_len, uint32_t *out_ctg, int32_t *out_pos, uint8_t *out_orien, uint8_t *out_footprint, uint64_t *rows,
+                        uint64_t *kmer_off);
+/* pg_map_long_reads over a device list as above: the lookups a wavefront a read on every rank, the decision by the wave-per-read
+ * kernel's decision half from the merged rows (map_decide_rows_wave_kernel).  rows and kmer_off may each be null;
+ * pg_map_long_last_stats speaks of this call too. */
+int pg_map_long_reads_sharded(const int *devices, int n_devices, int K, int mer127, const uint64_t *ctg_words, const uint64_t *ctg_off,
+                              const int32_t *ctg_len_bases, const uint32_t *ctg_ids, uint64_t n_ctg, const int32_t *id_len,
+                              const int8_t *id_bal, uint32_t n_ids, const uint64_t *read_words, const uint64_t *read_off,
+                              const int32_t *read_len, uint64_t n_reads, int align_len, uint32_t *out_ctg, int32_t *out_pos,
+                              uint8_t *out_orien, uint8_t *out_footprint, uint64_t *rows, uint64_t *kmer_off);
+/* The rank that owns each of n packed canonical keys when the index is cut over n_ranks (map_owner), for tests.  keys = n x
+ * (mer127 ? 4 : 2) words as the index stores them: the k-mer as one right-aligned integer of 2 bits a base, most significant word first. */
+int pg_host_map_owner(const uint64_t *keys, uint64_t n, int mer127, int n_ranks, uint32_t *out);
+/* The device memory one rank of the `map` stage takes, from the sizing rules the engines allocate by (csrc/map_plan.cpp); no GPU is
+ * touched.  `map` asks it before anything is allocated whether the index fits the first GPU, and over how many ranks it must be cut
+ * when it does not.
+ *   n_ctg_kmers   k-mers of the contigs of K + 2 bases or more;  batch_kmers  k-mers of the largest batch of reads (the reference's
+ *   batches hold at most 1e8);  n_ranks  1 = one table (the single-device engine), more = an even share a rank and a sixteenth of
+ *   slack (a run counts its keys and allocates exactly);  device_bytes  a GPU's free memory
+ * out[12] (bytes unless said): 0 the rank's table, 1 its slots, 2 the keys it is made for, 3 row buffer, 4 the lead's staging buffer,
+ * 5 read buffers, 6 the contigs while the table is built, 7 peak, 8 budget (0.85 x device_bytes, the partition engine's rule), 9 fits
+ * (peak <= budget), 10 the whole index as one table, 11 the fewest ranks whose plan fits (0: none).  PG_OK or PG_EINVAL. */
+int pg_host_map_plan(uint64_t n_ctg_kmers, int mer127, int n_ranks, uint64_t batch_kmers, uint64_t device_bytes, uint64_t out[12]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,10 @@ contigs from pregraph + the reference's `contig`, then `SOAPdenovo-63mer|127mer 
     # on the GPU box: this build's pregraph (byte-identical to the reference's) + the reference's contig, then this build's map, timed
     python scripts/map_cli_check.py --expect profiles/map_ref_10M_K31.json --out /tmp/map10
 
+    # the index cut over three ranks of the one GPU against one table: map alternately both ways, three times each, on the same prefix
+    python scripts/map_cli_check.py --expect profiles/map_ref_10M_K31.json --out /tmp/map10 --sharded-ranks 3 --repeat 3 \
+        --save-ab profiles/map_sharded_one_gpu.json
+
 Defaults are BASELINE configs[1]: 10 M x 100 bp, K = 31, an E. coli-sized genome.  q1 = the first half of the reads (seed), q2 = the second
 half (seed + 1): map reads only paired libraries (nextValidIndex with pairs = 1), and two files of independent reads are such a library.
 Exit code 1 when the md5s differ or a command fails."""
@@ -56,6 +60,9 @@ def main():
     ap.add_argument("--save", default="")
     ap.add_argument("--expect", default="", help="JSON written by --reference --save for the same arguments")
     ap.add_argument("--threads", type=int, default=16, help="threads of the FASTQ generator")
+    ap.add_argument("--sharded-ranks", type=int, default=0, help="after the first map: map again, alternately on one table and with the index cut over this many ranks of GPU 0")
+    ap.add_argument("--repeat", type=int, default=3, help="runs of each form with --sharded-ranks")
+    ap.add_argument("--save-ab", default="", help="where the alternating runs' times go")
     a = ap.parse_args()
     key = {k: getattr(a, k) for k in ("reads", "read_len", "genome", "err", "seed", "kmer", "p", "fill")}
     want = None
@@ -91,6 +98,22 @@ def main():
     if want is not None:
         res["identical_to_reference"] = res["md5"] == want
         ok = res["identical_to_reference"]
+    if a.sharded_ranks and not a.reference:
+        forms = {"one_table": {}, "sharded": {"SOAPDENOVO2_AMD_DEVICES": ",".join(["0"] * a.sharded_ranks), "SOAPDENOVO2_AMD_MAP_SHARD": "1"}}
+        ab = {"workload": key, "ranks_on_gpu_0": a.sharded_ranks, "runs": []}
+        for i in range(a.repeat):
+            for form, extra in forms.items():
+                for ext in OUTS:
+                    if os.path.exists(f"{pre}.{ext}"):
+                        os.remove(f"{pre}.{ext}")
+                secs, err = timed(cmd, dict(env, **extra), os.path.join(out, f"map_stderr_{form}_{i}.txt"))
+                same = md5s(pre) == want
+                ok = ok and same
+                ab["runs"].append({"form": form, "run": i, "map_s": secs, "identical_to_reference": same,
+                                   "map_log": [l for l in err.splitlines() if l.startswith(("[map]", "Time spent"))]})
+        res["sharded_ab"] = ab
+        if a.save_ab:
+            json.dump(dict(ab, made_by="scripts/map_cli_check.py --sharded-ranks"), open(a.save_ab, "w"), indent=1)
     for f in os.listdir(out):
         if f.startswith("r_") or f.startswith("g."):
             os.remove(os.path.join(out, f))

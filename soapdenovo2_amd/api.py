@@ -65,6 +65,11 @@ def lib() -> C.CDLL:
                                u64p, u64p, u64p, C.c_uint64, C.c_int, u64p, u64p, u64p, u64p]
     L.pg_map_hits.argtypes = list(L.pg_map_reads.argtypes) + [u64p, u64p]
     L.pg_map_long_reads.argtypes = list(L.pg_map_hits.argtypes)
+    L.pg_map_reads_sharded.argtypes = [u64p, C.c_int] + list(L.pg_map_reads.argtypes)[1:]
+    L.pg_map_hits_sharded.argtypes = [u64p, C.c_int] + list(L.pg_map_hits.argtypes)[1:]
+    L.pg_map_long_reads_sharded.argtypes = list(L.pg_map_hits_sharded.argtypes)
+    L.pg_host_map_owner.argtypes = [u64p, C.c_uint64, C.c_int, C.c_int, u64p]
+    L.pg_host_map_plan.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, u64p]
     L.pg_map_wave_ids.argtypes = [C.c_int]
     L.pg_map_long_last_stats.argtypes = [u64p]
     L.pg_map_long_last_stats.restype = None
@@ -178,6 +183,7 @@ EXPORTED_SYMBOLS = [
     "pg_host_emu_layout_static", "pg_graph_begin_device", "pg_host_emu_clip_tips", "pg_exchange_regroup_by_set", "pg_comm_regroup_stats", "pg_graph_begin_sharded", "pg_host_regroup_plan", "pg_host_bam_pair_state", "pg_device_scratch_offer", "pg_device_scratch_withdraw", "pg_host_emu_layout_growable", "pg_exchange_regroup_by_set_ws", "pg_host_edge_file_in_background", "pg_graph_add_packed_device", "pg_host_emu_home_slots", "pg_comm_pipeline_stats", "pg_comm_create_host", "pg_comm_flush",
     "pg_set_read_len_bound", "pg_graph_add_packed_device_ragged", "pg_expect", "pg_host_plan_memory", "pg_create_planned", "pg_graph_add_packed_device_segments",
     "call_align", "call_align_127mer", "pg_map_reads", "pg_map_hits", "pg_map_long_reads", "pg_map_wave_ids", "pg_map_long_last_stats",
+    "pg_map_reads_sharded", "pg_map_hits_sharded", "pg_map_long_reads_sharded", "pg_host_map_owner", "pg_host_map_plan",
 ]
 
 
@@ -244,10 +250,20 @@ def _pack_many(seqs):
     return words, off, lens
 
 
-def map_reads(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, mer127: bool = False, device: int = 0):
+def _map_call(name: str, device, *args):
+    """pg_<name>(device, ...) for an int, pg_<name>_sharded(devices, n, ...) for a sequence of device ordinals (one rank each)."""
+    if isinstance(device, (int, np.integer)):
+        _check(getattr(lib(), "pg_" + name)(int(device), *args), "pg_" + name)
+        return
+    devs = np.ascontiguousarray(list(device), dtype=np.int32)
+    _check(getattr(lib(), "pg_" + name + "_sharded")(devs.ctypes.data, len(devs), *args), "pg_" + name + "_sharded")
+
+
+def map_reads(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, mer127: bool = False, device=0):
     """The `map` stage's index + read kernel on one batch (pg_map_reads): contigs (base-code arrays, each of K + 2 bases or more) with
-    their ids, the length / bal_edge of every contig id, reads (base-code arrays).  device = -1 runs the host twin.  Returns
-    (ctg, pos, orien, footprint) arrays, one entry a read."""
+    their ids, the length / bal_edge of every contig id, reads (base-code arrays).  device = -1 runs the host twin.  A sequence of
+    ordinals for `device` cuts the index over that many ranks, one a GPU named (pg_map_reads_sharded; an ordinal may repeat, all -1:
+    the host twin of the cut).  Returns (ctg, pos, orien, footprint) arrays, one entry a read."""
     cw, co, cl = _pack_many(contigs)
     rw, ro, rl = _pack_many(reads)
     ids = np.ascontiguousarray(ctg_ids, dtype=np.uint32)
@@ -256,14 +272,15 @@ def map_reads(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, m
     n = len(reads)
     ctg = np.zeros(n, np.uint32); pos = np.zeros(n, np.int32); ori = np.zeros(n, np.uint8); fp = np.zeros(n, np.uint8)
     p = lambda a: a.ctypes.data
-    _check(lib().pg_map_reads(device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
-                              p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp)), "pg_map_reads")
+    _map_call("map_reads", device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
+              p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp))
     return ctg, pos, ori, fp
 
 
-def map_hits(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, mer127: bool = False, device: int = 0):
+def map_hits(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, mer127: bool = False, device=0):
     """map_reads that also returns the hit word of every k-mer (pg_map_hits): (ctg, pos, orien, footprint, rows, kmer_off); read r's hit
-    words are rows[kmer_off[r]:kmer_off[r + 1]] (csrc/map_decide.hpp gives their layout; 0 = absent or deleted key)."""
+    words are rows[kmer_off[r]:kmer_off[r + 1]] (csrc/map_decide.hpp gives their layout; 0 = absent or deleted key).  `device` as for
+    map_reads (a sequence: pg_map_hits_sharded)."""
     cw, co, cl = _pack_many(contigs)
     rw, ro, rl = _pack_many(reads)
     ids = np.ascontiguousarray(ctg_ids, dtype=np.uint32)
@@ -275,15 +292,16 @@ def map_hits(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, me
     rows = np.full(n_k + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)         # (every word must be written: 0 is an answer)
     koff = np.zeros(n + 1, np.uint64)
     p = lambda a: a.ctypes.data
-    _check(lib().pg_map_hits(device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
-                             p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp), p(rows), p(koff)), "pg_map_hits")
+    _map_call("map_hits", device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
+              p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp), p(rows), p(koff))
     return ctg, pos, ori, fp, rows[:n_k], koff
 
 
-def map_long_reads(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, mer127: bool = False, device: int = 0,
+def map_long_reads(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: int, mer127: bool = False, device=0,
                    want_hits: bool = False):
     """One batch of the long-read pass (pg_map_long_reads): the wave-per-read kernel on `device`, the host twin with device = -1.
-    Arguments as map_reads; returns what map_reads returns, or what map_hits returns with want_hits=True."""
+    Arguments as map_reads (a sequence for `device`: pg_map_long_reads_sharded); returns what map_reads returns, or what map_hits
+    returns with want_hits=True."""
     cw, co, cl = _pack_many(contigs)
     rw, ro, rl = _pack_many(reads)
     ids = np.ascontiguousarray(ctg_ids, dtype=np.uint32)
@@ -295,8 +313,8 @@ def map_long_reads(contigs, ctg_ids, id_len, id_bal, reads, K: int, align_len: i
     rows = np.full(n_k + 1, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64) if want_hits else None
     koff = np.zeros(n + 1, np.uint64) if want_hits else None
     p = lambda a: a.ctypes.data if a is not None else None
-    _check(lib().pg_map_long_reads(device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
-                                   p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp), p(rows), p(koff)), "pg_map_long_reads")
+    _map_call("map_long_reads", device, K, 1 if mer127 else 0, p(cw), p(co), p(cl), p(ids), len(contigs), p(il), p(ib), len(il),
+              p(rw), p(ro), p(rl), n, align_len, p(ctg), p(pos), p(ori), p(fp), p(rows), p(koff))
     return (ctg, pos, ori, fp, rows[:n_k], koff) if want_hits else (ctg, pos, ori, fp)
 
 
@@ -306,6 +324,27 @@ def map_long_last_stats():
     out = np.zeros(2, dtype=np.uint64)
     lib().pg_map_long_last_stats(out.ctypes.data)
     return int(out[0]), int(out[1])
+
+
+MAP_PLAN_FIELDS = ["table", "slots", "keys", "rows", "staging", "reads", "build", "peak", "budget", "fits", "one_table", "fewest_ranks"]
+
+
+def map_plan(n_ctg_kmers: int, mer127: bool = False, n_ranks: int = 1, batch_kmers: int = 10**8, device_bytes: int = 288 * 10**9) -> dict:
+    """pg_host_map_plan: the device memory one rank of `map` takes with the index cut over n_ranks (1: one table), whether that fits
+    the budget, and the fewest ranks that would (no GPU)."""
+    out = np.zeros(12, dtype=np.uint64)
+    _check(lib().pg_host_map_plan(n_ctg_kmers, 1 if mer127 else 0, n_ranks, batch_kmers, device_bytes, out.ctypes.data), "pg_host_map_plan")
+    d = {k: int(v) for k, v in zip(MAP_PLAN_FIELDS, out)}
+    d["fits"] = bool(d["fits"])
+    return d
+
+
+def map_owner(keys: np.ndarray, n_ranks: int, mer127: bool = False) -> np.ndarray:
+    """pg_host_map_owner: the rank of n_ranks that owns each packed canonical key; keys = [n, 4 if mer127 else 2] uint64."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 4 if mer127 else 2)
+    out = np.zeros(len(keys), dtype=np.uint32)
+    _check(lib().pg_host_map_owner(keys.ctypes.data, len(keys), 1 if mer127 else 0, n_ranks, out.ctypes.data), "pg_host_map_owner")
+    return out
 
 
 def map_wave_ids(mer127: bool = False) -> int:

@@ -22,9 +22,12 @@
 // Both passes are one loop (run_pass: batches, the BAM take-back, pack_batch, the engine, the timers); a pass brings what it does when
 // the library changes (on_read) and its recorder (Recorder, LongRecorder; both write through RcSeq1, the model of rcSeq[1]).  The 2-bit
 // packer and the BAM record reader are host_reads.cpp's.
-// Not here: without that switch a config with a long-read library (asm_flags=4) is refused before anything is written; one GPU (the
-// first of SOAPDENOVO2_AMD_DEVICES).  SOAPDENOVO2_AMD_MAP_HOST=1 runs the host twin of the index and the read kernels instead (the CPU
-// tests).
+//   6. the index lives on the first GPU of SOAPDENOVO2_AMD_DEVICES unless it is cut over all the ranks of that list by key (map_owner,
+//      map_index.hpp; ShardedDeviceMapEngine, map_kernels.hip): with SOAPDENOVO2_AMD_MAP_SHARD=1 and two ranks or more listed, or when
+//      the plan (pg_host_map_plan, map_plan.cpp) says that the table does not fit the first GPU and more ranks are listed.  The plan is
+//      asked once the contigs are counted and before anything is allocated or written; an index that fits nowhere ends the command there
+// Not here: without that switch a config with a long-read library (asm_flags=4) is refused before anything is written.
+// SOAPDENOVO2_AMD_MAP_HOST=1 runs the host twin of the index and the read kernels instead (the CPU tests), cut the same way.
 #include <getopt.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -40,6 +43,7 @@
 #include <vector>
 
 #include "../../include/soapdenovo2_amd.h"
+#include "device_list.hpp"
 #include "env.hpp"
 #include "host_reads.hpp"
 #include "map_index.hpp"
@@ -798,15 +802,52 @@ int run_map(int argc, char** argv, bool mer127) {
     std::vector<int8_t> cbal;
     fprintf(stderr, "\n%lld contig(s) read, %zu of %d bases or more.\n", num_seq, contigs.len.size(), K + 2);
     const int nw = mer127 ? 4 : 2;
-    std::unique_ptr<MapEngine> eng;
-    if (env_on(env_user("SOAPDENOVO2_AMD_MAP_HOST"))) eng = map_engine_host(K, nw);
-    else {
-        int device = 0;
-        if (const char* e = env_user("SOAPDENOVO2_AMD_DEVICE")) device = atoi(e);
-        if (const char* e = env_user("SOAPDENOVO2_AMD_DEVICES")) if (*e) device = atoi(e);      // the first of the list
-        eng = map_engine_device(device, K, nw);
-        if (!eng) { fprintf(stderr, "map: %s\n", pg_last_error()); return 1; }
+    // 6. where the index goes: one table on the first device, or cut over the listed ranks
+    const bool host = env_on(env_user("SOAPDENOVO2_AMD_MAP_HOST"));
+    const std::vector<int> devices = parse_device_list(env_user("SOAPDENOVO2_AMD_DEVICES"));
+    int device = 0;
+    if (const char* e = env_user("SOAPDENOVO2_AMD_DEVICE")) device = atoi(e);
+    if (!devices.empty()) device = devices[0];
+    const int n_listed = (int)devices.size();
+    bool sharded = env_on(env_user("SOAPDENOVO2_AMD_MAP_SHARD")) && n_listed >= 2;
+    // the test hook SOAPDENOVO2_AMD_MAP_BUDGET_MB: the most a rank's table may take, so that the does-not-fit paths run at test sizes
+    // (where the batch buffers outweigh any index); with it the host twin is planned too, against no device
+    const char* hook = env_test("SOAPDENOVO2_AMD_MAP_BUDGET_MB");
+    if (!host || hook) {
+        uint64_t device_bytes = ~0ull >> 2, plan[12];
+        if (!host && map_device_free_bytes(device, &device_bytes) != PG_OK) { fprintf(stderr, "map: %s\n", pg_last_error()); return 1; }
+        const uint64_t table_cap = hook ? (uint64_t)atoll(hook) << 20 : ~0ull;
+        auto fits = [&](int n) {                                      // a batch holds at most 1e8 k-mers (prlRead2Ctg.c:814)
+            pg_host_map_plan(contigs.n_kmers, mer127 ? 1 : 0, n, 100000000ull, device_bytes, plan);
+            return plan[9] != 0 && plan[0] <= table_cap;
+        };
+        if (!sharded && !fits(1) && n_listed >= 2) sharded = true;
+        if (sharded && n_listed > DEVICE_LIST_MAX_RANKS) {           // (a longer list is no matter to a run on the first device)
+            fprintf(stderr, "map: SOAPDENOVO2_AMD_DEVICES names %d ranks, the most an index is cut over is %d.\n", n_listed, DEVICE_LIST_MAX_RANKS);
+            return 1;
+        }
+        const int n_ranks = sharded ? n_listed : 1;
+        if (!fits(n_ranks)) {
+            const uint64_t table = plan[0], peak = plan[7], budget = plan[8], whole = plan[10];
+            int fewest = (int)plan[11];                               // the plan's own answer; under the hook's cap, the same search with it
+            if (hook) {
+                fewest = 0;
+                for (int n = 1; n <= DEVICE_LIST_MAX_RANKS && !fewest; n++) if (fits(n)) fewest = n;
+            }
+            fprintf(stderr, "map: the contig index does not fit: %llu k-mers are %llu bytes as one table; over %d rank(s) a rank's table is %llu bytes "
+                            "(%llu with its buffers) and the budget of a device is %llu bytes",
+                    (unsigned long long)contigs.n_kmers, (unsigned long long)whole, n_ranks, (unsigned long long)table, (unsigned long long)peak,
+                    (unsigned long long)budget);
+            if (hook) fprintf(stderr, "; SOAPDENOVO2_AMD_MAP_BUDGET_MB caps a rank's table at %llu bytes", (unsigned long long)table_cap);
+            if (fewest) fprintf(stderr, ".  %d ranks would hold it: list them in SOAPDENOVO2_AMD_DEVICES.  Nothing was written.\n", fewest);
+            else fprintf(stderr, ".  No number of ranks up to %d holds it.  Nothing was written.\n", DEVICE_LIST_MAX_RANKS);
+            return 1;
+        }
     }
+    std::unique_ptr<MapEngine> eng;
+    if (host) eng = sharded ? map_engine_host_sharded(n_listed, K, nw) : map_engine_host(K, nw);
+    else eng = sharded ? map_engine_device_sharded(devices.data(), n_listed, K, nw) : map_engine_device(device, K, nw);
+    if (!eng) { fprintf(stderr, "map: %s\n", pg_last_error()); return 1; }
     const double t1 = now_s();
     const int max_all = cfg.max_rd_len ? cfg.max_rd_len : 100;                  // prlRead2Ctg.c:796-799: maxReadLen
     fprintf(stderr, "In file: %s, max seq len %d, max name len %d\n", o.cfg.c_str(), max_all, 256);
@@ -884,6 +925,18 @@ int run_map(int argc, char** argv, bool mer127) {
                         "record %.3fs, files %.3fs (deflate waits %.3fs); whole stage %.3fs\n",
                 t1 - t0, t2 - t1, eng->t_index, tm.parse, tm.pack, tm.map, eng->t_kernel, eng->t_copy, tm.record, t4 - t3,
                 on_ctg.t_deflate + in_gap.t_deflate, t4 - t_start);
+    if (env_user("PG_HOST_VERBOSE") && !eng->ranks.empty()) {
+        std::string keys, load, probe;
+        char t[64];
+        for (const MapEngine::Rank& r : eng->ranks) {
+            const char* sep = keys.empty() ? "" : " / ";
+            keys += sep + std::to_string(r.keys);
+            snprintf(t, sizeof t, "%s%.3f", sep, (double)r.keys / (double)r.slots); load += t;
+            snprintf(t, sizeof t, "%s%.6f", sep, r.t_probe); probe += t;
+        }
+        fprintf(stderr, "[map] index sharded over %zu ranks: keys %s, load %s; probe %s s, merge %.6fs, decide %.6fs\n", eng->ranks.size(),
+                keys.c_str(), load.c_str(), probe.c_str(), eng->t_merge, eng->t_decide);
+    }
     fprintf(stderr, "Overall time spent on alignment: %dm.\n\n", (int)(t4 - t_start) / 60);
     return 0;
 }

@@ -28,6 +28,7 @@
 #include "host_graph.hpp"
 #include "arena.hpp"
 #include "cmd_plan.hpp"
+#include "device_list.hpp"
 #include "env.hpp"
 #include "host_reads.hpp"
 #include "../../include/soapdenovo2_amd.h"
@@ -647,18 +648,8 @@ int run(int argc, char** argv, bool mer127) {
     // several ranks on one GPU -- how the N-rank path is tested on a 1-GPU box); everything after pass 1 runs on the first.
     int device = 0;
     if (const char* e = pg::env_user("SOAPDENOVO2_AMD_DEVICE")) device = atoi(e);
-    std::vector<int> devices;
-    if (const char* e = pg::env_user("SOAPDENOVO2_AMD_DEVICES")) {
-        for (const char* q = e; *q;) {
-            char* end = nullptr;
-            const long v = strtol(q, &end, 10);
-            if (end == q) break;
-            devices.push_back((int)v);
-            q = *end == ',' ? end + 1 : end;
-            if (end == q && *q) break;
-        }
-        if (!devices.empty()) device = devices[0];
-    }
+    const std::vector<int> devices = pg::parse_device_list(pg::env_user("SOAPDENOVO2_AMD_DEVICES"));
+    if (!devices.empty()) device = devices[0];
     const int n_ranks = devices.size() > 1 ? (int)devices.size() : 1;
     // After pass 1 a reference k-mer set lives whole on one GPU (set s on rank s mod N: the layout and the scans are per set), so
     // -p is also the number of GPUs the graph stages can use: with fewer sets than ranks the other ranks only help in pass 1 and pass 2's threading.

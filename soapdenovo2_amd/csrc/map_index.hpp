@@ -14,6 +14,7 @@
 #include <memory>
 #include <vector>
 
+#include "device_list.hpp"
 #include "extract.hpp"
 #include "kmer.hpp"
 #include "map_decide.hpp"
@@ -23,9 +24,9 @@ namespace pg {
 template <int NW> PG_HD constexpr int map_slot_words() { return NW + 2; }
 constexpr uint64_t MAP_EMPTY = 0, MAP_CLAIMED = 1, MAP_ONCE = 2, MAP_DELETED = 3;
 
-// home slot of a canonical key (splitmix64's finaliser over the words)
+// 64-bit hash of a canonical key (splitmix64's finaliser over the words)
 template <int NW>
-PG_HD uint64_t map_home(const Kmer<NW>& k, uint64_t mask) {
+PG_HD uint64_t map_hash(const Kmer<NW>& k) {
     uint64_t h = 0x9E3779B97F4A7C15ULL;
 #pragma unroll
     for (int i = 0; i < NW; i++) {
@@ -34,8 +35,20 @@ PG_HD uint64_t map_home(const Kmer<NW>& k, uint64_t mask) {
         h ^= h >> 27; h *= 0x94D049BB133111EBULL;
         h ^= h >> 31;
     }
-    return h & mask;
+    return h;
 }
+
+// home slot of a canonical key
+template <int NW>
+PG_HD uint64_t map_home(const Kmer<NW>& k, uint64_t mask) { return map_hash<NW>(k) & mask; }
+
+// The rank that holds a key when the index is cut over n ranks (ShardedDeviceMapEngine, the sharded host twin): the hash's bits 40 and
+// up, which no slot index of a table that fits a card reaches (2^40 slots are 32 TB), so a rank's keys spread over its own table as the
+// whole set does over one.  n need not be a power of two.  Every put of a key reaches the same rank, so "the first put keeps, a second
+// put deletes" holds inside a rank's table
+constexpr int MAP_OWNER_SHIFT = 40;
+template <int NW>
+PG_HD uint32_t map_owner(const Kmer<NW>& k, uint32_t n) { return (uint32_t)((map_hash<NW>(k) >> MAP_OWNER_SHIFT) % n); }
 
 // The read-side probe over a finished table (searchKmer, prlRead2Ctg.c:233-246): the hit word of canonical key ck, 0 when the key is not
 // there or is deleted.  sm = the read's own strand is the canonical one (the hit word's `smaller` bit)
@@ -53,10 +66,11 @@ PG_HD uint64_t map_find(const uint64_t* tab, uint64_t mask, const Kmer<NW>& ck, 
     }
 }
 
-// k-mers j0 .. j1 - 1 of the packed read rd (chopKmer4read + searchKmer, prlRead2Ctg.c:153-246): roll, canonicalise, probe; row[j] = the
-// hit word, then on_hit(hit, j).  Nothing is read when the stretch is empty
-template <int NW, typename OnHit>
-PG_HD void map_stretch(const uint64_t* rd, int j0, int j1, int K, const uint64_t* tab, uint64_t mask, uint64_t* row, OnHit on_hit) {
+// k-mers j0 .. j1 - 1 of the packed read rd (chopKmer4read + searchKmer, prlRead2Ctg.c:153-246): roll, canonicalise, and for the keys
+// that own(key) takes, probe; row[j] = the hit word, then on_hit(hit, j).  A key that is not taken leaves row[j] as it is.  Nothing is
+// read when the stretch is empty
+template <int NW, typename Own, typename OnHit>
+PG_HD void map_stretch_if(const uint64_t* rd, int j0, int j1, int K, const uint64_t* tab, uint64_t mask, uint64_t* row, Own own, OnHit on_hit) {
     if (j0 >= j1) return;
     const Kmer<NW> filter = kmer_filter<NW>(K);
     Kmer<NW> word = read_kmer<NW>(rd, j0, K, filter);
@@ -64,10 +78,18 @@ PG_HD void map_stretch(const uint64_t* rd, int j0, int j1, int K, const uint64_t
     for (int j = j0; j < j1; j++) {
         if (j > j0) kmer_roll<NW>(word, bal, read_base(rd, j + K - 1), K, filter);
         const bool sm = kmer_less<NW>(word, bal);
-        const uint64_t hit = map_find<NW>(tab, mask, sm ? word : bal, sm);
+        const Kmer<NW>& ck = sm ? word : bal;
+        if (!own(ck)) continue;
+        const uint64_t hit = map_find<NW>(tab, mask, ck, sm);
         row[j] = hit;
         on_hit(hit, j);
     }
+}
+
+// the whole index in one table: every key is probed
+template <int NW, typename OnHit>
+PG_HD void map_stretch(const uint64_t* rd, int j0, int j1, int K, const uint64_t* tab, uint64_t mask, uint64_t* row, OnHit on_hit) {
+    map_stretch_if<NW>(rd, j0, j1, K, tab, mask, row, [](const Kmer<NW>&) { return true; }, on_hit);
 }
 
 // slots of the table for n k-mers: a power of two, at most half full
@@ -118,11 +140,22 @@ public:
     double t_index = 0, t_kernel = 0, t_copy = 0;
     // the wave kernel's figures: reads whose ids did not fit its LDS table (done in passes), distinct ids summed over the reads with k-mers
     uint64_t n_passes = 0, n_ids = 0;
+    // an index cut over ranks (map_owner): a rank's keys, the slots of its table and the seconds its probe kernel ran; t_kernel is then the
+    // lead's probe + its wait for the slowest rank's + merge + decide, with t_merge (the rows' copies to the lead and the OR, from the moment every rank's probe is done) and t_decide apart.  Empty: one table
+    struct Rank { uint64_t keys = 0, slots = 0; double t_probe = 0; };
+    std::vector<Rank> ranks;
+    double t_merge = 0, t_decide = 0;
 };
 
 // K and the flavour (nw = 2: the 63-mer build, 4: the 127-mer build)
 std::unique_ptr<MapEngine> map_engine_device(int device, int K, int nw);
 std::unique_ptr<MapEngine> map_engine_host(int K, int nw);
+// the index cut over n ranks (1 to DEVICE_LIST_MAX_RANKS, device_list.hpp) by map_owner: rank i on (devices[i], a stream of its own), rank 0 the lead; an ordinal may repeat.  The
+// host form: n serial tables
+std::unique_ptr<MapEngine> map_engine_device_sharded(const int* devices, int n, int K, int nw);
+std::unique_ptr<MapEngine> map_engine_host_sharded(int n, int K, int nw);
+// free memory of a device as the arena sees it (the plan's device_bytes); PG_OK or PG_ENODEV
+int map_device_free_bytes(int device, uint64_t* free_bytes);
 // distinct contig ids of a read that the wave kernel's LDS table holds (more: the read is done in passes)
 int map_wave_ids();
 

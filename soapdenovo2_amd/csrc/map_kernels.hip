@@ -13,7 +13,12 @@
 //   map_read_wave_kernel  a wavefront per read, for long reads (prlLongRead2Ctg, prlRead2Ctg.c:1080): the lanes share the read's k-mers and the
 //                     decision is linear in them, through a per-wave table in LDS keyed by contig id (count, first hit).  Same rows, same
 //                     out[] as map_read_kernel.
-// All three wait for random 32- / 48-byte slot reads of a table that is many times the L2: the bound is HBM random-access latency and rate,
+//   ShardedDeviceMapEngine  the index cut over ranks by key (map_owner, map_index.hpp) for a contig set whose one table does not fit a
+//                     card: map_count_owned_kernel / map_index_owned_kernel build a rank's table from the keys it owns,
+//                     map_probe_owned_kernel looks a batch's owned keys up into the rank's zeroed rows, map_rows_merge_kernel ORs the
+//                     ranks' rows together on the lead, and map_decide_rows_kernel / map_decide_rows_wave_kernel run the decision
+//                     halves of the two read kernels (map_lane_decide, map_wave_decide) from the finished rows.
+// All of them wait for random 32- / 48-byte slot reads of a table that is many times the L2: the bound is HBM random-access latency and rate,
 // not arithmetic.  Memory comes from the device arena (arena.hpp).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -82,13 +87,12 @@ __device__ __forceinline__ void map_insert(uint64_t* tab, uint64_t mask, const K
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(256) void map_index_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
-                                                        const int32_t* __restrict__ len, const uint32_t* __restrict__ ids,
-                                                        const uint32_t* __restrict__ item_ctg, const uint32_t* __restrict__ item_j0,
-                                                        uint64_t n_items, int K, uint64_t* tab, uint64_t mask, uint32_t* gave_up) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_items) return;
+// work item t of the index build: k-mers j0 .. j0 + MAP_ITEM - 1 of one contig, rolled and canonicalised; put(key, hit word) for each
+template <int NW, typename Put>
+__device__ __forceinline__ void map_index_item(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
+                                               const int32_t* __restrict__ len, const uint32_t* __restrict__ ids,
+                                               const uint32_t* __restrict__ item_ctg, const uint32_t* __restrict__ item_j0, uint64_t t, int K,
+                                               Put put) {
     const uint32_t c = item_ctg[t];
     const int j0 = (int)item_j0[t];
     const int nk = len[c] - K + 1;
@@ -101,8 +105,57 @@ __global__ __launch_bounds__(256) void map_index_kernel(const uint64_t* __restri
     for (int j = j0; j < j1; j++) {
         if (j > j0) kmer_roll<NW>(word, bal, read_base(rd, j + K - 1), K, filter);
         const bool sm = kmer_less<NW>(word, bal);
-        map_insert<NW>(tab, mask, sm ? word : bal, map_hit(id, (uint32_t)j, sm ? 0 : 1, 0), gave_up);   // twin = 0 when the contig's strand is canonical
+        put(sm ? word : bal, map_hit(id, (uint32_t)j, sm ? 0 : 1, 0));                 // twin = 0 when the contig's strand is canonical
     }
+}
+
+template <int NW>
+__global__ __launch_bounds__(256) void map_index_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
+                                                        const int32_t* __restrict__ len, const uint32_t* __restrict__ ids,
+                                                        const uint32_t* __restrict__ item_ctg, const uint32_t* __restrict__ item_j0,
+                                                        uint64_t n_items, int K, uint64_t* tab, uint64_t mask, uint32_t* gave_up) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_items) return;
+    map_index_item<NW>(words, off, len, ids, item_ctg, item_j0, t, K,
+                       [=](const Kmer<NW>& k, uint64_t value) { map_insert<NW>(tab, mask, k, value, gave_up); });
+}
+
+// ---- the index cut over ranks (ShardedDeviceMapEngine): rank `me` of n keeps the keys with map_owner(key, n) == me ----
+// the keys of the work items that rank `me` owns, added to *count: a sum per wavefront, one atomic a wavefront
+template <int NW>
+__global__ __launch_bounds__(256) void map_count_owned_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
+                                                              const int32_t* __restrict__ len, const uint32_t* __restrict__ ids,
+                                                              const uint32_t* __restrict__ item_ctg, const uint32_t* __restrict__ item_j0,
+                                                              uint64_t n_items, int K, uint32_t n, uint32_t me, unsigned long long* count) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned int mine = 0;
+    if (t < n_items)
+        map_index_item<NW>(words, off, len, ids, item_ctg, item_j0, t, K,
+                           [&mine, n, me](const Kmer<NW>& k, uint64_t) { mine += map_owner<NW>(k, n) == me ? 1u : 0u; });
+    for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d);                 // (every lane of the wavefront is here: nobody returned)
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, (unsigned long long)mine);
+}
+
+// map_index_kernel for the keys rank `me` owns; tab is that rank's table
+template <int NW>
+__global__ __launch_bounds__(256) void map_index_owned_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
+                                                              const int32_t* __restrict__ len, const uint32_t* __restrict__ ids,
+                                                              const uint32_t* __restrict__ item_ctg, const uint32_t* __restrict__ item_j0,
+                                                              uint64_t n_items, int K, uint32_t n, uint32_t me, uint64_t* tab, uint64_t mask,
+                                                              uint32_t* gave_up) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_items) return;
+    map_index_item<NW>(words, off, len, ids, item_ctg, item_j0, t, K, [=](const Kmer<NW>& k, uint64_t value) {
+        if (map_owner<NW>(k, n) == me) map_insert<NW>(tab, mask, k, value, gave_up);
+    });
+}
+
+// k-mers of a read (prlRead2Ctg.c:159-162: a read shorter than K + 1 has none)
+__device__ __forceinline__ int map_read_kmers(int len, int K) { return len >= K + 1 ? len - K + 1 : 0; }
+
+// the lane-per-read decision from a finished row (parse1read): the half of map_read_kernel behind its lookups, and all of map_decide_rows_kernel
+__device__ __forceinline__ MapOut map_lane_decide(const uint64_t* row, int len, int nk, int K, int align_len, const MapCtgs& ctgs) {
+    return map_decide(MapRow{row}, nk, K, map_multi(len, align_len, K), ctgs);
 }
 
 template <int NW>
@@ -113,10 +166,50 @@ __global__ __launch_bounds__(256) void map_read_kernel(const uint64_t* __restric
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     const int len = lens[r];
-    const int nk = len >= K + 1 ? len - K + 1 : 0;           // prlRead2Ctg.c:159-162
+    const int nk = map_read_kmers(len, K);
     uint64_t* row = rows + koff[r];
     map_stretch<NW>(words + off[r], 0, nk, K, tab, mask, row, [](uint64_t, int) {});
-    out[r] = map_decide(MapRow{row}, nk, K, map_multi(len, align_len, K), ctgs);
+    out[r] = map_lane_decide(row, len, nk, K, align_len, ctgs);
+}
+
+// the decision alone, a lane a read, from rows that are finished (the sharded engine: merged on the lead)
+__global__ __launch_bounds__(256) void map_decide_rows_kernel(const int32_t* __restrict__ lens, const uint64_t* __restrict__ koff, uint64_t n, int K,
+                                                              int align_len, MapCtgs ctgs, const uint64_t* __restrict__ rows,
+                                                              MapOut* __restrict__ out) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int len = lens[r];
+    out[r] = map_lane_decide(rows + koff[r], len, map_read_kmers(len, K), K, align_len, ctgs);
+}
+
+// A rank's lookups: k-mers of the batch's reads whose keys rank `me` of n owns are probed in its table and their hit words written to its
+// row buffer, which was zeroed before (a key of another rank leaves its word 0).  WAVE = false: a lane a read, as map_read_kernel; true: a
+// wavefront a read, a lane a stretch of ceil(nk / 64) k-mers, as map_read_wave_kernel (the long-read pass)
+template <int NW, bool WAVE>
+__global__ __launch_bounds__(256) void map_probe_owned_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
+                                                              const int32_t* __restrict__ lens, const uint64_t* __restrict__ koff, uint64_t n,
+                                                              int K, uint32_t n_ranks, uint32_t me, const uint64_t* __restrict__ tab,
+                                                              uint64_t mask, uint64_t* __restrict__ rows) {
+    const uint64_t r = WAVE ? (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6) : (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int nk = map_read_kmers(lens[r], K);
+    int j0 = 0, j1 = nk;
+    if (WAVE) {
+        const int per = (nk + 63) / 64;
+        j0 = (int)(threadIdx.x & 63) * per;
+        j1 = nk < j0 + per ? nk : j0 + per;
+    }
+    map_stretch_if<NW>(words + off[r], j0, j1, K, tab, mask, rows + koff[r],
+                       [n_ranks, me](const Kmer<NW>& ck) { return map_owner<NW>(ck, n_ranks) == me; }, [](uint64_t, int) {});
+}
+
+// rows |= part: another rank's hit words into the lead's.  A k-mer's key has one owner, so at most one rank brings a word that is not 0
+__global__ __launch_bounds__(256) void map_rows_merge_kernel(uint64_t* __restrict__ rows, const uint64_t* __restrict__ part, uint64_t n_words) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += stride) {
+        const uint64_t w = part[i];
+        if (w) rows[i] |= w;
+    }
 }
 
 
@@ -205,34 +298,10 @@ __device__ __forceinline__ void map_wave_collect(const MapWaveTable& t, int lane
     }
 }
 
-template <int NW>
-__global__ __launch_bounds__(256) void map_read_wave_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
-                                                            const int32_t* __restrict__ lens, const uint64_t* __restrict__ koff, uint64_t n,
-                                                            int K, int align_len, const uint64_t* __restrict__ tab, uint64_t mask,
-                                                            MapCtgs ctgs, uint64_t* rows, MapOut* __restrict__ out,
-                                                            unsigned long long* __restrict__ stats) {
-    __shared__ MapWaveTable tables[MAP_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t r = (uint64_t)blockIdx.x * MAP_WAVES + wave;
-    if (r >= n) return;                            // (no workgroup barrier follows)
-    const int len = lens[r];
-    const int nk = len >= K + 1 ? len - K + 1 : 0;
-    if (!nk) {
-        if (lane == 0) out[r] = MapOut{0, 0, 0, 0};
-        return;
-    }
-    MapWaveTable& t = tables[wave];
-    uint64_t* row = rows + koff[r];
-    const int multi = map_multi(len, align_len, K);
-    map_wave_clear(t, lane);
-    {   // the lookups: a lane rolls through its stretch of the read; every hit goes to the row and to the table
-        const int per = (nk + 63) / 64;
-        const int j0 = lane * per, j1 = nk < j0 + per ? nk : j0 + per;
-        map_stretch<NW>(words + off[r], j0, j1, K, tab, mask, row, [&t](uint64_t hit, int j) {
-            if ((uint32_t)hit) map_wave_put(t, hit, j);
-        });
-    }
-    map_wave_sync();
+// The decision half of the wave-per-read kernels: the read's ids are in the wave's table t (or t.over is raised) and its hit words in
+// row; the sums over the table, the passes and the scan of a read whose ids did not fit, the wave's butterfly, and out[r] from lane 0
+__device__ __forceinline__ void map_wave_decide(MapWaveTable& t, const uint64_t* row, int nk, int lane, int K, int multi, const MapCtgs& ctgs,
+                                                MapOut* out_r, unsigned long long* __restrict__ stats) {
     MapWaveSum s{0, 0, 0ull, 0u, 0u};
     uint32_t n_ids = t.n_ids;
     const bool over = t.over != 0;
@@ -293,13 +362,70 @@ __global__ __launch_bounds__(256) void map_read_wave_kernel(const uint64_t* __re
         if (key > s.key) { s.key = key; s.id = id; s.hi = hi; }
     }
     if (lane == 0) {
-        out[r] = s.counter ? map_place((uint64_t)s.id | (uint64_t)s.hi << 32, (int)(0xFFFFFFFFu - (uint32_t)s.key), K, s.counter2, ctgs)
+        *out_r = s.counter ? map_place((uint64_t)s.id | (uint64_t)s.hi << 32, (int)(0xFFFFFFFFu - (uint32_t)s.key), K, s.counter2, ctgs)
                            : MapOut{0, 0, 0, 0};
         if (stats) {                               // the measurement's figures: reads done in passes, distinct ids
             if (over) atomicAdd(stats, 1ull);
             atomicAdd(stats + 1, (unsigned long long)n_ids);
         }
     }
+}
+
+// the wave's prologue: its read, or false when the wave has nothing to decide (no read; a read without k-mers: out[r] is written here)
+__device__ __forceinline__ bool map_wave_read(const int32_t* __restrict__ lens, uint64_t n, int K, int lane, int wave, MapOut* __restrict__ out,
+                                              uint64_t& r, int& len, int& nk) {
+    r = (uint64_t)blockIdx.x * MAP_WAVES + wave;
+    if (r >= n) return false;                      // (no workgroup barrier follows)
+    len = lens[r];
+    nk = map_read_kmers(len, K);
+    if (!nk && lane == 0) out[r] = MapOut{0, 0, 0, 0};
+    return nk != 0;
+}
+
+template <int NW>
+__global__ __launch_bounds__(256) void map_read_wave_kernel(const uint64_t* __restrict__ words, const uint64_t* __restrict__ off,
+                                                            const int32_t* __restrict__ lens, const uint64_t* __restrict__ koff, uint64_t n,
+                                                            int K, int align_len, const uint64_t* __restrict__ tab, uint64_t mask,
+                                                            MapCtgs ctgs, uint64_t* rows, MapOut* __restrict__ out,
+                                                            unsigned long long* __restrict__ stats) {
+    __shared__ MapWaveTable tables[MAP_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t r;
+    int len, nk;
+    if (!map_wave_read(lens, n, K, lane, wave, out, r, len, nk)) return;
+    MapWaveTable& t = tables[wave];
+    uint64_t* row = rows + koff[r];
+    map_wave_clear(t, lane);
+    {   // the lookups: a lane rolls through its stretch of the read; every hit goes to the row and to the table
+        const int per = (nk + 63) / 64;
+        const int j0 = lane * per, j1 = nk < j0 + per ? nk : j0 + per;
+        map_stretch<NW>(words + off[r], j0, j1, K, tab, mask, row, [&t](uint64_t hit, int j) {
+            if ((uint32_t)hit) map_wave_put(t, hit, j);
+        });
+    }
+    map_wave_sync();
+    map_wave_decide(t, row, nk, lane, K, map_multi(len, align_len, K), ctgs, out + r, stats);
+}
+
+// the wave-per-read decision alone, from rows that are finished (the sharded engine: merged on the lead): the lanes bring the row's hits
+// to the table, then as above
+__global__ __launch_bounds__(256) void map_decide_rows_wave_kernel(const int32_t* __restrict__ lens, const uint64_t* __restrict__ koff, uint64_t n,
+                                                                   int K, int align_len, MapCtgs ctgs, const uint64_t* rows,
+                                                                   MapOut* __restrict__ out, unsigned long long* __restrict__ stats) {
+    __shared__ MapWaveTable tables[MAP_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t r;
+    int len, nk;
+    if (!map_wave_read(lens, n, K, lane, wave, out, r, len, nk)) return;
+    MapWaveTable& t = tables[wave];
+    const uint64_t* row = rows + koff[r];
+    map_wave_clear(t, lane);
+    for (int j = lane; j < nk; j += 64) {
+        const uint64_t hit = row[j];
+        if ((uint32_t)hit) map_wave_put(t, hit, j);
+    }
+    map_wave_sync();
+    map_wave_decide(t, row, nk, lane, K, map_multi(len, align_len, K), ctgs, out + r, stats);
 }
 
 namespace {
@@ -321,6 +447,26 @@ struct DevBuf {
     void release() { if (p) arena_free(p); p = nullptr; cap = 0; }
 };
 
+// f(std::integral_constant<int, NW>) for an engine's flavour: a kernel's argument list is written once
+template <typename F>
+void map_with_nw(int nw, F f) {
+    if (nw == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 4>{});
+}
+
+// the index build's work items: (contig, first k-mer) stretches of MAP_ITEM k-mers
+void map_index_items(const MapContigs& c, int K, std::vector<uint32_t>& item_c, std::vector<uint32_t>& item_j) {
+    for (size_t i = 0; i < c.len.size(); i++)
+        for (int j = 0; j < c.len[i] - K + 1; j += MAP_ITEM) { item_c.push_back((uint32_t)i); item_j.push_back((uint32_t)j); }
+}
+
+int map_check_device(int dev) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { pg_set_error("map: no HIP device"); return PG_ENODEV; }
+    if (dev < 0 || dev >= n) { pg_set_error("map: HIP device " + std::to_string(dev) + " does not exist"); return PG_ENODEV; }
+    return PG_OK;
+}
+
 class DeviceMapEngine : public MapEngine {
 public:
     DeviceMapEngine(int device, int K, int nw) : dev_(device), K_(K), nw_(nw) {}
@@ -335,9 +481,7 @@ public:
         arena_unpin(dev_);
     }
     int begin() {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { pg_set_error("map: no HIP device"); return PG_ENODEV; }
-        if (dev_ < 0 || dev_ >= n) { pg_set_error("map: HIP device " + std::to_string(dev_) + " does not exist"); return PG_ENODEV; }
+        if (int rc = map_check_device(dev_)) return rc;
         MAP_HIP(hipSetDevice(dev_));
         arena_pin(dev_);
         ready_ = true;
@@ -361,8 +505,7 @@ public:
         if ((rc = tab_.reserve(slots_ * SW)) || (rc = flag_.reserve(1))) return rc;
         // the contigs go through the read buffers; the work items are (contig, first k-mer) stretches of MAP_ITEM k-mers
         std::vector<uint32_t> item_c, item_j;
-        for (size_t i = 0; i < n_ctg; i++)
-            for (int j = 0; j < c.len[i] - K_ + 1; j += MAP_ITEM) { item_c.push_back((uint32_t)i); item_j.push_back((uint32_t)j); }
+        map_index_items(c, K_, item_c, item_j);
         const uint64_t n_items = item_c.size();
         DevBuf<uint32_t> d_ic, d_ij, d_id;
         DevBuf<uint64_t> d_w, d_off;
@@ -441,12 +584,7 @@ public:
     }
 
 private:
-    // f(std::integral_constant<int, NW>) for the engine's flavour: a kernel's argument list is written once
-    template <typename F>
-    void with_nw(F f) const {
-        if (nw_ == 2) f(std::integral_constant<int, 2>{});
-        else f(std::integral_constant<int, 4>{});
-    }
+    template <typename F> void with_nw(F f) const { map_with_nw(nw_, f); }
     int dev_, K_, nw_;
     bool ready_ = false;
     hipStream_t st_ = nullptr;
@@ -461,6 +599,279 @@ private:
     DevBuf<unsigned long long> stats_;              // the wave kernel's two figures
 };
 
+// The index cut over n ranks by map_owner (map_index.hpp), for a contig set whose one table does not fit a card.  One process, one host
+// thread; rank i is (devices[i], a stream of its own), rank 0 the lead, and an ordinal may repeat (several ranks on one GPU: how this is
+// tested).  Ranks on more than one physical GPU have never run.
+//   build   every rank receives the packed contigs and counts the keys it owns (map_count_owned_kernel); its table is made for exactly
+//           that many (arena_malloc, no headroom), zeroed, and filled by map_index_owned_kernel.  A rank without keys launches nothing
+//           and keeps a table of the smallest size, zeroed.  Any rank's spin flag fails the build
+//   map     every rank receives the batch's reads, zeroes its row buffer and probes the keys it owns (map_probe_owned_kernel).  The lead
+//           waits for each other rank's event (hipStreamWaitEvent), copies its rows into the staging buffer (hipMemcpyPeerAsync across
+//           devices, hipMemcpyAsync on its own) and ORs them in (map_rows_merge_kernel): all on the lead's stream, so one staging buffer
+//           serves every rank.  The decision runs on the lead from the finished rows (map_decide_rows_kernel / _wave_kernel).  The host
+//           waits once a batch, for the lead's stream; there is no spin loop and no atomic across ranks
+class ShardedDeviceMapEngine : public MapEngine {
+public:
+    ShardedDeviceMapEngine(const int* devices, int n, int K, int nw) : K_(K), nw_(nw), rk_((size_t)n) {
+        for (int i = 0; i < n; i++) rk_[(size_t)i].dev = devices[i];
+        ranks.resize((size_t)n);
+    }
+    ~ShardedDeviceMapEngine() override {
+        for (R& r : rk_) {
+            if (!r.pinned) continue;
+            (void)hipSetDevice(r.dev);
+            if (r.st) (void)hipStreamSynchronize(r.st);
+            if (r.tab) arena_free(r.tab);
+            r.flag.release(); r.count.release(); r.rwords.release(); r.roff.release(); r.rlen.release(); r.rkoff.release(); r.rows.release();
+            if (&r == &rk_[0]) { len_.release(); bal_.release(); staging_.release(); out_.release(); stats_.release(); }
+            if (r.st) (void)hipStreamDestroy(r.st);
+            for (hipEvent_t e : {r.e0, r.e1, r.e2, r.e3, r.e4}) if (e) (void)hipEventDestroy(e);
+            arena_unpin(r.dev);
+        }
+    }
+    int begin() {
+        for (R& r : rk_) {
+            if (int rc = map_check_device(r.dev)) return rc;
+            MAP_HIP(hipSetDevice(r.dev));
+            arena_pin(r.dev);
+            r.pinned = true;
+            MAP_HIP(hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking));
+            for (hipEvent_t* e : {&r.e0, &r.e1, &r.e2, &r.e3, &r.e4}) MAP_HIP(hipEventCreate(e));
+        }
+        return PG_OK;
+    }
+    int build(const MapContigs& c, const int32_t* ctg_len, const int8_t* bal, uint32_t n_ids) override {
+        const size_t n = rk_.size();
+        std::vector<uint32_t> item_c, item_j;
+        map_index_items(c, K_, item_c, item_j);
+        std::vector<Ctg> ctg(n);
+        std::vector<unsigned long long> share(n, 0);
+        std::vector<uint32_t> gave_up(n, 0);
+        const int rc = build_ranks(c, ctg_len, bal, n_ids, item_c, item_j, ctg, share, gave_up);
+        // However it ended: a failure on one rank leaves the others' streams copying out of the vectors above and the caller's arrays and
+        // into share / gave_up, so every stream is waited for before they go, and the ranks' copies of the contigs are given back
+        if (rc) sync_all();
+        for (size_t i = 0; i < n; i++) {
+            (void)hipSetDevice(rk_[i].dev);
+            ctg[i].release();
+        }
+        return rc;
+    }
+    int map(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out, bool wave) override {
+        if (!b.n) return PG_OK;
+        const int rc = map_ranks(b, align_len, out, rows_out, wave);
+        if (rc) sync_all();                         // no stream is left reading the caller's batch or writing its results
+        return rc;
+    }
+
+private:
+    void sync_all() {
+        for (R& r : rk_) {
+            (void)hipSetDevice(r.dev);
+            if (r.st) (void)hipStreamSynchronize(r.st);
+        }
+    }
+    int map_ranks(const MapBatch& b, int align_len, MapOut* out, uint64_t* rows_out, bool wave) {
+        const uint32_t n = (uint32_t)rk_.size();
+        const uint64_t n_k = b.kmer_off[b.n];
+        R& lead = rk_[0];
+        int rc;
+        const double c0 = now_s();
+        const dim3 block(256);
+        const dim3 grid_reads((unsigned)(wave ? (b.n + MAP_WAVES - 1) / MAP_WAVES : (b.n + 255) / 256));
+        // 1. every rank: the reads, a zeroed row buffer, its lookups
+        for (uint32_t i = 0; i < n; i++) {
+            R& r = rk_[i];
+            MAP_HIP(hipSetDevice(r.dev));
+            if ((rc = r.rwords.reserve(b.n_words)) || (rc = r.roff.reserve(b.n)) || (rc = r.rlen.reserve(b.n)) || (rc = r.rkoff.reserve(b.n + 1)) ||
+                (rc = r.rows.reserve(std::max<uint64_t>(n_k, 1)))) return rc;
+            MAP_HIP(hipMemcpyAsync(r.rwords.p, b.words, b.n_words * 8, hipMemcpyHostToDevice, r.st));
+            MAP_HIP(hipMemcpyAsync(r.roff.p, b.off, b.n * 8, hipMemcpyHostToDevice, r.st));
+            MAP_HIP(hipMemcpyAsync(r.rlen.p, b.len, b.n * 4, hipMemcpyHostToDevice, r.st));
+            MAP_HIP(hipMemcpyAsync(r.rkoff.p, b.kmer_off, (b.n + 1) * 8, hipMemcpyHostToDevice, r.st));
+            if (n_k) MAP_HIP(hipMemsetAsync(r.rows.p, 0, n_k * sizeof(uint64_t), r.st));
+            MAP_HIP(hipEventRecord(r.e0, r.st));
+            map_with_nw(nw_, [&](auto nw) {
+                constexpr int NW = decltype(nw)::value;
+                if (wave) hipLaunchKernelGGL((map_probe_owned_kernel<NW, true>), grid_reads, block, 0, r.st, r.rwords.p, r.roff.p, r.rlen.p, r.rkoff.p,
+                                             b.n, K_, n, i, r.tab, r.slots - 1, r.rows.p);
+                else hipLaunchKernelGGL((map_probe_owned_kernel<NW, false>), grid_reads, block, 0, r.st, r.rwords.p, r.roff.p, r.rlen.p, r.rkoff.p,
+                                        b.n, K_, n, i, r.tab, r.slots - 1, r.rows.p);
+            });
+            MAP_HIP(hipGetLastError());
+            MAP_HIP(hipEventRecord(r.e1, r.st));
+        }
+        // 2. the lead: the other ranks' rows, one after the other through the staging buffer
+        MAP_HIP(hipSetDevice(lead.dev));
+        if ((rc = out_.reserve(b.n)) || (n > 1 && n_k && (rc = staging_.reserve(n_k))) || (wave && (rc = stats_.reserve(2)))) return rc;
+        // the lead's stream goes behind every other rank's probe, k-mers or none: the host's one wait below then covers every rank's
+        // events and its copies out of the caller's batch.  e4 marks where the waiting ends, so that t_merge is the copies and the OR alone
+        for (uint32_t i = 1; i < n; i++) MAP_HIP(hipStreamWaitEvent(lead.st, rk_[i].e1, 0));
+        MAP_HIP(hipEventRecord(lead.e4, lead.st));
+        for (uint32_t i = 1; i < n && n_k; i++) {
+            R& r = rk_[i];
+            if (r.dev == lead.dev) MAP_HIP(hipMemcpyAsync(staging_.p, r.rows.p, n_k * sizeof(uint64_t), hipMemcpyDeviceToDevice, lead.st));
+            else MAP_HIP(hipMemcpyPeerAsync(staging_.p, lead.dev, r.rows.p, r.dev, n_k * sizeof(uint64_t), lead.st));
+            const unsigned blocks = (unsigned)std::min<uint64_t>((n_k + 255) / 256, 65536);
+            hipLaunchKernelGGL(map_rows_merge_kernel, dim3(blocks), block, 0, lead.st, lead.rows.p, staging_.p, n_k);
+            MAP_HIP(hipGetLastError());
+        }
+        MAP_HIP(hipEventRecord(lead.e2, lead.st));
+        // 3. the decision, from the finished rows
+        if (wave) {
+            MAP_HIP(hipMemsetAsync(stats_.p, 0, 2 * sizeof(unsigned long long), lead.st));
+            hipLaunchKernelGGL(map_decide_rows_wave_kernel, grid_reads, block, 0, lead.st, lead.rlen.p, lead.rkoff.p, b.n, K_, align_len, ctgs_,
+                               lead.rows.p, out_.p, stats_.p);
+        } else
+            hipLaunchKernelGGL(map_decide_rows_kernel, grid_reads, block, 0, lead.st, lead.rlen.p, lead.rkoff.p, b.n, K_, align_len, ctgs_,
+                               lead.rows.p, out_.p);
+        MAP_HIP(hipGetLastError());
+        MAP_HIP(hipEventRecord(lead.e3, lead.st));
+        MAP_HIP(hipMemcpyAsync(out, out_.p, b.n * sizeof(MapOut), hipMemcpyDeviceToHost, lead.st));
+        if (rows_out && n_k) MAP_HIP(hipMemcpyAsync(rows_out, lead.rows.p, n_k * sizeof(uint64_t), hipMemcpyDeviceToHost, lead.st));
+        unsigned long long stats[2] = {0, 0};
+        if (wave) MAP_HIP(hipMemcpyAsync(stats, stats_.p, sizeof stats, hipMemcpyDeviceToHost, lead.st));
+        // the batch's one wait: the lead's stream is behind every other rank's e1
+        MAP_HIP(hipStreamSynchronize(lead.st));
+        n_passes += stats[0];
+        n_ids += stats[1];
+        float ms = 0, all = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            MAP_HIP(hipEventElapsedTime(&ms, rk_[i].e0, rk_[i].e1));
+            ranks[i].t_probe += ms * 1e-3;
+        }
+        MAP_HIP(hipEventElapsedTime(&ms, lead.e4, lead.e2));
+        t_merge += ms * 1e-3;
+        MAP_HIP(hipEventElapsedTime(&ms, lead.e2, lead.e3));
+        t_decide += ms * 1e-3;
+        MAP_HIP(hipEventElapsedTime(&all, lead.e0, lead.e3));
+        t_kernel += all * 1e-3;
+        t_copy += now_s() - c0 - all * 1e-3;
+        return PG_OK;
+    }
+    struct Ctg {                                    // a rank's copy of the contigs, alive while its table is built
+        DevBuf<uint32_t> ic, ij, id;
+        DevBuf<uint64_t> w, off;
+        DevBuf<int32_t> len;
+        void release() { ic.release(); ij.release(); id.release(); w.release(); off.release(); len.release(); }
+    };
+    // build()'s work; build() owns what the ranks' streams read and write meanwhile, and cleans up after every way out of here
+    int build_ranks(const MapContigs& c, const int32_t* ctg_len, const int8_t* bal, uint32_t n_ids, const std::vector<uint32_t>& item_c,
+                    const std::vector<uint32_t>& item_j, std::vector<Ctg>& ctg, std::vector<unsigned long long>& share,
+                    std::vector<uint32_t>& gave_up) {
+        const uint32_t n = (uint32_t)rk_.size();
+        const size_t n_ctg = c.len.size();
+        const int SW = nw_ + 2;
+        int rc;
+        R& lead = rk_[0];
+        MAP_HIP(hipSetDevice(lead.dev));
+        if ((rc = len_.reserve(n_ids)) || (rc = bal_.reserve(n_ids))) return rc;
+        if (n_ids) {
+            MAP_HIP(hipMemcpyAsync(len_.p, ctg_len, n_ids * sizeof(int32_t), hipMemcpyHostToDevice, lead.st));
+            MAP_HIP(hipMemcpyAsync(bal_.p, bal, n_ids * sizeof(int8_t), hipMemcpyHostToDevice, lead.st));
+        }
+        ctgs_ = MapCtgs{len_.p, bal_.p, n_ids};
+        const uint64_t n_items = item_c.size();
+        const dim3 grid((unsigned)((n_items + 255) / 256)), block(256);
+        // 1. the contigs to every rank, and its count
+        for (uint32_t i = 0; i < n; i++) {
+            R& r = rk_[i];
+            Ctg& g = ctg[i];
+            MAP_HIP(hipSetDevice(r.dev));
+            if ((rc = r.flag.reserve(1)) || (rc = r.count.reserve(1))) return rc;
+            MAP_HIP(hipEventRecord(r.e0, r.st));
+            MAP_HIP(hipMemsetAsync(r.flag.p, 0, sizeof(uint32_t), r.st));
+            MAP_HIP(hipMemsetAsync(r.count.p, 0, sizeof(unsigned long long), r.st));
+            if (!n_items) continue;
+            if ((rc = g.ic.reserve(n_items)) || (rc = g.ij.reserve(n_items)) || (rc = g.id.reserve(n_ctg)) || (rc = g.w.reserve(c.words.size())) ||
+                (rc = g.off.reserve(n_ctg + 1)) || (rc = g.len.reserve(n_ctg))) return rc;
+            MAP_HIP(hipMemcpyAsync(g.ic.p, item_c.data(), n_items * 4, hipMemcpyHostToDevice, r.st));
+            MAP_HIP(hipMemcpyAsync(g.ij.p, item_j.data(), n_items * 4, hipMemcpyHostToDevice, r.st));
+            MAP_HIP(hipMemcpyAsync(g.id.p, c.id.data(), n_ctg * 4, hipMemcpyHostToDevice, r.st));
+            MAP_HIP(hipMemcpyAsync(g.w.p, c.words.data(), c.words.size() * 8, hipMemcpyHostToDevice, r.st));
+            MAP_HIP(hipMemcpyAsync(g.off.p, c.off.data(), (n_ctg + 1) * 8, hipMemcpyHostToDevice, r.st));
+            MAP_HIP(hipMemcpyAsync(g.len.p, c.len.data(), n_ctg * 4, hipMemcpyHostToDevice, r.st));
+            map_with_nw(nw_, [&](auto nw) {
+                hipLaunchKernelGGL((map_count_owned_kernel<decltype(nw)::value>), grid, block, 0, r.st, g.w.p, g.off.p, g.len.p, g.id.p, g.ic.p,
+                                   g.ij.p, n_items, K_, n, i, r.count.p);
+            });
+            MAP_HIP(hipGetLastError());
+            MAP_HIP(hipMemcpyAsync(&share[i], r.count.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, r.st));
+        }
+        // 2. a table of exactly that share, and the keys
+        for (uint32_t i = 0; i < n; i++) {
+            R& r = rk_[i];
+            Ctg& g = ctg[i];
+            MAP_HIP(hipSetDevice(r.dev));
+            MAP_HIP(hipStreamSynchronize(r.st));
+            r.slots = map_table_slots(share[i]);
+            ranks[i].keys = share[i];
+            ranks[i].slots = r.slots;
+            if (r.tab) arena_free(r.tab);
+            r.tab = nullptr;
+            if (arena_malloc(&r.tab, r.slots * SW * sizeof(uint64_t)) != hipSuccess) {
+                pg_set_error("map: device allocation failed (rank " + std::to_string(i) + ": a table of " + std::to_string(r.slots) + " slots)");
+                return PG_ENOMEM;
+            }
+            MAP_HIP(hipMemsetAsync(r.tab, 0, r.slots * SW * sizeof(uint64_t), r.st));
+            if (share[i]) {                         // (a rank that owns nothing launches nothing)
+                map_with_nw(nw_, [&](auto nw) {
+                    hipLaunchKernelGGL((map_index_owned_kernel<decltype(nw)::value>), grid, block, 0, r.st, g.w.p, g.off.p, g.len.p, g.id.p,
+                                       g.ic.p, g.ij.p, n_items, K_, n, i, r.tab, r.slots - 1, r.flag.p);
+                });
+                MAP_HIP(hipGetLastError());
+            }
+            MAP_HIP(hipEventRecord(r.e1, r.st));
+            MAP_HIP(hipMemcpyAsync(&gave_up[i], r.flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, r.st));
+        }
+        uint64_t total = 0;
+        double t_max = 0;
+        bool spun = false;
+        for (uint32_t i = 0; i < n; i++) {
+            R& r = rk_[i];
+            MAP_HIP(hipSetDevice(r.dev));
+            MAP_HIP(hipStreamSynchronize(r.st));
+            float ms = 0;
+            MAP_HIP(hipEventElapsedTime(&ms, r.e0, r.e1));
+            t_max = std::max(t_max, (double)ms * 1e-3);
+            total += share[i];
+            spun = spun || gave_up[i];
+        }
+        t_index += t_max;                           // (the ranks build side by side: the longest)
+        if (spun) {
+            pg_set_error("map: the index build gave up on a claimed slot after " + std::to_string(MAP_SPIN_CAP) +
+                         " trips (the slot's key was never published); the index is not complete");
+            return PG_ESPIN;
+        }
+        if (total != c.n_kmers) {
+            pg_set_error("map: the ranks own " + std::to_string(total) + " keys of " + std::to_string(c.n_kmers));
+            return PG_EINVAL;
+        }
+        return PG_OK;
+    }
+    struct R {                                      // a rank
+        int dev = 0;
+        bool pinned = false;
+        hipStream_t st = nullptr;
+        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr, e4 = nullptr;   // probe / build from e0 to e1; the lead: every rank's probe done at e4, merge to e2, decide to e3
+        uint64_t* tab = nullptr;                    // exactly slots * (NW + 2) words
+        uint64_t slots = 0;
+        DevBuf<uint32_t> flag;                      // raised by a lane of the index build that gave up on a claimed slot
+        DevBuf<unsigned long long> count;           // the keys it owns
+        DevBuf<uint64_t> rwords, roff, rkoff, rows;
+        DevBuf<int32_t> rlen;
+    };
+    int K_, nw_;
+    std::vector<R> rk_;
+    MapCtgs ctgs_{nullptr, nullptr, 0};
+    // the lead's alone
+    DevBuf<int32_t> len_;
+    DevBuf<int8_t> bal_;
+    DevBuf<uint64_t> staging_;
+    DevBuf<MapOut> out_;
+    DevBuf<unsigned long long> stats_;
+};
+
 }  // namespace
 
 int map_wave_ids() { return MAP_WAVE_IDS; }
@@ -469,6 +880,22 @@ std::unique_ptr<MapEngine> map_engine_device(int device, int K, int nw) {
     std::unique_ptr<DeviceMapEngine> e(new DeviceMapEngine(device, K, nw));
     if (e->begin() != PG_OK) return nullptr;
     return std::unique_ptr<MapEngine>(e.release());
+}
+
+std::unique_ptr<MapEngine> map_engine_device_sharded(const int* devices, int n, int K, int nw) {
+    if (!devices || n < 1 || n > DEVICE_LIST_MAX_RANKS) { pg_set_error("map: an index is cut over 1 to " + std::to_string(DEVICE_LIST_MAX_RANKS) + " ranks"); return nullptr; }
+    std::unique_ptr<ShardedDeviceMapEngine> e(new ShardedDeviceMapEngine(devices, n, K, nw));
+    if (e->begin() != PG_OK) return nullptr;
+    return std::unique_ptr<MapEngine>(e.release());
+}
+
+int map_device_free_bytes(int device, uint64_t* free_bytes) {
+    if (int rc = map_check_device(device)) return rc;
+    MAP_HIP(hipSetDevice(device));
+    size_t free_b = 0, total_b = 0;
+    MAP_HIP(arena_mem_info(&free_b, &total_b));
+    *free_bytes = free_b;
+    return PG_OK;
 }
 
 }  // namespace pg
