@@ -420,6 +420,41 @@ int pg_sort_records(uint64_t *d_records, uint64_t n_records, int mer127, void *s
  * records' bytes; otherwise the call allocates what is missing). */
 int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void *d_workspace, uint64_t workspace_bytes, void *stream);
 
+/* The k-mer index: which k-mers of a batch of sequences were counted, and how often (csrc/kindex.hpp).  The reference has no operator
+ * of its own for this; its multi-k step looks the k-mers of reads up in a finished set the same way (contig -m: iterate.c, kmerhash.c).
+ * An index is one open-addressing table over the distinct k-mers of pass 1 -- pg_host_kindex_bytes(n_records, mer127) bytes, at most
+ * half full -- whose value is the record's cnt word (layout above).  A stored record has coverage >= 1 in bits 31:24 of cnt, so an
+ * answer of 0 means "not in the set" and nothing else.  A k-mer that pg_finalize's -d filter removed stays in the export array with the
+ * `deleted` bit of word B set (bit 25; thread_delow, prlHashReads.c:953-996): the build passes such records over, so it reads as 0 too.
+ *   pg_kindex_build     records: n_records records in export format (what pg_export, pg_export_peek, pg_export_take and
+ *                       pg_sort_records leave; any order, keys distinct).  device >= 0: device memory on that device, the table is cut
+ *                       from that device's arena; device = -1: host memory, the host twin (no GPU).  The index owns its table only: the
+ *                       records stay the caller's and may be freed when the call returns (it synchronises the stream).
+ *                       Null on failure, and pg_last_error's message ends with the code in brackets: (PG_ENOMEM) out of device
+ *                       memory, (PG_EINVAL) K even or outside 13..63 / 13..127, or "duplicate key in records", (PG_ESPIN), (PG_ENODEV).
+ *   pg_kindex_from_ctx  straight from a finalized context, on its device (partition engine: its export array where it lies, no copy
+ *                       of the records; the global-set engine exports into a temporary array).  Before pg_finalize: null, (PG_ESTATE).
+ *   pg_kindex_query     one batch of sequences laid out as pg_count_reads' batches: packed = pg_pack_read words, either every sequence
+ *                       of uniform_len bases (word_off / kmer_base unused) or word_off[n_seqs] + kmer_base[n_seqs + 1].  A sequence of
+ *                       len bases has max(0, len - K + 1) k-mers -- one of exactly K bases has one, one of fewer none -- so for a
+ *                       ragged batch kmer_base is the exclusive prefix sum of that, and n_kmers = kmer_base[n_seqs].  Behind the last
+ *                       sequence nw + 1 words must be readable (3 for the 63-mer flavour, 5 for the 127-mer one).
+ *                       out_cnt[kmer_base[r] + j] = the cnt word of k-mer j of sequence r, or 0;  out_summary[4 r ..] = k-mers present,
+ *                       sum of their coverage (bits 31:24), least coverage among them (0 when none is present), index of the first
+ *                       absent k-mer (the sequence's number of k-mers when none is).  Either may be null, not both.
+ *                       wave = 0: a lane per sequence (read-sized sequences); wave != 0: a wavefront per sequence (contig-sized
+ *                       ones); same answers.  Pointers are device memory of the index's device and the call is asynchronous on
+ *                       `stream`; for a host-twin index they are host memory, and wave and stream are ignored.
+ *   pg_kindex_info      out[0] keys (the records the table was made for, deleted ones included), [1] slots, [2] bytes of the table, [3] device (-1 as a 64-bit value: the host twin) */
+typedef struct pg_kindex pg_kindex;
+pg_kindex *pg_kindex_build(int device, int K, int mer127, const uint64_t *records, uint64_t n_records, void *stream);
+pg_kindex *pg_kindex_from_ctx(pg_ctx *ctx, void *stream);
+int pg_kindex_query(pg_kindex *ix, const uint64_t *packed, const uint64_t *word_off, const uint64_t *kmer_base, uint64_t n_seqs,
+                    uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t *out_cnt, uint64_t *out_summary, void *stream);
+int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
+void pg_kindex_destroy(pg_kindex *ix);
+uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */
+
 /* ------------------------------------------------------------------------------------------------
  * 4. Multi-GPU pass 1.  The reference hands every k-mer to the set it hashes to through shared memory
  *    (each of its `thrd_num` workers scans the whole buffer for `hashBanBuffer[i] % thrd_num == id`,

@@ -169,6 +169,17 @@ def lib() -> C.CDLL:
     L.pg_host_emu_clip_tips.argtypes = [u64p, C.c_uint64, u64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u64p]
     L.pg_host_emu_layout_static.argtypes = [u64p, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int, u64p]
     L.pg_host_emu_home_slots.argtypes = [u64p, C.c_uint64, C.c_int, C.c_uint64, u64p]
+    # the k-mer index (include/soapdenovo2_amd.h, section 3)
+    L.pg_kindex_build.restype = C.c_void_p
+    L.pg_kindex_build.argtypes = [C.c_int, C.c_int, C.c_int, u64p, C.c_uint64, C.c_void_p]
+    L.pg_kindex_from_ctx.restype = C.c_void_p
+    L.pg_kindex_from_ctx.argtypes = [C.c_void_p, C.c_void_p]
+    L.pg_kindex_query.argtypes = [C.c_void_p, u64p, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u64p, u64p, C.c_void_p]
+    L.pg_kindex_info.argtypes = [C.c_void_p, u64p]
+    L.pg_kindex_destroy.argtypes = [C.c_void_p]
+    L.pg_kindex_destroy.restype = None
+    L.pg_host_kindex_bytes.restype = C.c_uint64
+    L.pg_host_kindex_bytes.argtypes = [C.c_uint64, C.c_int]
     _lib = L
     return L
 
@@ -184,6 +195,7 @@ EXPORTED_SYMBOLS = [
     "pg_set_read_len_bound", "pg_graph_add_packed_device_ragged", "pg_expect", "pg_host_plan_memory", "pg_create_planned", "pg_graph_add_packed_device_segments",
     "call_align", "call_align_127mer", "pg_map_reads", "pg_map_hits", "pg_map_long_reads", "pg_map_wave_ids", "pg_map_long_last_stats",
     "pg_map_reads_sharded", "pg_map_hits_sharded", "pg_map_long_reads_sharded", "pg_host_map_owner", "pg_host_map_plan",
+    "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
 ]
 
 
@@ -773,6 +785,14 @@ class KmerCounter:
         _check(lib().pg_records_checksum(ptr, n.value, self.nw + 2, out.ctypes.data, self._stream()), "pg_records_checksum")
         return out
 
+    def index(self) -> "KmerIndex":
+        """The k-mer index of the distinct k-mers, after finalize (pg_kindex_from_ctx): on this counter's device, and its own --
+        the counter may be closed while the index lives."""
+        h = lib().pg_kindex_from_ctx(self.h, self._stream())
+        if not h:
+            raise PgError("pg_kindex_from_ctx failed: " + lib().pg_last_error().decode())
+        return KmerIndex(h, self.K, self.mer127, self.device)
+
     def export(self, sort: bool = False) -> np.ndarray:
         """(n, nw + 2) uint64 records on the host (key words, cnt, set << 56 | first ordinal); with sort=True in the layout
         replay's insertion order (pg_sort_records on the device)."""
@@ -798,3 +818,141 @@ class KmerCounter:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the k-mer index (pg_kindex_*): which k-mers of a batch of sequences were counted, and how often
+# ---------------------------------------------------------------------------------------------------------
+KINDEX_SUMMARY_FIELDS = ["present", "coverage_sum", "coverage_min", "first_absent"]
+
+
+def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
+    """pg_host_kindex_bytes: the table an index of n_records k-mers cuts (no GPU)."""
+    return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
+
+
+class KmerIndex:
+    """A lookup table over the distinct k-mers of pass 1 (pg_kindex_*): `KmerCounter.index()` after finalize, or
+    `KmerIndex.from_records(records, K)`.  On a GPU the batches and the answers are torch tensors of that device; with device = -1
+    (the host twin, no GPU) they are numpy arrays.  An answer is a record's cnt word, 0 for a k-mer that is not in the set."""
+
+    def __init__(self, handle, K: int, mer127: bool, device: int):
+        self.h, self.K, self.mer127, self.device = handle, K, mer127, device
+        self.nw = 4 if mer127 else 2
+        if device >= 0:
+            import torch
+            self.torch = torch
+
+    @staticmethod
+    def from_records(records, K: int, mer127: bool = False, device: int = 0) -> "KmerIndex":
+        """records: (n, nw + 2) records as KmerCounter.export returns them, any order -- a numpy array (copied to `device` for the
+        build, or indexed where it lies by the host twin with device = -1) or a torch tensor on `device`."""
+        rw = (4 if mer127 else 2) + 2
+        keep = None
+        if device < 0:
+            keep = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, rw)
+            n, ptr, stream = keep.shape[0], keep.ctypes.data, None
+        else:
+            import torch
+            if isinstance(records, np.ndarray):
+                records = torch.from_numpy(np.ascontiguousarray(records, dtype=np.uint64).reshape(-1).view(np.int64)).to(f"cuda:{device}")
+            keep = records.contiguous().view(-1)
+            if keep.device.index != device or keep.element_size() != 8:
+                raise PgError("KmerIndex.from_records: the records are 64-bit words on the index's device")
+            n, ptr = keep.numel() // rw, keep.data_ptr()
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        h = lib().pg_kindex_build(device, K, 1 if mer127 else 0, ptr if n else None, n, stream)
+        if not h:
+            raise PgError("pg_kindex_build failed: " + lib().pg_last_error().decode())
+        return KmerIndex(h, K, mer127, device)
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream) if self.device >= 0 else None
+
+    def _ptr(self, a):
+        if a is None:
+            return None
+        if self.device < 0:
+            if a.dtype != np.uint64 or not a.flags["C_CONTIGUOUS"]:
+                raise PgError("KmerIndex: the host twin takes contiguous numpy uint64 arrays")
+            return a.ctypes.data
+        return a.data_ptr()
+
+    def _query(self, packed, word_off, kmer_base, n_seqs, uniform_len, n_kmers, wave, counts, summary):
+        if not counts and not summary:
+            raise PgError("KmerIndex: ask for the counts, the summary or both")
+        # (one element at least: an empty array has no address, and a null pointer means "not wanted")
+        if self.device < 0:
+            out = np.zeros(max(n_kmers, 1), dtype=np.uint64) if counts else None
+            summ = np.zeros((max(n_seqs, 1), 4), dtype=np.uint64) if summary else None
+        else:
+            t, dev = self.torch, f"cuda:{self.device}"
+            out = t.zeros(max(n_kmers, 1), dtype=t.int64, device=dev) if counts else None
+            summ = t.zeros((max(n_seqs, 1), 4), dtype=t.int64, device=dev) if summary else None
+        _check(lib().pg_kindex_query(self.h, self._ptr(packed), self._ptr(word_off), self._ptr(kmer_base), n_seqs, uniform_len, n_kmers, int(bool(wave)),
+                                     self._ptr(out), self._ptr(summ), self._stream()), "pg_kindex_query")
+        out = out[:n_kmers] if counts else None
+        summ = summ[:n_seqs] if summary else None
+        return (out, summ) if counts and summary else (out if counts else summ)
+
+    def query_uniform(self, d_packed, n_seqs: int, seq_len: int, wave: bool = False, counts: bool = True, summary: bool = False):
+        """Every sequence of seq_len bases, sequence r at word r * packed_words(seq_len) (pack_reads_uniform): the cnt words of its
+        max(0, seq_len - K + 1) k-mers at [r * that ..) of the counts, a row of KINDEX_SUMMARY_FIELDS in the summary.  Returns the counts,
+        the summary, or (counts, summary).  wave=True: a wavefront instead of a lane per sequence (contig-sized sequences)."""
+        nk = max(0, seq_len - self.K + 1)
+        return self._query(d_packed, None, None, n_seqs, seq_len, n_seqs * nk, wave, counts, summary)
+
+    def query_ragged(self, d_packed, d_word_off, d_kmer_base, n_seqs: int, n_kmers: int, wave: bool = False, counts: bool = True,
+                     summary: bool = False):
+        """Sequences of any lengths (pack_seqs_ragged): sequence r starts at word d_word_off[r] and its answers at d_kmer_base[r]."""
+        return self._query(d_packed, d_word_off, d_kmer_base, n_seqs, 0, n_kmers, wave, counts, summary)
+
+    def info(self) -> dict:
+        out = np.zeros(4, dtype=np.uint64)
+        _check(lib().pg_kindex_info(self.h, out.ctypes.data), "pg_kindex_info")
+        return {"keys": int(out[0]), "slots": int(out[1]), "bytes": int(out[2]), "device": int(out.view(np.int64)[3])}
+
+    def close(self) -> None:
+        if self.h:
+            lib().pg_kindex_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pack_seqs_ragged(seqs: Sequence[np.ndarray], K: int):
+    """pack_reads_ragged for the k-mer index's batches: sequences of any length, those shorter than K included (they have no k-mers and
+    keep their place) -> (words, word_off [n], kmer_base [n + 1]) numpy uint64, with 8 words of readable padding."""
+    L = lib()
+    n = len(seqs)
+    lens = np.array([len(s) for s in seqs], dtype=np.int64)
+    word_off = np.zeros(n, dtype=np.uint64)
+    kmer_base = np.zeros(n + 1, dtype=np.uint64)
+    if n:
+        word_off[1:] = np.cumsum((lens[:-1] + 31) // 32)
+        kmer_base[1:] = np.cumsum(np.maximum(lens - K + 1, 0))
+    words = np.zeros(int(((lens + 31) // 32).sum()) + 8, dtype=np.uint64)
+    for i, s in enumerate(seqs):
+        s = np.ascontiguousarray(s, dtype=np.uint8)
+        if len(s):
+            L.pg_pack_read(s.ctypes.data, len(s), words[int(word_off[i]):].ctypes.data)
+    return words, word_off, kmer_base
+
+
+def kmer_coverage(seqs: Sequence[np.ndarray], index: KmerIndex, wave: bool = False):
+    """The coverage of every k-mer of every sequence (base-code arrays, any lengths): a list of uint8 arrays, sequence i's of
+    max(0, len - K + 1) entries, 0 for a k-mer that is not in the set."""
+    words, word_off, kmer_base = pack_seqs_ragged(seqs, index.K)
+    n_k = int(kmer_base[-1])
+    if index.device < 0:
+        cnt = index.query_ragged(words, word_off, kmer_base, len(seqs), n_k)
+    else:
+        t, dev = index.torch, f"cuda:{index.device}"
+        up = lambda a: t.from_numpy(a.view(np.int64)).to(dev)
+        cnt = index.query_ragged(up(words), up(word_off), up(kmer_base), len(seqs), n_k, wave=wave).cpu().numpy().view(np.uint64)
+    cov = ((cnt >> np.uint64(24)) & np.uint64(0xff)).astype(np.uint8)
+    return [cov[int(kmer_base[i]):int(kmer_base[i + 1])] for i in range(len(seqs))]

@@ -1,0 +1,115 @@
+// kindex.hpp -- the k-mer index: a lookup table over the distinct k-mers pass 1 counted, asked with batches of sequences (pg_kindex_*,
+// include/soapdenovo2_amd.h section 3).  The reference has no such operator on its own; its multi-k step looks k-mers of reads up in a
+// finished set the same way (contig -m: iterate.c, kmerhash.c).
+//
+// The table is map_index.hpp's: map_table_slots(n_records) slots (a power of two, at most half full, at least 1024), a slot = NW key
+// words | value | state, home slot map_home, linear probing.  The value is the record's counter word as the ABI defines it (low 32 bit
+// word A = l_links | covs << 24, high 32 bit word B); a stored record has coverage >= 1, so a value of 0 means "not in the set" and
+// nothing else.  pg_finalize's -d filter does not take a k-mer out of the export array: it sets the record's `deleted` bit (thread_delow,
+// prlHashReads.c:953-996; B_DELETED, kmer.hpp).  Such a record is not stored (kidx_stored), so a filtered k-mer reads as 0 too.
+// State: 0 empty, 1 claimed (key being written), 2 published; the keys of the records are distinct by contract, and a
+// build that meets a key twice fails.  The build side stays with each engine (kindex_kernels.hip: a CAS protocol, kindex_host.cpp: a
+// serial insert); the read side -- kidx_find (map_index.hpp), kidx_stretch and the per-sequence summary below -- is one piece of code
+// for the two query kernels and the host twin.
+//
+// A batch of sequences is laid out as pg_count_reads' batches are: pg_pack_read words, either all of uniform_len bases (sequence r at
+// word r * pg_packed_words(uniform_len)) or with d_word_off[n] + d_kmer_base[n + 1].  A sequence of len bases has max(0, len - K + 1)
+// k-mers: one of exactly K bases has one (the "K + 1" rule is pregraph's reader's, not the query's).  Behind the last sequence NW + 1
+// words (3 in the 63-mer build, 5 in the 127-mer one) must be readable: read_kmer<NW> loads NW + 1 words from the one that holds the
+// k-mer's first base on.  A sequence without k-mers is never read.
+#pragma once
+#include <stdint.h>
+#include <vector>
+
+#include "map_index.hpp"
+
+struct pg_kindex;
+
+namespace pg {
+
+constexpr uint64_t KIDX_EMPTY = MAP_EMPTY, KIDX_CLAIMED = MAP_CLAIMED, KIDX_FULL = MAP_ONCE;   // (map_probe tells empty from not empty only)
+constexpr int KIDX_SUMMARY_WORDS = 4;
+
+PG_HD uint32_t kidx_coverage(uint64_t cnt) { return (uint32_t)(cnt >> 24) & 0xffu; }
+// a record with this counter word goes into the table: every one but those the -d filter deleted
+PG_HD bool kidx_stored(uint64_t cnt) { return ((uint32_t)(cnt >> 32) & B_DELETED) == 0; }
+
+// What a sequence's k-mers add up to: k-mers present, the sum of their coverage, the least coverage among them and the first k-mer
+// that is absent.  Sums and minima: the order the k-mers arrive in, and how they are split over lanes, changes nothing
+struct KidxSummary {
+    uint64_t present, cov_sum;
+    uint32_t cov_min;              // over the present k-mers; KIDX_NO_MIN while there is none
+    uint32_t first_absent;         // KIDX_NO_ABSENT while every k-mer was present
+};
+constexpr uint32_t KIDX_NO_MIN = 0xFFFFFFFFu, KIDX_NO_ABSENT = 0xFFFFFFFFu;
+
+PG_HD KidxSummary kidx_summary_none() { return KidxSummary{0, 0, KIDX_NO_MIN, KIDX_NO_ABSENT}; }
+
+PG_HD void kidx_summary_add(KidxSummary& s, uint64_t cnt, int j) {
+    if (cnt) {
+        const uint32_t c = kidx_coverage(cnt);
+        s.present++;
+        s.cov_sum += c;
+        s.cov_min = c < s.cov_min ? c : s.cov_min;
+    } else
+        s.first_absent = (uint32_t)j < s.first_absent ? (uint32_t)j : s.first_absent;
+}
+
+PG_HD void kidx_summary_merge(KidxSummary& s, const KidxSummary& o) {
+    s.present += o.present;
+    s.cov_sum += o.cov_sum;
+    s.cov_min = o.cov_min < s.cov_min ? o.cov_min : s.cov_min;
+    s.first_absent = o.first_absent < s.first_absent ? o.first_absent : s.first_absent;
+}
+
+// the four words of a sequence of nk k-mers: present, coverage sum, least coverage (0 when none is present), first absent (nk when none is)
+PG_HD void kidx_summary_store(const KidxSummary& s, int nk, uint64_t* out4) {
+    out4[0] = s.present;
+    out4[1] = s.cov_sum;
+    out4[2] = s.cov_min == KIDX_NO_MIN ? 0 : s.cov_min;
+    out4[3] = s.first_absent == KIDX_NO_ABSENT ? (uint64_t)nk : s.first_absent;
+}
+
+// k-mers j0 .. j1 - 1 of the packed sequence rd: roll, canonicalise, probe (map_roll + kidx_find, map_index.hpp); out[j] = the counter
+// word or 0 (out may be null), and every answer goes into s
+template <int NW>
+PG_HD void kidx_stretch(const uint64_t* rd, int j0, int j1, int K, const uint64_t* tab, uint64_t mask, uint64_t* out, KidxSummary& s) {
+    map_roll<NW>(rd, j0, j1, K, [&](const Kmer<NW>& ck, bool, int j) {
+        const uint64_t cnt = kidx_find<NW>(tab, mask, ck);
+        if (out) out[j] = cnt;
+        kidx_summary_add(s, cnt, j);
+    });
+}
+
+// sequence r of a batch: its words, its k-mers and where its answers go (uniform_len != 0: word_off / kmer_base are not read)
+struct KidxSeq {
+    const uint64_t* rd;
+    uint64_t base;
+    int nk;
+};
+PG_HD KidxSeq kidx_seq(const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint32_t uniform_len, int K, uint64_t r) {
+    if (uniform_len) {
+        const int nk = (int)uniform_len >= K ? (int)uniform_len - K + 1 : 0;
+        return KidxSeq{packed + r * (uint64_t)((uniform_len + 31) / 32), r * (uint64_t)nk, nk};
+    }
+    return KidxSeq{packed + word_off[r], kmer_base[r], (int)(kmer_base[r + 1] - kmer_base[r])};
+}
+
+inline uint64_t kidx_table_bytes(uint64_t n_records, int nw) { return map_table_slots(n_records) * (uint64_t)(nw + 2) * sizeof(uint64_t); }
+
+// the device engine (kindex_kernels.hip); the table is cut from the arena of ix->device.  PG_OK or a PG_E* code with pg_set_error done
+int kidx_device_build(::pg_kindex* ix, const uint64_t* d_records, uint64_t n_records, void* stream);
+int kidx_device_query(::pg_kindex* ix, const uint64_t* d_packed, const uint64_t* d_word_off, const uint64_t* d_kmer_base, uint64_t n_seqs,
+                      uint32_t uniform_len, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream);
+void kidx_device_free(::pg_kindex* ix);
+
+}  // namespace pg
+
+struct pg_kindex {
+    int device = -1;               // -1: the host twin
+    int K = 0, nw = 2;
+    uint64_t keys = 0, slots = 0;   // the records the table was made for (the deleted ones among them are not stored), its slots
+    uint64_t* d_tab = nullptr;     // device: slots * (nw + 2) words of the arena
+    uint32_t* d_flags = nullptr;   // device: the build's flags (KIDX_FLAG_*)
+    std::vector<uint64_t> tab;     // host twin
+};

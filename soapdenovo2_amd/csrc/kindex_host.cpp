@@ -1,0 +1,125 @@
+// kindex_host.cpp -- the k-mer index's C ABI (pg_kindex_*, include/soapdenovo2_amd.h section 3) and its host twin (device = -1): the same
+// table built by a serial insert, the same lookups and summary (kindex.hpp: kidx_stretch, KidxSummary) over host memory.  What the CPU
+// tests run, and the device path's yardstick.
+#include <string>
+
+#include "../../include/soapdenovo2_amd.h"
+#include "kindex.hpp"
+
+void pg_set_error(const std::string& s);
+
+namespace pg {
+namespace {
+
+const char* kidx_code_name(int rc) {
+    switch (rc) {
+        case PG_EINVAL: return "PG_EINVAL";
+        case PG_ENODEV: return "PG_ENODEV";
+        case PG_ENOMEM: return "PG_ENOMEM";
+        case PG_ESTATE: return "PG_ESTATE";
+        case PG_ESPIN: return "PG_ESPIN";
+    }
+    return "PG_E?";
+}
+
+// a build that returns null says which code it failed with at the end of pg_last_error's message
+pg_kindex* kidx_build_failed(pg_kindex* ix, int rc) {
+    if (ix) {
+        if (ix->device >= 0) kidx_device_free(ix);
+        delete ix;
+    }
+    pg_set_error(std::string(pg_last_error()) + " (" + kidx_code_name(rc) + ")");
+    return nullptr;
+}
+
+template <int NW>
+int kidx_host_build(pg_kindex* ix, const uint64_t* records, uint64_t n_records) {
+    constexpr int SW = map_slot_words<NW>();
+    ix->keys = n_records;
+    ix->slots = map_table_slots(n_records);
+    const uint64_t mask = ix->slots - 1;
+    ix->tab.assign(ix->slots * SW, 0);
+    for (uint64_t i = 0; i < n_records; i++) {
+        const uint64_t* rec = records + i * (NW + 2);
+        if (!kidx_stored(rec[NW])) continue;
+        Kmer<NW> k;
+        for (int q = 0; q < NW; q++) k.w[q] = rec[q];
+        for (uint64_t e = map_home<NW>(k, mask);; e = (e + 1) & mask) {
+            uint64_t* sl = ix->tab.data() + e * SW;
+            if (sl[NW + 1] == KIDX_EMPTY) {
+                for (int q = 0; q < NW; q++) sl[q] = k.w[q];
+                sl[NW] = rec[NW];
+                sl[NW + 1] = KIDX_FULL;
+                break;
+            }
+            bool eq = true;
+            for (int q = 0; q < NW; q++) eq = eq && sl[q] == k.w[q];
+            if (eq) { pg_set_error("k-mer index: duplicate key in records"); return PG_EINVAL; }
+        }
+    }
+    return PG_OK;
+}
+
+template <int NW>
+void kidx_host_query(const pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
+                     uint32_t uniform_len, uint64_t* out, uint64_t* summary) {
+    for (uint64_t r = 0; r < n_seqs; r++) {
+        const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, ix->K, r);
+        KidxSummary s = kidx_summary_none();
+        kidx_stretch<NW>(q.rd, 0, q.nk, ix->K, ix->tab.data(), ix->slots - 1, out ? out + q.base : nullptr, s);
+        if (summary) kidx_summary_store(s, q.nk, summary + r * KIDX_SUMMARY_WORDS);
+    }
+}
+
+}  // namespace
+}  // namespace pg
+
+extern "C" pg_kindex* pg_kindex_build(int device, int K, int mer127, const uint64_t* records, uint64_t n_records, void* stream) {
+    const int maxK = mer127 ? 127 : 63;
+    if (K < 13 || K > maxK || (K & 1) == 0) {
+        pg_set_error("pg_kindex_build: K must be odd and within 13.." + std::to_string(maxK));
+        return pg::kidx_build_failed(nullptr, PG_EINVAL);
+    }
+    if (device < -1 || (!records && n_records)) { pg_set_error("pg_kindex_build: bad device or null records"); return pg::kidx_build_failed(nullptr, PG_EINVAL); }
+    pg_kindex* ix = new pg_kindex();
+    ix->device = device;
+    ix->K = K;
+    ix->nw = mer127 ? 4 : 2;
+    const int rc = device >= 0 ? pg::kidx_device_build(ix, records, n_records, stream)
+                               : mer127 ? pg::kidx_host_build<4>(ix, records, n_records) : pg::kidx_host_build<2>(ix, records, n_records);
+    return rc == PG_OK ? ix : pg::kidx_build_failed(ix, rc);
+}
+
+extern "C" int pg_kindex_query(pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
+                               uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* out_cnt, uint64_t* out_summary, void* stream) {
+    if (!ix) { pg_set_error("pg_kindex_query: null index"); return PG_EINVAL; }
+    if (!out_cnt && !out_summary) { pg_set_error("pg_kindex_query: out_cnt and out_summary are both null"); return PG_EINVAL; }
+    if (n_seqs && !packed) { pg_set_error("pg_kindex_query: null sequence buffer"); return PG_EINVAL; }
+    if (n_seqs && !uniform_len && (!word_off || !kmer_base)) { pg_set_error("pg_kindex_query: a ragged batch needs word_off and kmer_base"); return PG_EINVAL; }
+    if (uniform_len) {
+        if (uniform_len > 0x7FFFFFFFu) { pg_set_error("pg_kindex_query: uniform_len out of range"); return PG_EINVAL; }
+        const uint64_t nk = (int)uniform_len >= ix->K ? (uint64_t)uniform_len - ix->K + 1 : 0;
+        if (n_kmers != n_seqs * nk) { pg_set_error("pg_kindex_query: n_kmers does not match n_seqs * max(0, len - K + 1)"); return PG_EINVAL; }
+    }
+    if (ix->device >= 0) return pg::kidx_device_query(ix, packed, word_off, kmer_base, n_seqs, uniform_len, wave, out_cnt, out_summary, stream);
+    if (ix->nw == 4) pg::kidx_host_query<4>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
+    else pg::kidx_host_query<2>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
+    return PG_OK;
+}
+
+extern "C" int pg_kindex_info(const pg_kindex* ix, uint64_t out[4]) {
+    if (!ix || !out) { pg_set_error("pg_kindex_info: null argument"); return PG_EINVAL; }
+    out[0] = ix->keys;
+    out[1] = ix->slots;
+    out[2] = pg::kidx_table_bytes(ix->keys, ix->nw);
+    out[3] = (uint64_t)(int64_t)ix->device;
+    return PG_OK;
+}
+
+extern "C" void pg_kindex_destroy(pg_kindex* ix) {
+    if (!ix) return;
+    if (ix->device >= 0) pg::kidx_device_free(ix);
+    delete ix;
+}
+
+extern "C" uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127) { return pg::kidx_table_bytes(n_records, mer127 ? 4 : 2); }

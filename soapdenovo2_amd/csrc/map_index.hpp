@@ -1,6 +1,7 @@
 // map_index.hpp -- the contig k-mer index of the `map` stage, its read side (map_find: the probe, map_stretch: roll / canonicalise / probe
 // over a stretch of a read's k-mers, shared by both kernels and the host twin) and the two engines that map reads with it (device:
 // map_kernels.hip, host twin: map_host.cpp).  The build side stays with each engine: a CAS protocol on the device, a serial insert on the host.
+// The probe loop (map_probe) and the roll (map_roll) are also what the k-mer index of kindex.hpp reads its table with (kidx_find).
 //
 // The reference (prlContig2nodes, prlHashCtg.c:345-467) puts every canonical K-mer of every contig of K + 2 bases or more into its k-mer
 // sets: the first put keeps (contig id, position, twin), a second put of the same key marks it deleted (singleKmer, :131-155), and a deleted
@@ -50,27 +51,40 @@ constexpr int MAP_OWNER_SHIFT = 40;
 template <int NW>
 PG_HD uint32_t map_owner(const Kmer<NW>& k, uint32_t n) { return (uint32_t)((map_hash<NW>(k) >> MAP_OWNER_SHIFT) % n); }
 
+// The probe of a finished table, shared by the finds below: the slot that holds canonical key ck, null when the key is not in the table
+template <int NW>
+PG_HD const uint64_t* map_probe(const uint64_t* tab, uint64_t mask, const Kmer<NW>& ck) {
+    constexpr int SW = map_slot_words<NW>();
+    for (uint64_t e = map_home<NW>(ck, mask);; e = (e + 1) & mask) {
+        const uint64_t* sl = tab + e * SW;
+        if (sl[NW + 1] == MAP_EMPTY) return nullptr;
+        bool eq = true;
+#pragma unroll
+        for (int i = 0; i < NW; i++) eq = eq && sl[i] == ck.w[i];
+        if (eq) return sl;
+    }
+}
+
 // The read-side probe over a finished table (searchKmer, prlRead2Ctg.c:233-246): the hit word of canonical key ck, 0 when the key is not
 // there or is deleted.  sm = the read's own strand is the canonical one (the hit word's `smaller` bit)
 template <int NW>
 PG_HD uint64_t map_find(const uint64_t* tab, uint64_t mask, const Kmer<NW>& ck, bool sm) {
-    constexpr int SW = map_slot_words<NW>();
-    for (uint64_t e = map_home<NW>(ck, mask);; e = (e + 1) & mask) {
-        const uint64_t* sl = tab + e * SW;
-        const uint64_t s = sl[NW + 1];
-        if (s == MAP_EMPTY) return 0;
-        bool eq = true;
-#pragma unroll
-        for (int i = 0; i < NW; i++) eq = eq && sl[i] == ck.w[i];
-        if (eq) return s == MAP_DELETED ? 0 : sl[NW] | ((uint64_t)(sm ? 1 : 0) << 32);
-    }
+    const uint64_t* sl = map_probe<NW>(tab, mask, ck);
+    return !sl || sl[NW + 1] == MAP_DELETED ? 0 : sl[NW] | ((uint64_t)(sm ? 1 : 0) << 32);
 }
 
-// k-mers j0 .. j1 - 1 of the packed read rd (chopKmer4read + searchKmer, prlRead2Ctg.c:153-246): roll, canonicalise, and for the keys
-// that own(key) takes, probe; row[j] = the hit word, then on_hit(hit, j).  A key that is not taken leaves row[j] as it is.  Nothing is
-// read when the stretch is empty
-template <int NW, typename Own, typename OnHit>
-PG_HD void map_stretch_if(const uint64_t* rd, int j0, int j1, int K, const uint64_t* tab, uint64_t mask, uint64_t* row, Own own, OnHit on_hit) {
+// Its sibling over the k-mer index of kindex.hpp, whose value is a pass-1 record's counter word: the word as it was stored, 0 when the
+// key is not in the set (a stored word has coverage >= 1 in bits 31:24; no key of that table is ever deleted)
+template <int NW>
+PG_HD uint64_t kidx_find(const uint64_t* tab, uint64_t mask, const Kmer<NW>& ck) {
+    const uint64_t* sl = map_probe<NW>(tab, mask, ck);
+    return sl ? sl[NW] : 0;
+}
+
+// k-mers j0 .. j1 - 1 of the packed read rd (chopKmer4read, prlRead2Ctg.c:153-231): roll, canonicalise, f(canonical key, sm, j) for each.
+// Nothing is read when the stretch is empty; else the NW + 1 words from the one that holds base j0 on, and the bases up to j1 + K - 2
+template <int NW, typename F>
+PG_HD void map_roll(const uint64_t* rd, int j0, int j1, int K, F f) {
     if (j0 >= j1) return;
     const Kmer<NW> filter = kmer_filter<NW>(K);
     Kmer<NW> word = read_kmer<NW>(rd, j0, K, filter);
@@ -78,12 +92,20 @@ PG_HD void map_stretch_if(const uint64_t* rd, int j0, int j1, int K, const uint6
     for (int j = j0; j < j1; j++) {
         if (j > j0) kmer_roll<NW>(word, bal, read_base(rd, j + K - 1), K, filter);
         const bool sm = kmer_less<NW>(word, bal);
-        const Kmer<NW>& ck = sm ? word : bal;
-        if (!own(ck)) continue;
+        f(sm ? word : bal, sm, j);
+    }
+}
+
+// map_roll + searchKmer (prlRead2Ctg.c:233-246) for the keys that own(key) takes: row[j] = the hit word, then on_hit(hit, j).  A key
+// that is not taken leaves row[j] as it is
+template <int NW, typename Own, typename OnHit>
+PG_HD void map_stretch_if(const uint64_t* rd, int j0, int j1, int K, const uint64_t* tab, uint64_t mask, uint64_t* row, Own own, OnHit on_hit) {
+    map_roll<NW>(rd, j0, j1, K, [&](const Kmer<NW>& ck, bool sm, int j) {
+        if (!own(ck)) return;
         const uint64_t hit = map_find<NW>(tab, mask, ck, sm);
         row[j] = hit;
         on_hit(hit, j);
-    }
+    });
 }
 
 // the whole index in one table: every key is probed
