@@ -445,12 +445,31 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       wave = 0: a lane per sequence (read-sized sequences); wave != 0: a wavefront per sequence (contig-sized
  *                       ones); same answers.  Pointers are device memory of the index's device and the call is asynchronous on
  *                       `stream`; for a host-twin index they are host memory, and wave and stream are ignored.
+ *   pg_kindex_correct   substitution errors of one batch of reads corrected against the index (csrc/kcorrect.hpp; the reference has no such
+ *                       stage, its pipeline runs a separate k-mer-spectrum corrector before pregraph).  The batch is laid out as for
+ *                       pg_kindex_query; n_words = its words, the nw + 1 readable ones behind the last read included.  packed_out
+ *                       receives the whole batch (pad bits and tail copied, never interpreted) with the corrected bases written;
+ *                       packed_out == packed corrects in place with the same result, any other overlap is not allowed.  A k-mer is
+ *                       solid when its answer is not 0 and its coverage (bits 31:24) is >= min_cov.  From the first solid k-mer of a
+ *                       read (the anchor) a sweep goes right and then one goes left; at a weak k-mer the base that entered is put on
+ *                       trial: each of the three other bases counts the consecutive solid k-mers it gives, from that k-mer on, among
+ *                       the (at most K) k-mers that hold the base; the best one is written iff it gives min(min_run, that many) or
+ *                       more and beats both others, else the sweep stops there and what was fixed stays.  A weak k-mer met after
+ *                       max_fixes fixes (0..255, shared by the two sweeps) ends the sweep without a trial.
+ *                       out_report[r] (may be null): bits 7:0 fixes made, bit 8 the read has no k-mer, 9 no solid k-mer (both: read
+ *                       unchanged), 10 the right sweep stopped at a rejected trial, 11 the left one did, 12 max_fixes was reached,
+ *                       bits 63:32 the weak k-mers of the read as given.  Which bases changed is packed XOR packed_out.
+ *                       PG_EINVAL: min_cov == 0, min_run == 0, max_fixes > 255, null packed_out.  n_seqs == 0: PG_OK, nothing touched.
+ *                       Device memory of the index's device, asynchronous on `stream`; host memory for a host-twin index.
  *   pg_kindex_info      out[0] keys (the records the table was made for, deleted ones included), [1] slots, [2] bytes of the table, [3] device (-1 as a 64-bit value: the host twin) */
 typedef struct pg_kindex pg_kindex;
 pg_kindex *pg_kindex_build(int device, int K, int mer127, const uint64_t *records, uint64_t n_records, void *stream);
 pg_kindex *pg_kindex_from_ctx(pg_ctx *ctx, void *stream);
 int pg_kindex_query(pg_kindex *ix, const uint64_t *packed, const uint64_t *word_off, const uint64_t *kmer_base, uint64_t n_seqs,
                     uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t *out_cnt, uint64_t *out_summary, void *stream);
+int pg_kindex_correct(pg_kindex *ix, const uint64_t *packed, const uint64_t *word_off, const uint64_t *kmer_base, uint64_t n_seqs,
+                      uint32_t uniform_len, uint64_t n_words, uint32_t min_cov, uint32_t max_fixes, uint32_t min_run,
+                      uint64_t *packed_out, uint64_t *out_report, void *stream);
 int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
 void pg_kindex_destroy(pg_kindex *ix);
 uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */

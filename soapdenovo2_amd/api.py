@@ -175,6 +175,8 @@ def lib() -> C.CDLL:
     L.pg_kindex_from_ctx.restype = C.c_void_p
     L.pg_kindex_from_ctx.argtypes = [C.c_void_p, C.c_void_p]
     L.pg_kindex_query.argtypes = [C.c_void_p, u64p, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u64p, u64p, C.c_void_p]
+    L.pg_kindex_correct.argtypes = [C.c_void_p, u64p, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u64p,
+                                    C.c_void_p]
     L.pg_kindex_info.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_destroy.argtypes = [C.c_void_p]
     L.pg_kindex_destroy.restype = None
@@ -195,7 +197,7 @@ EXPORTED_SYMBOLS = [
     "pg_set_read_len_bound", "pg_graph_add_packed_device_ragged", "pg_expect", "pg_host_plan_memory", "pg_create_planned", "pg_graph_add_packed_device_segments",
     "call_align", "call_align_127mer", "pg_map_reads", "pg_map_hits", "pg_map_long_reads", "pg_map_wave_ids", "pg_map_long_last_stats",
     "pg_map_reads_sharded", "pg_map_hits_sharded", "pg_map_long_reads_sharded", "pg_host_map_owner", "pg_host_map_plan",
-    "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
+    "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
 ]
 
 
@@ -826,6 +828,30 @@ class KmerCounter:
 KINDEX_SUMMARY_FIELDS = ["present", "coverage_sum", "coverage_min", "first_absent"]
 
 
+# The corrector's defaults (arguments of pg_kindex_correct, not constants of the kernel).
+# max_fixes = 8: at a substitution rate of 1 % a read of 100 to 250 bases carries 1 to 2.5 errors on average and more than 8 about once
+# in 10^5 reads; a read that needs more is more likely foreign or chimeric than unlucky, and is better left as it is (flag `limit`).
+# min_run = 4: one solid k-mer is weak evidence at small K (a 4.6 Mb genome holds 14 % of all 13-mers, so a wrong base hits one by chance
+# one time in seven; four in a row by chance need a real path of K + 3 bases), while two errors four or more bases apart are still
+# fixed one after the other -- a run as long as K would leave every read with two errors inside one k-mer uncorrected.  Near a read's
+# end, where fewer than min_run k-mers hold the base, all of them must be solid.
+CORRECT_MAX_FIXES = 8
+CORRECT_MIN_RUN = 4
+CORRECT_FLAGS = {"no_kmers": 8, "no_anchor": 9, "stop_right": 10, "stop_left": 11, "limit": 12}
+
+
+def report_fields(report) -> dict:
+    """The corrector's report words split up: `fixes` (bases written), one boolean array a flag of CORRECT_FLAGS, and `weak` (the weak
+    k-mers of the read as given).  Takes a numpy array or a torch tensor; returns numpy arrays."""
+    if not isinstance(report, np.ndarray):
+        report = report.cpu().numpy()
+    w = np.ascontiguousarray(report).view(np.uint64)
+    out = {"fixes": (w & np.uint64(0xff)).astype(np.int64), "weak": (w >> np.uint64(32)).astype(np.int64)}
+    for name, bit in CORRECT_FLAGS.items():
+        out[name] = (w >> np.uint64(bit)) & np.uint64(1) != 0
+    return out
+
+
 def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
     """pg_host_kindex_bytes: the table an index of n_records k-mers cuts (no GPU)."""
     return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
@@ -907,6 +933,32 @@ class KmerIndex:
         """Sequences of any lengths (pack_seqs_ragged): sequence r starts at word d_word_off[r] and its answers at d_kmer_base[r]."""
         return self._query(d_packed, d_word_off, d_kmer_base, n_seqs, 0, n_kmers, wave, counts, summary)
 
+    def _correct(self, packed, word_off, kmer_base, n_reads, uniform_len, min_cov, max_fixes, min_run, out):
+        n_words = int(packed.size if self.device < 0 else packed.numel())
+        if out is None:
+            out = np.empty_like(packed) if self.device < 0 else self.torch.empty_like(packed)
+        elif int(out.size if self.device < 0 else out.numel()) < n_words:
+            raise PgError("KmerIndex: `out` is shorter than the batch")
+        # (one element at least: an empty array has no address)
+        report = np.zeros(max(n_reads, 1), dtype=np.uint64) if self.device < 0 else \
+            self.torch.zeros(max(n_reads, 1), dtype=self.torch.int64, device=f"cuda:{self.device}")
+        _check(lib().pg_kindex_correct(self.h, self._ptr(packed), self._ptr(word_off), self._ptr(kmer_base), n_reads, uniform_len, n_words, min_cov,
+                                       max_fixes, min_run, self._ptr(out), self._ptr(report), self._stream()), "pg_kindex_correct")
+        return out, report[:n_reads]
+
+    def correct_uniform(self, d_packed, n_reads: int, read_len: int, min_cov: int, max_fixes: int = CORRECT_MAX_FIXES,
+                        min_run: int = CORRECT_MIN_RUN, out=None):
+        """Substitution errors of a batch of reads of read_len bases (pack_reads_uniform; the whole of d_packed is the batch, its
+        readable tail included) corrected against the index (pg_kindex_correct): returns (packed_out, report).  packed_out is a new
+        buffer, or `out` -- which may be d_packed itself: in place, same result.  A k-mer is solid when it is in the index with
+        coverage >= min_cov; report_fields splits the report words.  See CORRECT_MAX_FIXES / CORRECT_MIN_RUN for the defaults."""
+        return self._correct(d_packed, None, None, n_reads, read_len, min_cov, max_fixes, min_run, out)
+
+    def correct_ragged(self, d_packed, d_word_off, d_kmer_base, n_reads: int, min_cov: int, max_fixes: int = CORRECT_MAX_FIXES,
+                       min_run: int = CORRECT_MIN_RUN, out=None):
+        """correct_uniform for reads of any lengths (pack_seqs_ragged); a read shorter than K comes back as it is, flagged."""
+        return self._correct(d_packed, d_word_off, d_kmer_base, n_reads, 0, min_cov, max_fixes, min_run, out)
+
     def info(self) -> dict:
         out = np.zeros(4, dtype=np.uint64)
         _check(lib().pg_kindex_info(self.h, out.ctypes.data), "pg_kindex_info")
@@ -956,3 +1008,25 @@ def kmer_coverage(seqs: Sequence[np.ndarray], index: KmerIndex, wave: bool = Fal
         cnt = index.query_ragged(up(words), up(word_off), up(kmer_base), len(seqs), n_k, wave=wave).cpu().numpy().view(np.uint64)
     cov = ((cnt >> np.uint64(24)) & np.uint64(0xff)).astype(np.uint8)
     return [cov[int(kmer_base[i]):int(kmer_base[i + 1])] for i in range(len(seqs))]
+
+
+def unpack_seq(words: np.ndarray, length: int) -> np.ndarray:
+    """The first `length` base codes of a packed sequence (the inverse of pg_pack_read)."""
+    w = np.asarray(words[:packed_words(length)], dtype=np.uint64)
+    shifts = (62 - 2 * np.arange(32, dtype=np.uint64)).astype(np.uint64)
+    return ((w[:, None] >> shifts[None, :]) & np.uint64(3)).astype(np.uint8).reshape(-1)[:length]
+
+
+def correct_reads(reads: Sequence[np.ndarray], index: KmerIndex, min_cov: int, max_fixes: int = CORRECT_MAX_FIXES,
+                  min_run: int = CORRECT_MIN_RUN):
+    """Substitution errors of reads (base-code arrays, any lengths) corrected against the index: (a list of base-code arrays of the
+    same lengths, the report words as a numpy uint64 array -- see report_fields)."""
+    words, word_off, kmer_base = pack_seqs_ragged(reads, index.K)
+    if index.device < 0:
+        out, report = index.correct_ragged(words, word_off, kmer_base, len(reads), min_cov, max_fixes, min_run)
+    else:
+        t, dev = index.torch, f"cuda:{index.device}"
+        up = lambda a: t.from_numpy(a.view(np.int64)).to(dev)
+        out, report = index.correct_ragged(up(words), up(word_off), up(kmer_base), len(reads), min_cov, max_fixes, min_run)
+        out, report = out.cpu().numpy().view(np.uint64), report.cpu().numpy().view(np.uint64)
+    return [unpack_seq(out[int(word_off[i]):], len(r)) for i, r in enumerate(reads)], report

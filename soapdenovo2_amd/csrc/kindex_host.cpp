@@ -1,9 +1,11 @@
 // kindex_host.cpp -- the k-mer index's C ABI (pg_kindex_*, include/soapdenovo2_amd.h section 3) and its host twin (device = -1): the same
 // table built by a serial insert, the same lookups and summary (kindex.hpp: kidx_stretch, KidxSummary) over host memory.  What the CPU
 // tests run, and the device path's yardstick.
+#include <string.h>
 #include <string>
 
 #include "../../include/soapdenovo2_amd.h"
+#include "kcorrect.hpp"
 #include "kindex.hpp"
 
 void pg_set_error(const std::string& s);
@@ -71,6 +73,18 @@ void kidx_host_query(const pg_kindex* ix, const uint64_t* packed, const uint64_t
     }
 }
 
+// the host twin of kcor_kernel: the copy first, then kcor_read on every read's own words of the output
+template <int NW>
+void kcor_host_correct(const pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
+                       uint32_t uniform_len, uint64_t n_words, const KcorParams& pr, uint64_t* packed_out, uint64_t* report) {
+    if (packed_out != packed) memmove(packed_out, packed, n_words * sizeof(uint64_t));
+    for (uint64_t r = 0; r < n_seqs; r++) {
+        const KidxSeq q = kidx_seq(packed_out, word_off, kmer_base, uniform_len, ix->K, r);
+        const uint64_t rep = kcor_read<NW>(packed_out + (q.rd - packed_out), q.nk, ix->K, ix->tab.data(), ix->slots - 1, pr);
+        if (report) report[r] = rep;
+    }
+}
+
 }  // namespace
 }  // namespace pg
 
@@ -104,6 +118,27 @@ extern "C" int pg_kindex_query(pg_kindex* ix, const uint64_t* packed, const uint
     if (ix->device >= 0) return pg::kidx_device_query(ix, packed, word_off, kmer_base, n_seqs, uniform_len, wave, out_cnt, out_summary, stream);
     if (ix->nw == 4) pg::kidx_host_query<4>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
     else pg::kidx_host_query<2>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
+    return PG_OK;
+}
+
+extern "C" int pg_kindex_correct(pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
+                                 uint32_t uniform_len, uint64_t n_words, uint32_t min_cov, uint32_t max_fixes, uint32_t min_run,
+                                 uint64_t* packed_out, uint64_t* out_report, void* stream) {
+    if (!ix) { pg_set_error("pg_kindex_correct: null index"); return PG_EINVAL; }
+    if (!min_cov || !min_run || max_fixes > pg::KCOR_MAX_FIXES) { pg_set_error("pg_kindex_correct: min_cov and min_run are at least 1, max_fixes at most 255"); return PG_EINVAL; }
+    if (!packed_out) { pg_set_error("pg_kindex_correct: null packed_out"); return PG_EINVAL; }
+    if (!n_seqs) return PG_OK;
+    if (!packed) { pg_set_error("pg_kindex_correct: null read buffer"); return PG_EINVAL; }
+    if (!uniform_len && (!word_off || !kmer_base)) { pg_set_error("pg_kindex_correct: a ragged batch needs word_off and kmer_base"); return PG_EINVAL; }
+    if (uniform_len > 0x7FFFFFFFu) { pg_set_error("pg_kindex_correct: uniform_len out of range"); return PG_EINVAL; }
+    if (uniform_len && n_words < n_seqs * (uint64_t)((uniform_len + 31) / 32) + (uint64_t)ix->nw + 1) {
+        pg_set_error("pg_kindex_correct: n_words is less than the reads' words and the nw + 1 readable words behind them");
+        return PG_EINVAL;
+    }
+    const pg::KcorParams pr{min_cov, max_fixes, min_run};
+    if (ix->device >= 0) return pg::kcor_device_correct(ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_words, pr, packed_out, out_report, stream);
+    if (ix->nw == 4) pg::kcor_host_correct<4>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_words, pr, packed_out, out_report);
+    else pg::kcor_host_correct<2>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_words, pr, packed_out, out_report);
     return PG_OK;
 }
 

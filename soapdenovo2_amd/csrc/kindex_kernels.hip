@@ -14,6 +14,9 @@
 //                           ceil(nk / 64) consecutive k-mers (one read_kmer, then rolling: map_read_wave_kernel's split), the summary
 //                           through a __shfl_xor butterfly, lane 0 writes it.  No LDS, no workgroup barrier: a wave without a sequence
 //                           just ends.
+//   kcor_kernel             a lane per read of a batch that already lies in the output buffer: kcor_read (kcorrect.hpp) on the lane's own
+//                           words, in global memory -- the first pass over the read as given is kidx_query_kernel's walk, and a read
+//                           without a weak k-mer ends there; the lanes of a wave diverge in the trials.
 // Both query kernels wait for one random slot read per k-mer (32 B a slot in the 63-mer build, 48 B in the 127-mer one) of a table that
 // is many times the L2; the roll is arithmetic hidden under it.  Nothing here has been measured.
 #include <hip/hip_runtime.h>
@@ -23,6 +26,7 @@
 #include "../../include/soapdenovo2_amd.h"
 #include "arena.hpp"
 #include "device_ctx.hpp"
+#include "kcorrect.hpp"
 #include "kindex.hpp"
 
 namespace pg {
@@ -128,6 +132,17 @@ __global__ __launch_bounds__(256) void kidx_query_wave_kernel(const uint64_t* __
     if (lane == 0) kidx_summary_store(s, q.nk, summary + r * KIDX_SUMMARY_WORDS);
 }
 
+template <int NW>
+__global__ __launch_bounds__(256) void kcor_kernel(uint64_t* packed_out, const uint64_t* __restrict__ word_off, const uint64_t* __restrict__ kmer_base,
+                                                   uint64_t n_seqs, uint32_t uniform_len, int K, const uint64_t* __restrict__ tab, uint64_t mask,
+                                                   KcorParams pr, uint64_t* __restrict__ report) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_seqs) return;
+    const KidxSeq q = kidx_seq(packed_out, word_off, kmer_base, uniform_len, K, r);
+    const uint64_t rep = kcor_read<NW>(packed_out + (q.rd - packed_out), q.nk, K, tab, mask, pr);
+    if (report) report[r] = rep;
+}
+
 namespace {
 
 // f(std::integral_constant<int, NW>) for an index's flavour
@@ -195,6 +210,24 @@ int kidx_device_query(::pg_kindex* ix, const uint64_t* d_packed, const uint64_t*
                                      ix->d_tab, ix->slots - 1, d_out, d_summary);
         else hipLaunchKernelGGL((kidx_query_kernel<NW>), grid, block, 0, st, d_packed, d_word_off, d_kmer_base, n_seqs, uniform_len, ix->K, ix->d_tab,
                                 ix->slots - 1, d_out, d_summary);
+    });
+    KIDX_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+int kcor_device_correct(::pg_kindex* ix, const uint64_t* d_packed, const uint64_t* d_word_off, const uint64_t* d_kmer_base, uint64_t n_seqs,
+                        uint32_t uniform_len, uint64_t n_words, const KcorParams& pr, uint64_t* d_packed_out, uint64_t* d_report, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    if (!n_seqs) return PG_OK;
+    const uint64_t blocks = (n_seqs + 255) / 256;
+    if (blocks > 0x7FFFFFFFULL) { pg_set_error("k-mer index: batch too large for one launch"); return PG_EINVAL; }
+    // the copy first -- pad bits and the readable tail with it -- then every lane works on its own words of the output
+    if (d_packed_out != d_packed) KIDX_HIP(hipMemcpyAsync(d_packed_out, d_packed, n_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    const dim3 grid((unsigned)blocks), block(256);
+    kidx_with_nw(ix->nw, [&](auto nw) {
+        hipLaunchKernelGGL((kcor_kernel<decltype(nw)::value>), grid, block, 0, st, d_packed_out, d_word_off, d_kmer_base, n_seqs, uniform_len, ix->K,
+                           ix->d_tab, ix->slots - 1, pr, d_report);
     });
     KIDX_HIP(hipGetLastError());
     return PG_OK;
