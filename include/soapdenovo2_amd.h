@@ -556,9 +556,13 @@ int pg_count_reads_sharded(pg_ctx *ctx, pg_comm *comm, const uint64_t *d_packed,
                            uint64_t n_reads, uint32_t uniform_len, uint64_t n_kmers, uint64_t ord_base, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
- * 5. Test hooks.  The device graph stages (csrc/dev_graph.hpp, csrc/dev_tips.hpp) are written once over a backend; these
- *    entry points run the SAME function objects on host threads instead of HIP lanes, so that the CPU-only tests can
- *    compare them with the sequential host stages.  Not a fallback: nothing in the product path calls them.
+ * 5. Test hooks.  The device graph stages (csrc/dev_graph.hpp, csrc/dev_rehash.hpp, csrc/dev_tips.hpp) are written once over a
+ *    backend; the pg_host_emu_* entry points run the SAME function objects on host threads instead of HIP lanes, so that the
+ *    CPU-only tests can compare them with the sequential host stages, and the pg_device_emu_* entry points hand the same test
+ *    inputs to the HIP instantiations the product runs.  Both k-mer-set layouts, the modulus by reciprocal and the append
+ *    primitive are held to the same models on both backends: the inputs and comparisons live in tests/dev_graph_cases.py,
+ *    tests/test_dev_graph_emu.py runs them on the host backend and tests/test_gpu_dev_graph.py on a GPU.  Not a fallback:
+ *    nothing in the product path calls any of them.
  * ------------------------------------------------------------------------------------------------ */
 /* layout of static (-a) k-mer sets, SURVEY.md App. C "K6" (put_kmerset into a table that never grows, newhash.c:353-366,
  * 473-528): records sorted by (set, ordinal), per_set_count[s] of them per set; nodes_out = n_sets * set_size slots of
@@ -586,6 +590,27 @@ int pg_host_emu_clip_tips(const uint64_t *records, uint64_t n_records, const uin
  * the 127-mer build) as the graph stages' lookups and both device layouts compute it: by a precomputed reciprocal of the size
  * instead of the compiler's 64-bit `%` (csrc/graph_lookup.hpp: ModConst, rem128).  keys = n x (mer127 ? 4 : 2) words. */
 int pg_host_emu_home_slots(const uint64_t *keys, uint64_t n, int mer127, uint64_t size, uint64_t *out);
+
+/* The device twins of the hooks above: the host arrays are uploaded to HIP device `device`, the product's own functions run there
+ * (csrc/graph_kernels.hip: p2_layout_rank, p2_layout_rank_growable; a HipBackend launch of home_slot; HipBackend::append_at) and the
+ * result is downloaded.  PG_ENODEV without a usable device.  Every call allocates its device blocks and frees them all: a caller that
+ * calls them in a loop holds a pin on the device's arena around the loop (pg_device_arena_pin).
+ * pg_device_emu_layout_static: pg_host_emu_layout_static's image and return values (1 = unsuited).
+ * pg_device_emu_layout_growable: the node image only (nodes_cap_slots slots of 3 / 5 words, the sets back to back, word 0 of an empty
+ * slot all ones): a record's slot is read off the image.  Two or more sets are laid out side by side on streams of their own, as in
+ * the product. */
+int pg_device_emu_layout_static(int device, const uint64_t *records, const uint64_t *per_set_count, int n_sets, uint64_t set_size,
+                                int mer127, uint64_t *nodes_out);
+int pg_device_emu_layout_growable(int device, const uint64_t *records, uint64_t n_records, const uint64_t *set_last_put, int mer127,
+                                  int n_sets, uint64_t *out_set_size, uint64_t *out_rounds, uint64_t *out_nodes,
+                                  uint64_t nodes_cap_slots);
+int pg_device_emu_home_slots(int device, const uint64_t *keys, uint64_t n, int mer127, uint64_t size, uint64_t *out);
+/* The backend's append primitive (csrc/backend_hip.hpp: be_append_kernel, which has no host twin) with f(i) = flags[i] ?
+ * PG_EMU_APPEND_BASE + i : ~0 over i in [0, n) and room for `cap` entries: list_out[0 .. cap) = what the kernel left in the list,
+ * which was all ones before (entries in any order; everything behind min(cap, hits) stays all ones), *count_out = the counter
+ * (every hit, also those beyond cap).  PG_ESTATE when the kernel wrote behind cap. */
+#define PG_EMU_APPEND_BASE 0x9E3779B900000000ULL
+int pg_device_emu_append(int device, const unsigned char *flags, uint64_t n, uint64_t cap, uint64_t *list_out, uint64_t *count_out);
 
 /* The `map` stage's two operators on caller-owned host arrays, for tests: the contig k-mer index of n_ctg contigs (each of K + 2 bases
  * or more, packed with pg_pack_read, contig i at ctg_words + ctg_off[i], ctg_off[n_ctg] = words in all; its k-mers carry ctg_ids[i])

@@ -169,6 +169,10 @@ def lib() -> C.CDLL:
     L.pg_host_emu_clip_tips.argtypes = [u64p, C.c_uint64, u64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u64p]
     L.pg_host_emu_layout_static.argtypes = [u64p, u64p, C.c_int, C.c_uint64, C.c_int, C.c_int, u64p]
     L.pg_host_emu_home_slots.argtypes = [u64p, C.c_uint64, C.c_int, C.c_uint64, u64p]
+    L.pg_device_emu_layout_static.argtypes = [C.c_int, u64p, u64p, C.c_int, C.c_uint64, C.c_int, u64p]
+    L.pg_device_emu_layout_growable.argtypes = [C.c_int, u64p, C.c_uint64, u64p, C.c_int, C.c_int, u64p, u64p, u64p, C.c_uint64]
+    L.pg_device_emu_home_slots.argtypes = [C.c_int, u64p, C.c_uint64, C.c_int, C.c_uint64, u64p]
+    L.pg_device_emu_append.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, u64p, u64p]
     # the k-mer index (include/soapdenovo2_amd.h, section 3)
     L.pg_kindex_build.restype = C.c_void_p
     L.pg_kindex_build.argtypes = [C.c_int, C.c_int, C.c_int, u64p, C.c_uint64, C.c_void_p]
@@ -198,6 +202,7 @@ EXPORTED_SYMBOLS = [
     "call_align", "call_align_127mer", "pg_map_reads", "pg_map_hits", "pg_map_long_reads", "pg_map_wave_ids", "pg_map_long_last_stats",
     "pg_map_reads_sharded", "pg_map_hits_sharded", "pg_map_long_reads_sharded", "pg_host_map_owner", "pg_host_map_plan",
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
+    "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
 

@@ -512,4 +512,21 @@ int layout_growable_sets(BE& be, const uint64_t* records, const uint64_t* per_se
     return rc;
 }
 
+// What the layout test hooks of both backends (pg_host_emu_layout_growable, pg_device_emu_layout_growable) derive from HOST records
+// sorted by (set, ordinal), nw + 2 words each: the keys of every set, and whether a duplicate put arrived after the set's last new key
+// (set_last_put, may be null, against the last record's ordinal).  false: the records are not sorted by set.
+inline bool growable_counts_of_records(const uint64_t* records, uint64_t n, int nw, const uint64_t* set_last_put, int P, std::vector<uint64_t>& cnt,
+                                       std::vector<unsigned char>& trailing) {
+    const uint64_t rw = (uint64_t)nw + 2;
+    cnt.assign((size_t)P, 0);
+    trailing.assign((size_t)P, 0);
+    uint64_t at = 0;
+    for (int s = 0; s < P; s++) {
+        while (at + cnt[s] < n && (int)(records[(at + cnt[s]) * rw + nw + 1] >> PG_ORD_BITS) == s) cnt[s]++;
+        trailing[s] = cnt[s] && set_last_put && set_last_put[s] > (records[(at + cnt[s] - 1) * rw + nw + 1] & PG_ORD_MASK) + 1;
+        at += cnt[s];
+    }
+    return at == n;
+}
+
 }  // namespace pg

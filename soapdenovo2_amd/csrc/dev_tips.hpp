@@ -26,8 +26,11 @@
 // unchanged); sorting and replaying the arrivals is cheap.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 #include "backend.hpp"
+#include "env.hpp"
 #include "graph_lookup.hpp"
 #include "../../include/soapdenovo2_amd.h"
 
@@ -287,7 +290,10 @@ int tip_scan(BE& be, const SetsView& view, const SetsGeo& geo, int cut_len, bool
         std::vector<uint64_t> pl_slots(NPL, 0), pl_cap(NPL, 0), pl_n(NPL, 0);
         std::vector<unsigned long long*> pl_list(NPL, nullptr), pl_cnt(NPL, nullptr);
         for (int s = 0; s < geo.P; s++) pl_slots[be.place_of_set(s)] += geo.size[s];
-        for (int pl = 0; pl < NPL; pl++) { pl_cap[pl] = pl_slots[pl] / 8 + 65536; pl_cnt[pl] = be.template alloc_at<unsigned long long>(pl, 1); }
+        // (test hook: PG_TIP_LIST_ROOM=n replaces that room, so that inputs of test size are short of it and list a second time)
+        const char* const room_env = pg::env_test("PG_TIP_LIST_ROOM");
+        const uint64_t room_forced = room_env ? (uint64_t)std::max(1LL, atoll(room_env)) : 0;
+        for (int pl = 0; pl < NPL; pl++) { pl_cap[pl] = room_forced ? room_forced : pl_slots[pl] / 8 + 65536; pl_cnt[pl] = be.template alloc_at<unsigned long long>(pl, 1); }
         be.sync();                                                   // what the lead wrote into the sets so far is in place
         for (int attempt = 0; attempt < 2 && !be.error; attempt++) {
             bool short_of_room = false;
@@ -315,7 +321,10 @@ int tip_scan(BE& be, const SetsView& view, const SetsGeo& geo, int cut_len, bool
                 if (pl_n[pl]) continue;
                 unsigned long long got = 0;
                 be.to_host_at(pl, &got, pl_cnt[pl], 1);
-                if (got > pl_cap[pl]) { be.release_at(pl, pl_list[pl]); pl_list[pl] = nullptr; pl_cap[pl] = got; short_of_room = true; }
+                if (got > pl_cap[pl]) {
+                    if (pg::env_user("PG_HOST_VERBOSE")) fprintf(stderr, "tips: %llu dead ends at place %d, room for %llu: dead ends listed again\n", got, pl, (unsigned long long)pl_cap[pl]);
+                    be.release_at(pl, pl_list[pl]); pl_list[pl] = nullptr; pl_cap[pl] = got; short_of_room = true;
+                }
                 else pl_n[pl] = got ? got : ~0ULL;                      // (~0: listed, nothing found)
             }
             if (!short_of_room) break;

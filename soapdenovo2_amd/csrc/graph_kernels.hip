@@ -37,6 +37,7 @@
 #include "extract.hpp"
 #include "kmer.hpp"
 #include "graph_dev.hpp"
+#include "host_graph.hpp"
 #include "graph_lookup.hpp"
 #include "cmd_plan.hpp"
 #include "backend_hip.hpp"
@@ -1498,7 +1499,7 @@ int p2_layout_rank(int device, int nw, int n_own, const uint64_t* d_records, con
 // (sizes_out), and every key in the slot the whole history of in-place rehashes leaves it in (dev_rehash.hpp: layout_growable).
 // The sets lie back to back in one allocation, set i at sizes_out[0] + ... + sizes_out[i - 1] slots.
 int p2_layout_rank_growable(int device, int nw, int n_own, const uint64_t* d_records, const uint64_t* own_counts, const unsigned char* own_trailing,
-                            uint64_t init_size, uint64_t* sizes_out, uint64_t** d_nodes_out, void** alloc_out) {
+                            uint64_t init_size, uint64_t* sizes_out, uint64_t** d_nodes_out, void** alloc_out, uint64_t* rounds_out) {
     *d_nodes_out = nullptr;
     if (alloc_out) *alloc_out = nullptr;
     if (n_own < 1) return PG_OK;
@@ -1585,6 +1586,7 @@ int p2_layout_rank_growable(int device, int nw, int n_own, const uint64_t* d_rec
         fprintf(stderr, "growable sets on device %d: %d set(s), %llu slots in all, %s %.2fs, layout %.2fs (%llu rounds over all sizes, %d set(s) side by side)\n", device, n_own,
                 (unsigned long long)total, block ? "memory taken over from pass 1" : "allocation", t1 - t0, now() - t1, (unsigned long long)r_all, lanes);
     }
+    if (rounds_out) for (int s = 0; s < n_own; s++) rounds_out[s] = rounds[s];
     *d_nodes_out = nodes;
     if (alloc_out) *alloc_out = block ? block : (void*)nodes;
     return PG_OK;
@@ -2812,6 +2814,177 @@ int p2_finish(P2Device* d, P2Result& out) {
     }
     P2_HIP(hipSetDevice(d->device));
     return PG_OK;
+}
+
+// ---- TEST HOOKS ONLY (pg_device_emu_*): the device twins of pg_host_emu_* (host_emu.cpp, host_graph.cpp).  Host arrays go up, the
+// product's own entry points run (p2_layout_rank, p2_layout_rank_growable, HipBackend::launch of home_slot, HipBackend::append_at), the
+// result comes down; tests/test_gpu_dev_graph.py holds them to the models the CPU tests hold the HostBackend to.  Nothing in the product
+// path calls these.
+static int emu_device(int device, const char* who) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { pg_set_error(std::string(who) + ": no HIP device"); return PG_ENODEV; }
+    if (device < 0 || device >= n) { pg_set_error(std::string(who) + ": HIP device " + std::to_string(device) + " does not exist"); return PG_ENODEV; }
+    P2_HIP(hipSetDevice(device));
+    return PG_OK;
+}
+// host words into a fresh device block (*d_out; nullptr for n = 0)
+template <typename T>
+static int emu_upload(const T* src, uint64_t n, T** d_out) {
+    *d_out = nullptr;
+    if (!n) return PG_OK;
+    if (pg::arena_malloc((void**)d_out, n * sizeof(T)) != hipSuccess) { *d_out = nullptr; pg_set_error("test hook: out of device memory"); return PG_ENOMEM; }
+    if (hipMemcpy(*d_out, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)pg::arena_free(*d_out); *d_out = nullptr; pg_set_error("test hook: upload failed"); return PG_ENODEV;
+    }
+    return PG_OK;
+}
+static int emu_download(int device, const uint64_t* d_src, uint64_t n_words, uint64_t* dst) {
+    int rc = n_words ? p2_fetch_words(device, d_src, n_words, dst) : PG_OK;
+    (void)p2_fetch_words(device, nullptr, 0, nullptr);                 // (the caller's array stays page-locked no longer than this call)
+    if (rc) pg_set_error("test hook: download failed");
+    return rc;
+}
+
+extern "C" int pg_device_emu_layout_static(int device, const uint64_t* records, const uint64_t* per_set_count, int n_sets, uint64_t set_size, int mer127,
+                                           uint64_t* nodes_out) {
+    if (!records || !per_set_count || !nodes_out || n_sets < 1 || set_size < 2) { pg_set_error("pg_device_emu_layout_static: bad argument"); return PG_EINVAL; }
+    int rc = emu_device(device, "pg_device_emu_layout_static");
+    if (rc) return rc;
+    pg::ArenaPin pin(device);                                          // (one life of the arena for the call's blocks, not one for every block)
+    const int nw = mer127 ? 4 : 2;
+    uint64_t n = 0;
+    for (int s = 0; s < n_sets; s++) n += per_set_count[s];
+    uint64_t* d_rec = nullptr;
+    if ((rc = emu_upload(records, n * (uint64_t)(nw + 2), &d_rec)) != PG_OK) return rc;
+    uint64_t* nodes = nullptr;
+    void* alloc = nullptr;
+    rc = p2_layout_rank(device, nw, n_sets, d_rec, per_set_count, set_size, &nodes, &alloc);
+    if (rc == PG_OK) {
+        rc = emu_download(device, nodes, (uint64_t)n_sets * set_size * (uint64_t)(nw + 1), nodes_out);
+        pg_device_release_layout(device, alloc);
+    }
+    (void)pg::arena_free(d_rec);
+    return rc;
+}
+
+extern "C" int pg_device_emu_layout_growable(int device, const uint64_t* records, uint64_t n_records, const uint64_t* set_last_put, int mer127, int n_sets,
+                                             uint64_t* out_set_size, uint64_t* out_rounds, uint64_t* out_nodes, uint64_t nodes_cap_slots) {
+    if ((!records && n_records) || !out_nodes || n_sets < 1 || n_sets > P2_MAX_SETS) { pg_set_error("pg_device_emu_layout_growable: bad argument"); return PG_EINVAL; }
+    int rc = emu_device(device, "pg_device_emu_layout_growable");
+    if (rc) return rc;
+    pg::ArenaPin pin(device);                                          // (one life of the arena for the call's blocks, not one for every block)
+    const int nw = mer127 ? 4 : 2;
+    std::vector<uint64_t> cnt;
+    std::vector<unsigned char> trailing;
+    if (!growable_counts_of_records(records, n_records, nw, set_last_put, n_sets, cnt, trailing)) { pg_set_error("records are not sorted by set"); return PG_EINVAL; }
+    uint64_t* d_rec = nullptr;
+    if ((rc = emu_upload(records, n_records * (uint64_t)(nw + 2), &d_rec)) != PG_OK) return rc;
+    std::vector<uint64_t> sizes((size_t)n_sets, 0), rounds((size_t)n_sets, 0);
+    uint64_t* nodes = nullptr;
+    void* alloc = nullptr;
+    rc = p2_layout_rank_growable(device, nw, n_sets, d_rec, cnt.data(), trailing.data(), ref_initial_set_size(0, n_sets, mer127 ? 1 : 0), sizes.data(), &nodes, &alloc,
+                                 rounds.data());
+    if (rc == PG_OK) {
+        uint64_t total = 0;
+        for (int s = 0; s < n_sets; s++) {
+            total += sizes[s];
+            if (out_set_size) out_set_size[s] = sizes[s];
+            if (out_rounds) out_rounds[s] = rounds[s];
+        }
+        if (nodes_cap_slots < total) { pg_set_error("node image too small"); rc = PG_EINVAL; }
+        else rc = emu_download(device, nodes, total * (uint64_t)(nw + 1), out_nodes);
+        pg_device_release_layout(device, alloc);
+    }
+    (void)pg::arena_free(d_rec);
+    return rc;
+}
+
+template <int NW>
+int emu_home_slots_on(HipBackend& be, const uint64_t* d_keys, uint64_t n, uint64_t size, unsigned long long* d_out) {
+    const ModConst mc = make_modconst(size);
+    be.launch(n, [=] PG_LAMBDA(uint64_t i) {
+        Kmer<NW> k;
+#pragma unroll
+        for (int w = 0; w < NW; w++) k.w[w] = d_keys[(uint64_t)NW * i + w];
+        d_out[i] = home_slot<NW>(k, mc);
+    });
+    be.sync();
+    return be.error;
+}
+extern "C" int pg_device_emu_home_slots(int device, const uint64_t* keys, uint64_t n, int mer127, uint64_t size, uint64_t* out) {
+    if (!keys || !out || size < 1 || (size >> 63)) { pg_set_error("pg_device_emu_home_slots: bad argument"); return PG_EINVAL; }
+    int rc = emu_device(device, "pg_device_emu_home_slots");
+    if (rc || !n) return rc;
+    pg::ArenaPin pin(device);                                          // (one life of the arena for the call's blocks, not one for every block)
+    const int nw = mer127 ? 4 : 2;
+    uint64_t* d_keys = nullptr;
+    if ((rc = emu_upload(keys, n * (uint64_t)nw, &d_keys)) != PG_OK) return rc;
+    unsigned long long* d_out = nullptr;
+    hipStream_t st = nullptr;
+    if (pg::arena_malloc((void**)&d_out, n * sizeof(unsigned long long)) != hipSuccess) { d_out = nullptr; pg_set_error("test hook: out of device memory"); rc = PG_ENOMEM; }
+    else if (hipStreamCreate(&st) != hipSuccess) { st = nullptr; pg_set_error("test hook: no stream"); rc = PG_ENODEV; }
+    else {
+        std::string why;
+        {
+            HipBackend be(device, st);
+            rc = mer127 ? emu_home_slots_on<4>(be, d_keys, n, size, d_out) : emu_home_slots_on<2>(be, d_keys, n, size, d_out);
+            why = be.error_text;
+        }
+        if (rc) pg_set_error("pg_device_emu_home_slots: " + why);
+        else rc = emu_download(device, (const uint64_t*)d_out, n, out);
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)pg::arena_free(d_out);
+    (void)pg::arena_free(d_keys);
+    return rc;
+}
+
+int emu_append_on(HipBackend& be, const unsigned char* d_flags, uint64_t n, unsigned long long* d_list, unsigned long long* d_cnt, uint64_t cap) {
+    be.append_at(0, n, [=] PG_LAMBDA(uint64_t i) -> unsigned long long { return d_flags[i] ? PG_EMU_APPEND_BASE + i : ~0ULL; }, d_list, d_cnt, cap);
+    be.sync_places();
+    return be.error;
+}
+extern "C" int pg_device_emu_append(int device, const unsigned char* flags, uint64_t n, uint64_t cap, uint64_t* list_out, uint64_t* count_out) {
+    if ((!flags && n) || (!list_out && cap) || !count_out || n >= ~0ULL - PG_EMU_APPEND_BASE) { pg_set_error("pg_device_emu_append: bad argument"); return PG_EINVAL; }
+    int rc = emu_device(device, "pg_device_emu_append");
+    if (rc) return rc;
+    pg::ArenaPin pin(device);                                          // (one life of the arena for the call's blocks, not one for every block)
+    for (uint64_t i = 0; i < cap; i++) list_out[i] = ~0ULL;
+    *count_out = 0;
+    if (!n) return PG_OK;
+    // the list lies in front of GUARD words the kernel has no business with: a write behind `cap` is an error of this call, not a stray store
+    constexpr uint64_t GUARD = 1024;
+    unsigned char* d_flags = nullptr;
+    if ((rc = emu_upload(flags, n, &d_flags)) != PG_OK) return rc;
+    unsigned long long* d_list = nullptr;                              // [cap + GUARD] list, then [1] counter
+    hipStream_t st = nullptr;
+    std::vector<uint64_t> back;
+    if (pg::arena_malloc((void**)&d_list, (cap + GUARD + 1) * sizeof(unsigned long long)) != hipSuccess) { d_list = nullptr; pg_set_error("test hook: out of device memory"); rc = PG_ENOMEM; }
+    else if (hipStreamCreate(&st) != hipSuccess) { st = nullptr; pg_set_error("test hook: no stream"); rc = PG_ENODEV; }
+    else {
+        std::string why;
+        {
+            HipBackend be(device, st);
+            be.fill(d_list, (size_t)(cap + GUARD), ~0ULL);
+            be.fill(d_list + cap + GUARD, 1, 0ULL);
+            rc = emu_append_on(be, d_flags, n, d_list, d_list + cap + GUARD, cap);
+            why = be.error_text;
+        }
+        if (rc) pg_set_error("pg_device_emu_append: " + why);
+        else {
+            back.resize((size_t)(cap + GUARD + 1));
+            rc = emu_download(device, (const uint64_t*)d_list, cap + GUARD + 1, back.data());
+        }
+    }
+    if (rc == PG_OK) {
+        for (uint64_t i = 0; i < cap; i++) list_out[i] = back[i];
+        *count_out = back[cap + GUARD];
+        for (uint64_t i = cap; i < cap + GUARD; i++) if (back[i] != ~0ULL) { pg_set_error("pg_device_emu_append: the kernel wrote behind cap"); rc = PG_ESTATE; break; }
+    }
+    if (st) (void)hipStreamDestroy(st);
+    (void)pg::arena_free(d_list);
+    (void)pg::arena_free(d_flags);
+    return rc;
 }
 
 }  // namespace pg

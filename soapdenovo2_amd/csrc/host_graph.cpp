@@ -2816,21 +2816,16 @@ template <int NW>
 static int emu_layout_growable(const uint64_t* records, uint64_t n, const uint64_t* set_last_put, int P, int n_threads, uint64_t* out_slot,
                                uint64_t* out_size, uint64_t* out_rounds, uint64_t* out_nodes, uint64_t nodes_cap_slots) {
     using namespace pg;
-    constexpr int RW = NW + 2;
     HostBackend be(n_threads);
     const uint64_t init = ref_initial_set_size(0, P, NW == 4);
-    std::vector<uint64_t> cnt(P, 0), first_slot(P + 1, 0);
-    std::vector<unsigned char> trailing(P, 0);
-    uint64_t at = 0;
+    std::vector<uint64_t> cnt, first_slot(P + 1, 0);
+    std::vector<unsigned char> trailing;
+    if (!growable_counts_of_records(records, n, NW, set_last_put, P, cnt, trailing)) { pg_set_error("records are not sorted by set"); return PG_EINVAL; }
     for (int s = 0; s < P; s++) {
-        while (at + cnt[s] < n && (int)(records[(at + cnt[s]) * RW + NW + 1] >> PG_ORD_BITS) == s) cnt[s]++;
-        trailing[s] = cnt[s] && set_last_put && set_last_put[s] > (records[(at + cnt[s] - 1) * RW + NW + 1] & PG_ORD_MASK) + 1;
         const uint64_t fsize = grow_schedule(cnt[s], trailing[s] != 0, init).back().size;
         if (out_size) out_size[s] = fsize;
         first_slot[s + 1] = first_slot[s] + fsize;
-        at += cnt[s];
     }
-    if (at != n) { pg_set_error("records are not sorted by set"); return PG_EINVAL; }
     if (out_nodes) {
         if (nodes_cap_slots < first_slot[P]) { pg_set_error("node image too small"); return PG_EINVAL; }
         for (uint64_t i = 0; i < first_slot[P]; i++) { out_nodes[i * (NW + 1)] = ~0ULL; for (int w = 1; w <= NW; w++) out_nodes[i * (NW + 1) + w] = 0; }

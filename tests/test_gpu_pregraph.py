@@ -286,6 +286,27 @@ def test_cli_matches_reference_files(golden, tmp_path, name, engine):
         assert md5_file(pre + ".contig") == golden["md5"][t]["contig"], t
 
 
+@pytest.mark.parametrize("name", ["t6k_k31", "d8k_k63"])
+def test_cli_tip_listing_short_of_room_lists_again(golden, tmp_path, name):
+    """The tip stage's first listing of the dead ends has room for slots / 8 + 65536 of them at every place and lists again with the exact room
+    when that was short (csrc/dev_tips.hpp: tip_scan) -- which no input of test size ever is.  PG_TIP_LIST_ROOM=1 leaves room for one: every scan
+    with two dead ends or more counts them all in the first attempt, writes one, and lists a second time.  The files stay the reference's."""
+    c = golden["cases"][name]
+    cfg = case_config(c, str(tmp_path), name)
+    for run in c["runs"]:
+        P, D, a, m = run
+        t = case_tag(name, run)
+        pre = str(tmp_path / t)
+        log = _run_cli(cfg, c["K"], pre, P, D, a, m, extra_env={"PG_TIP_LIST_ROOM": "1", "PG_HOST_VERBOSE": "1"})
+        assert "dead ends listed again" in log, t
+        want = golden["md5"][t]
+        assert md5_file(pre + ".kmerFreq") == want["kmerFreq"], t
+        assert md5_file(pre + ".preGraphBasic") == want["preGraphBasic"], t
+        assert md5_file(pre + ".vertex") == want["vertex"], t
+        assert md5_gz_text(pre + ".edge.gz") == want["edge"], t
+        assert md5_file(pre + ".preArc") == want["preArc"], t
+
+
 @pytest.mark.parametrize("form,says", [("SOAPDENOVO2_AMD_P2_SORT", "sorted by their smallest hashed 16-mer"),
                                        ("SOAPDENOVO2_AMD_P2_PARTITIONED", "through the partition engine"),
                                        ("SOAPDENOVO2_AMD_P2_LOOK", "pass 2: lookup table of")])
