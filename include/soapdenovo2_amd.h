@@ -461,7 +461,38 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       bits 63:32 the weak k-mers of the read as given.  Which bases changed is packed XOR packed_out.
  *                       PG_EINVAL: min_cov == 0, min_run == 0, max_fixes > 255, null packed_out.  n_seqs == 0: PG_OK, nothing touched.
  *                       Device memory of the index's device, asynchronous on `stream`; host memory for a host-twin index.
- *   pg_kindex_info      out[0] keys (the records the table was made for, deleted ones included), [1] slots, [2] bytes of the table, [3] device (-1 as a 64-bit value: the host twin) */
+ *   pg_kindex_info      out[0] keys (the records the table was made for, deleted ones included), [1] slots, [2] bytes of the table, [3] device (-1 as a 64-bit value: the host twin).
+ *                       An index cut over ranks: the totals over its ranks, and the lead's device.
+ *
+ * The index cut over ranks, for a record set whose one table does not fit a card (a table is 2 to 4 times the records' bytes).  Rank i of
+ * n_devices holds the records whose canonical key hashes to it (pg_host_map_owner: bits 40 and up of the hash, modulo n) in a table of its
+ * own, exactly sized, cut from the arena of devices[i]; an ordinal may repeat, rank 0 is the lead, and one process drives every rank.
+ *   pg_kindex_build_sharded      the records as n_parts arrays in export format: parts[p] holds part_records[p] records and lies on
+ *                       device part_device[p], or in host memory when that is -1 -- one array on the lead, a host array larger than a
+ *                       card, or the arrays a sharded pass 1 leaves on its GPUs.  Keys are distinct across all parts.  `stream` is a
+ *                       stream of the lead's device that the device parts are finished on.  A part on a rank's own device is read
+ *                       where it lies, any other reaches the rank in chunks.  Before a table is allocated every rank's is checked against
+ *                       0.85 of its device's free memory: null, (PG_ENOMEM), and the message names the rank, its table's bytes and the
+ *                       fewest ranks that hold the index (pg_host_kindex_plan).  devices all -1: the host twin, n serial tables, host
+ *                       parts only; a list that mixes -1 with ordinals, n_devices outside 1..256, a null part with records: (PG_EINVAL).
+ *                       The other failures are pg_kindex_build's.  n_devices = 1 gives pg_kindex_build's keys, slots and bytes.
+ *   pg_kindex_from_ctx_sharded   pg_kindex_from_ctx over a device list: the context's export array as one device part.
+ *   pg_kindex_query_words        pg_kindex_query with n_words, the words of `packed` (the nw + 1 readable ones included, as in
+ *                       pg_kindex_correct): a rank on another device than the lead's receives a copy of the batch.  Pointers are device
+ *                       memory of the lead's device (host memory for the host twin); results have pg_kindex_query's layout and meaning,
+ *                       and the call is asynchronous on `stream`: every rank probes the k-mers it owns on a stream of its own, and
+ *                       `stream` waits for them, ORs their rows together and takes the summary from the merged rows.  The host waits
+ *                       only where a buffer has to grow past the largest batch met so far.  On an index in one table it is
+ *                       pg_kindex_query.  pg_kindex_query itself returns PG_EINVAL on an index cut over ranks, and pg_kindex_correct
+ *                       PG_ESTATE: its trials are chains of dependent lookups, which merged rows cannot answer.
+ *   pg_kindex_ranks     the ranks of an index cut over ranks; 0: one table (pg_kindex_build, pg_kindex_from_ctx).
+ *   pg_kindex_rank_info pg_kindex_info's four words of one rank: the keys it owns, its slots, its table's bytes, its device.
+ *   pg_kindex_query_times        milliseconds of the last pg_kindex_query_words on a device index cut over ranks, from its events, after
+ *                       waiting for its end: out[0] the slowest rank's probe, [1] the rows' copies and ORs, [2] the summary, [3] all of it.
+ *   pg_host_kindex_plan the device memory a rank takes with n_records cut over n_ranks and batches of batch_kmers k-mers in batch_words
+ *                       words (no GPU): out[0] a rank's table, [1] its slots, [2] the keys it is planned for, [3] the build's chunk buffer,
+ *                       [4] rows, [5] staging, [6] a rank's copy of a batch, [7] peak, [8] budget = 0.85 device_bytes, [9] fits,
+ *                       [10] the whole index as one table, [11] the fewest ranks whose plan fits (0: none up to 256). */
 typedef struct pg_kindex pg_kindex;
 pg_kindex *pg_kindex_build(int device, int K, int mer127, const uint64_t *records, uint64_t n_records, void *stream);
 pg_kindex *pg_kindex_from_ctx(pg_ctx *ctx, void *stream);
@@ -473,6 +504,17 @@ int pg_kindex_correct(pg_kindex *ix, const uint64_t *packed, const uint64_t *wor
 int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
 void pg_kindex_destroy(pg_kindex *ix);
 uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */
+pg_kindex *pg_kindex_build_sharded(const int *devices, int n_devices, int K, int mer127, const uint64_t *const *parts,
+                                   const uint64_t *part_records, const int *part_device, int n_parts, void *stream);
+pg_kindex *pg_kindex_from_ctx_sharded(pg_ctx *ctx, const int *devices, int n_devices, void *stream);
+int pg_kindex_query_words(pg_kindex *ix, const uint64_t *packed, uint64_t n_words, const uint64_t *word_off, const uint64_t *kmer_base,
+                          uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t *out_cnt, uint64_t *out_summary,
+                          void *stream);
+int pg_kindex_ranks(const pg_kindex *ix);
+int pg_kindex_rank_info(const pg_kindex *ix, int rank, uint64_t out[4]);
+int pg_kindex_query_times(pg_kindex *ix, double out[4]);
+int pg_host_kindex_plan(uint64_t n_records, int mer127, int n_ranks, uint64_t batch_kmers, uint64_t batch_words, uint64_t device_bytes,
+                        uint64_t out[12]);
 
 /* ------------------------------------------------------------------------------------------------
  * 4. Multi-GPU pass 1.  The reference hands every k-mer to the set it hashes to through shared memory

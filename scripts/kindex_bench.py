@@ -6,6 +6,13 @@ one launch.  Writes profiles/kindex_query.json: lookups/s of every run next to t
 pass 2, whose slot reads these are.  Needs a GPU; nothing falls back.
 
     python scripts/kindex_bench.py [--reads 10000000] [--out profiles/kindex_query.json]
+
+--ranks N [N ...]: the same reads through the index cut over N ranks (KmerCounter.index(devices=(0,) * N): every rank on this one GPU), in
+the same process and with the same runs, after the single table's.  Writes profiles/kindex_query_sharded.json next to the single-table
+file: per N the seconds of every run, their ratio to the single table's of this run -- the yardstick; every rank rolls every k-mer and
+probes 1/N of them, and the lead adds N - 1 row copies and ORs of 8 B a k-mer, so on one GPU the cut costs time and is for tables that
+do not fit, not for speed -- and the split of the last run into the slowest rank's probe, the merge and the summary from the index's
+own events.
 """
 import argparse
 import json
@@ -27,6 +34,8 @@ def main():
     ap.add_argument("--kmer", type=int, default=31)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kindex_query.json"))
+    ap.add_argument("--ranks", type=int, nargs="+", default=[])
+    ap.add_argument("--out-sharded", default=os.path.join(ROOT, "profiles", "kindex_query_sharded.json"))
     a = ap.parse_args()
     import torch
     from soapdenovo2_amd import api, synth
@@ -45,6 +54,7 @@ def main():
     kc.finalize(0)
     digest = kc.checksum()
     ix = kc.index()
+    cut = {n_ranks: kc.index(devices=(0,) * n_ranks) for n_ranks in a.ranks}
     kc.close()
     info = ix.info()
     runs = {"lane": [], "wave": []}
@@ -69,6 +79,30 @@ def main():
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     json.dump(out, open(a.out, "w"), indent=1)
     print(json.dumps({k: out[k]["median_lookups_per_s"] for k in runs}))
+    if not cut:
+        return
+    sharded = {"workload": out["workload"] + "; the index cut over N ranks, every rank on this GPU", "device": out["device"], "lookups": n_kmers,
+               "single_table_median_seconds": {k: float(np.median(runs[k])) for k in runs}, "ranks": {}}
+    for n_ranks, cx in cut.items():
+        c_runs, split = {"lane": [], "wave": []}, {}
+        for i in range(a.runs + 1):
+            for name, wave in (("lane", False), ("wave", True)):
+                e0.record()
+                summ = cx.query_uniform(packed, n, L, wave=wave, counts=False, summary=True)
+                e1.record()
+                torch.cuda.synchronize()
+                assert int(summ[:, 0].sum()) == n_kmers, "a k-mer of the counted reads is absent"
+                if i:
+                    c_runs[name].append(e0.elapsed_time(e1) * 1e-3)
+                    split[name] = cx.query_times()
+        c_info = cx.info()
+        sharded["ranks"][str(n_ranks)] = {
+            "index": {k: c_info[k] for k in ("keys", "slots", "bytes")}, "keys_of_a_rank": [r["keys"] for r in c_info["ranks"]],
+            **{name: {"seconds": t, "median_seconds": float(np.median(t)), "ratio_to_single_table": float(np.median(t) / np.median(runs[name])),
+                      "last_run_ms": split[name]} for name, t in c_runs.items()}}
+        cx.close()
+    json.dump(sharded, open(a.out_sharded, "w"), indent=1)
+    print(json.dumps({n_ranks: {k: v[k]["ratio_to_single_table"] for k in runs} for n_ranks, v in sharded["ranks"].items()}))
 
 
 if __name__ == "__main__":

@@ -186,6 +186,15 @@ def lib() -> C.CDLL:
     L.pg_kindex_destroy.restype = None
     L.pg_host_kindex_bytes.restype = C.c_uint64
     L.pg_host_kindex_bytes.argtypes = [C.c_uint64, C.c_int]
+    L.pg_kindex_build_sharded.restype = C.c_void_p
+    L.pg_kindex_build_sharded.argtypes = [u64p, C.c_int, C.c_int, C.c_int, u64p, u64p, u64p, C.c_int, C.c_void_p]
+    L.pg_kindex_from_ctx_sharded.restype = C.c_void_p
+    L.pg_kindex_from_ctx_sharded.argtypes = [C.c_void_p, u64p, C.c_int, C.c_void_p]
+    L.pg_kindex_query_words.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u64p, u64p, C.c_void_p]
+    L.pg_kindex_ranks.argtypes = [C.c_void_p]
+    L.pg_kindex_rank_info.argtypes = [C.c_void_p, C.c_int, u64p]
+    L.pg_kindex_query_times.argtypes = [C.c_void_p, u64p]
+    L.pg_host_kindex_plan.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
     _lib = L
     return L
 
@@ -202,6 +211,8 @@ EXPORTED_SYMBOLS = [
     "call_align", "call_align_127mer", "pg_map_reads", "pg_map_hits", "pg_map_long_reads", "pg_map_wave_ids", "pg_map_long_last_stats",
     "pg_map_reads_sharded", "pg_map_hits_sharded", "pg_map_long_reads_sharded", "pg_host_map_owner", "pg_host_map_plan",
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
+    "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
+    "pg_host_kindex_plan",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
@@ -792,13 +803,20 @@ class KmerCounter:
         _check(lib().pg_records_checksum(ptr, n.value, self.nw + 2, out.ctypes.data, self._stream()), "pg_records_checksum")
         return out
 
-    def index(self) -> "KmerIndex":
+    def index(self, devices=None) -> "KmerIndex":
         """The k-mer index of the distinct k-mers, after finalize (pg_kindex_from_ctx): on this counter's device, and its own --
-        the counter may be closed while the index lives."""
-        h = lib().pg_kindex_from_ctx(self.h, self._stream())
+        the counter may be closed while the index lives.  devices = a sequence of ordinals: the index cut over those ranks
+        (pg_kindex_from_ctx_sharded), the first one the lead."""
+        if devices is None:
+            h = lib().pg_kindex_from_ctx(self.h, self._stream())
+            if not h:
+                raise PgError("pg_kindex_from_ctx failed: " + lib().pg_last_error().decode())
+            return KmerIndex(h, self.K, self.mer127, self.device)
+        devs = np.ascontiguousarray(list(devices), dtype=np.int32)
+        h = lib().pg_kindex_from_ctx_sharded(self.h, devs.ctypes.data, len(devs), self._stream())
         if not h:
-            raise PgError("pg_kindex_from_ctx failed: " + lib().pg_last_error().decode())
-        return KmerIndex(h, self.K, self.mer127, self.device)
+            raise PgError("pg_kindex_from_ctx_sharded failed: " + lib().pg_last_error().decode())
+        return KmerIndex(h, self.K, self.mer127, int(devs[0]) if len(devs) else -1)
 
     def export(self, sort: bool = False) -> np.ndarray:
         """(n, nw + 2) uint64 records on the host (key words, cnt, set << 56 | first ordinal); with sort=True in the layout
@@ -862,22 +880,83 @@ def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
     return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
 
 
+KINDEX_PLAN_FIELDS = ["table", "slots", "keys", "chunk", "rows", "staging", "batch_copy", "peak", "budget", "fits", "one_table", "fewest_ranks"]
+
+
+def kindex_plan(n_records: int, mer127: bool = False, n_ranks: int = 1, batch_kmers: int = 10**8, batch_words: int = 10**7,
+                device_bytes: int = 288 * 10**9) -> dict:
+    """pg_host_kindex_plan: the device memory one rank of a k-mer index takes with the index cut over n_ranks (1: one table), whether that
+    fits the budget, and the fewest ranks that would (no GPU)."""
+    out = np.zeros(12, dtype=np.uint64)
+    _check(lib().pg_host_kindex_plan(n_records, 1 if mer127 else 0, n_ranks, batch_kmers, batch_words, device_bytes, out.ctypes.data),
+           "pg_host_kindex_plan")
+    d = {k: int(v) for k, v in zip(KINDEX_PLAN_FIELDS, out)}
+    d["fits"] = bool(d["fits"])
+    return d
+
+
 class KmerIndex:
     """A lookup table over the distinct k-mers of pass 1 (pg_kindex_*): `KmerCounter.index()` after finalize, or
     `KmerIndex.from_records(records, K)`.  On a GPU the batches and the answers are torch tensors of that device; with device = -1
-    (the host twin, no GPU) they are numpy arrays.  An answer is a record's cnt word, 0 for a k-mer that is not in the set."""
+    (the host twin, no GPU) they are numpy arrays.  An answer is a record's cnt word, 0 for a k-mer that is not in the set.
+    An index cut over ranks (`device` a sequence of ordinals, `from_parts`, `KmerCounter.index(devices)`) answers the same queries with
+    the same words; its batches and answers lie on the lead's device, `device`, and it does not correct reads."""
 
     def __init__(self, handle, K: int, mer127: bool, device: int):
         self.h, self.K, self.mer127, self.device = handle, K, mer127, device
         self.nw = 4 if mer127 else 2
+        self.sharded = lib().pg_kindex_ranks(handle) > 0
         if device >= 0:
             import torch
             self.torch = torch
 
     @staticmethod
-    def from_records(records, K: int, mer127: bool = False, device: int = 0) -> "KmerIndex":
+    def from_parts(parts, K: int, mer127: bool = False, devices=(0,)) -> "KmerIndex":
+        """The index cut over the ranks `devices` (pg_kindex_build_sharded; ordinals may repeat, the first is the lead, all -1: the host
+        twin).  parts: a list of (n, nw + 2) record arrays with keys distinct across all of them -- a numpy array is a part in host
+        memory, a torch tensor a part on the tensor's device."""
+        rw = (4 if mer127 else 2) + 2
+        devs = np.ascontiguousarray(list(devices), dtype=np.int32)
+        lead = int(devs[0]) if len(devs) else -1
+        keep, ptrs, counts, where = [], [], [], []
+        for part in parts:
+            if isinstance(part, np.ndarray):
+                a = np.ascontiguousarray(part, dtype=np.uint64).reshape(-1, rw)
+                keep.append(a)
+                ptrs.append(a.ctypes.data if a.shape[0] else 0)
+                counts.append(a.shape[0])
+                where.append(-1)
+            else:
+                t = part.contiguous().view(-1)
+                if not t.is_cuda or t.element_size() != 8:
+                    raise PgError("KmerIndex.from_parts: a tensor part is 64-bit words on a GPU")
+                keep.append(t)
+                ptrs.append(t.data_ptr() if t.numel() else 0)
+                counts.append(t.numel() // rw)
+                where.append(t.device.index)
+        stream = None
+        if lead >= 0 and any(d >= 0 for d in where):
+            import torch
+            if not 0 <= lead < torch.cuda.device_count():
+                raise PgError("KmerIndex.from_parts: HIP device %d does not exist" % lead)
+            for t, d in zip(keep, where):                                     # (the build takes one stream, the lead's)
+                if d >= 0 and d != lead:
+                    torch.cuda.current_stream(d).synchronize()
+            stream = C.c_void_p(torch.cuda.current_stream(lead).cuda_stream)
+        a_ptrs, a_counts, a_where = np.array(ptrs, dtype=np.uint64), np.array(counts, dtype=np.uint64), np.array(where, dtype=np.int32)
+        h = lib().pg_kindex_build_sharded(devs.ctypes.data, len(devs), K, 1 if mer127 else 0, a_ptrs.ctypes.data, a_counts.ctypes.data,
+                                          a_where.ctypes.data, len(ptrs), stream)
+        if not h:
+            raise PgError("pg_kindex_build_sharded failed: " + lib().pg_last_error().decode())
+        return KmerIndex(h, K, mer127, lead)
+
+    @staticmethod
+    def from_records(records, K: int, mer127: bool = False, device=0) -> "KmerIndex":
         """records: (n, nw + 2) records as KmerCounter.export returns them, any order -- a numpy array (copied to `device` for the
-        build, or indexed where it lies by the host twin with device = -1) or a torch tensor on `device`."""
+        build, or indexed where it lies by the host twin with device = -1) or a torch tensor on `device`.  device = a sequence of
+        ordinals: the index cut over those ranks (from_parts), a numpy array as one host part, a tensor as one device part."""
+        if not isinstance(device, (int, np.integer)):
+            return KmerIndex.from_parts([records], K, mer127, device)
         rw = (4 if mer127 else 2) + 2
         keep = None
         if device < 0:
@@ -920,8 +999,13 @@ class KmerIndex:
             t, dev = self.torch, f"cuda:{self.device}"
             out = t.zeros(max(n_kmers, 1), dtype=t.int64, device=dev) if counts else None
             summ = t.zeros((max(n_seqs, 1), 4), dtype=t.int64, device=dev) if summary else None
-        _check(lib().pg_kindex_query(self.h, self._ptr(packed), self._ptr(word_off), self._ptr(kmer_base), n_seqs, uniform_len, n_kmers, int(bool(wave)),
-                                     self._ptr(out), self._ptr(summ), self._stream()), "pg_kindex_query")
+        if self.sharded:                            # (the ranks off the lead's device receive the batch: its extent goes along)
+            n_words = int(packed.size if self.device < 0 else packed.numel()) if packed is not None else 0
+            _check(lib().pg_kindex_query_words(self.h, self._ptr(packed), n_words, self._ptr(word_off), self._ptr(kmer_base), n_seqs, uniform_len,
+                                               n_kmers, int(bool(wave)), self._ptr(out), self._ptr(summ), self._stream()), "pg_kindex_query_words")
+        else:
+            _check(lib().pg_kindex_query(self.h, self._ptr(packed), self._ptr(word_off), self._ptr(kmer_base), n_seqs, uniform_len, n_kmers,
+                                         int(bool(wave)), self._ptr(out), self._ptr(summ), self._stream()), "pg_kindex_query")
         out = out[:n_kmers] if counts else None
         summ = summ[:n_seqs] if summary else None
         return (out, summ) if counts and summary else (out if counts else summ)
@@ -967,7 +1051,20 @@ class KmerIndex:
     def info(self) -> dict:
         out = np.zeros(4, dtype=np.uint64)
         _check(lib().pg_kindex_info(self.h, out.ctypes.data), "pg_kindex_info")
-        return {"keys": int(out[0]), "slots": int(out[1]), "bytes": int(out[2]), "device": int(out.view(np.int64)[3])}
+        fields = lambda o: {"keys": int(o[0]), "slots": int(o[1]), "bytes": int(o[2]), "device": int(o.view(np.int64)[3])}
+        d = fields(out)
+        d["ranks"] = []                             # (one table: its own four words)
+        for i in range(max(1, lib().pg_kindex_ranks(self.h))):
+            one = np.zeros(4, dtype=np.uint64)
+            _check(lib().pg_kindex_rank_info(self.h, i, one.ctypes.data), "pg_kindex_rank_info")
+            d["ranks"].append(fields(one))
+        return d
+
+    def query_times(self) -> dict:
+        """Milliseconds of the last query of a device index cut over ranks, from its events (pg_kindex_query_times; waits for the query)."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(lib().pg_kindex_query_times(self.h, out.ctypes.data), "pg_kindex_query_times")
+        return {"probe": float(out[0]), "merge": float(out[1]), "summary": float(out[2]), "total": float(out[3])}
 
     def close(self) -> None:
         if self.h:

@@ -17,7 +17,16 @@
 // k-mers: one of exactly K bases has one (the "K + 1" rule is pregraph's reader's, not the query's).  Behind the last sequence NW + 1
 // words (3 in the 63-mer build, 5 in the 127-mer one) must be readable: read_kmer<NW> loads NW + 1 words from the one that holds the
 // k-mer's first base on.  A sequence without k-mers is never read.
+//
+// The index cut over ranks (pg_kindex_build_sharded): rank i of n holds the stored records whose canonical key has map_owner(key, n) == i
+// (map_index.hpp: the hash's bits 40 and up, modulo n) in a table of its own -- map_table_slots(owned_i) slots, the same slot format,
+// cut from the arena of devices[i]; owned_i counts the records the rank owns, the deleted ones among them included, so that
+// sum(owned_i) == n_records and a one-rank cut is pg_kindex_build's table.  A rank that owns nothing keeps a zeroed table of the smallest
+// size.  Rank 0 is the lead: a batch and its answers lie on its device.  A key has one owner and 0 means "absent", so the ranks' rows of
+// a batch -- each rank probes the keys it owns into zeroed rows -- OR together into the answers (map_rows_merge_kernel), and the
+// summary is taken from the finished rows.  The host twin is n serial tables with the same cut.
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 #include <vector>
 
@@ -97,11 +106,40 @@ PG_HD KidxSeq kidx_seq(const uint64_t* packed, const uint64_t* word_off, const u
 
 inline uint64_t kidx_table_bytes(uint64_t n_records, int nw) { return map_table_slots(n_records) * (uint64_t)(nw + 2) * sizeof(uint64_t); }
 
+// Records of a chunk: a part that does not lie on a rank's device reaches it through one buffer of this many records, an insert launch
+// a chunk.  2^22 records are 128 MB in the 63-mer build and 192 MB in the 127-mer one: a copy of 2 to 4 ms over a 64 GB/s link or from
+// pinned host memory, against some 10 us to launch it and its kernel, and under a thousandth of a card beside a table of tens of GB.
+// SOAPDENOVO2_AMD_KINDEX_CHUNK_RECORDS (env_test, read at build time) makes it small, so that chunk edges run at test sizes
+constexpr uint64_t KIDX_CHUNK_RECORDS = 1ull << 22;
+uint64_t kidx_chunk_records();
+
+// a rank of an index cut over ranks.  The device engine fills the device half, the host twin `tab`
+struct KidxRank {
+    int device = -1;
+    uint64_t keys = 0, slots = 0;  // the records it owns (deleted ones included), the slots of its table
+    std::vector<uint64_t> tab;     // host twin
+    hipStream_t st = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // its probe of a batch runs from e0 to e1; the caller's stream waits for e1
+    uint64_t* d_tab = nullptr;     // exactly slots * (nw + 2) words of the arena of `device`
+    uint32_t* d_flags = nullptr;   // the build's flags (KIDX_FLAG_*)
+    uint64_t* d_chunk = nullptr;   // the build's chunk buffer; given back when the build ends
+    // the rank's copy of a batch (a rank off the lead's device) and its rows; they grow to the largest batch met
+    uint64_t *d_packed = nullptr, *d_word_off = nullptr, *d_kmer_base = nullptr, *d_rows = nullptr;
+    uint64_t cap_packed = 0, cap_seqs = 0, cap_rows = 0;
+};
+
 // the device engine (kindex_kernels.hip); the table is cut from the arena of ix->device.  PG_OK or a PG_E* code with pg_set_error done
 int kidx_device_build(::pg_kindex* ix, const uint64_t* d_records, uint64_t n_records, void* stream);
 int kidx_device_query(::pg_kindex* ix, const uint64_t* d_packed, const uint64_t* d_word_off, const uint64_t* d_kmer_base, uint64_t n_seqs,
                       uint32_t uniform_len, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream);
 void kidx_device_free(::pg_kindex* ix);
+// the index cut over ix->ranks (their `device` set): part p = part_records[p] records on device part_device[p], or in host memory (-1)
+int kidx_device_build_sharded(::pg_kindex* ix, const uint64_t* const* parts, const uint64_t* part_records, const int* part_device, int n_parts,
+                              void* stream);
+int kidx_device_query_sharded(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words, const uint64_t* d_word_off, const uint64_t* d_kmer_base,
+                              uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream);
+// the last sharded query's milliseconds from its events, after waiting for its end: the slowest rank's probe, the merge, the summary, all of it
+int kidx_device_query_times(::pg_kindex* ix, double out[4]);
 
 }  // namespace pg
 
@@ -112,4 +150,13 @@ struct pg_kindex {
     uint64_t* d_tab = nullptr;     // device: slots * (nw + 2) words of the arena
     uint32_t* d_flags = nullptr;   // device: the build's flags (KIDX_FLAG_*)
     std::vector<uint64_t> tab;     // host twin
+    // An index cut over ranks (pg_kindex_build_sharded): one entry a rank, rank 0 the lead; `device` is then the lead's, keys the sum over
+    // the ranks and slots the sum of their tables', and d_tab / tab stay empty.  Empty: one table, the fields above
+    std::vector<pg::KidxRank> ranks;
+    // the lead's alone: the buffer the other ranks' rows arrive in, and the events of a query on the caller's stream -- its begin, every
+    // rank's probe waited for, merged, its end (which the next query's ranks wait for: the row buffers are reused)
+    uint64_t* d_staging = nullptr;
+    uint64_t cap_staging = 0;
+    hipEvent_t e_begin = nullptr, e_probed = nullptr, e_merged = nullptr, e_end = nullptr;
+    bool queried = false;          // e_end has been recorded
 };

@@ -1,10 +1,13 @@
 // kindex_host.cpp -- the k-mer index's C ABI (pg_kindex_*, include/soapdenovo2_amd.h section 3) and its host twin (device = -1): the same
 // table built by a serial insert, the same lookups and summary (kindex.hpp: kidx_stretch, KidxSummary) over host memory.  What the CPU
-// tests run, and the device path's yardstick.
+// tests run, and the device path's yardstick.  The index cut over ranks (pg_kindex_build_sharded with a device list of -1s) is n such
+// tables with the device's cut: a k-mer is looked up in the table of map_owner(key, n).
+#include <stdlib.h>
 #include <string.h>
 #include <string>
 
 #include "../../include/soapdenovo2_amd.h"
+#include "env.hpp"
 #include "kcorrect.hpp"
 #include "kindex.hpp"
 
@@ -34,32 +37,87 @@ pg_kindex* kidx_build_failed(pg_kindex* ix, int rc) {
     return nullptr;
 }
 
+// the serial insert of a stored record; false: its key is in the table already
+template <int NW>
+bool kidx_host_put(uint64_t* tab, uint64_t mask, const uint64_t* rec) {
+    constexpr int SW = map_slot_words<NW>();
+    Kmer<NW> k;
+    for (int q = 0; q < NW; q++) k.w[q] = rec[q];
+    for (uint64_t e = map_home<NW>(k, mask);; e = (e + 1) & mask) {
+        uint64_t* sl = tab + e * SW;
+        if (sl[NW + 1] == KIDX_EMPTY) {
+            for (int q = 0; q < NW; q++) sl[q] = k.w[q];
+            sl[NW] = rec[NW];
+            sl[NW + 1] = KIDX_FULL;
+            return true;
+        }
+        bool eq = true;
+        for (int q = 0; q < NW; q++) eq = eq && sl[q] == k.w[q];
+        if (eq) return false;
+    }
+}
+
 template <int NW>
 int kidx_host_build(pg_kindex* ix, const uint64_t* records, uint64_t n_records) {
     constexpr int SW = map_slot_words<NW>();
     ix->keys = n_records;
     ix->slots = map_table_slots(n_records);
-    const uint64_t mask = ix->slots - 1;
     ix->tab.assign(ix->slots * SW, 0);
     for (uint64_t i = 0; i < n_records; i++) {
         const uint64_t* rec = records + i * (NW + 2);
         if (!kidx_stored(rec[NW])) continue;
-        Kmer<NW> k;
-        for (int q = 0; q < NW; q++) k.w[q] = rec[q];
-        for (uint64_t e = map_home<NW>(k, mask);; e = (e + 1) & mask) {
-            uint64_t* sl = ix->tab.data() + e * SW;
-            if (sl[NW + 1] == KIDX_EMPTY) {
-                for (int q = 0; q < NW; q++) sl[q] = k.w[q];
-                sl[NW] = rec[NW];
-                sl[NW + 1] = KIDX_FULL;
-                break;
-            }
-            bool eq = true;
-            for (int q = 0; q < NW; q++) eq = eq && sl[q] == k.w[q];
-            if (eq) { pg_set_error("k-mer index: duplicate key in records"); return PG_EINVAL; }
-        }
+        if (!kidx_host_put<NW>(ix->tab.data(), ix->slots - 1, rec)) { pg_set_error("k-mer index: duplicate key in records"); return PG_EINVAL; }
     }
     return PG_OK;
+}
+
+template <int NW>
+uint32_t kidx_record_owner(const uint64_t* rec, uint32_t n) {
+    Kmer<NW> k;
+    for (int q = 0; q < NW; q++) k.w[q] = rec[q];
+    return map_owner<NW>(k, n);
+}
+
+// n serial tables: the owners counted first, every rank's table made for exactly the records it owns, then the inserts
+template <int NW>
+int kidx_host_build_sharded(pg_kindex* ix, const uint64_t* const* parts, const uint64_t* part_records, int n_parts) {
+    constexpr int SW = map_slot_words<NW>();
+    const uint32_t n = (uint32_t)ix->ranks.size();
+    for (int p = 0; p < n_parts; p++)
+        for (uint64_t i = 0; i < part_records[p]; i++) ix->ranks[kidx_record_owner<NW>(parts[p] + i * (NW + 2), n)].keys++;
+    ix->keys = ix->slots = 0;
+    for (KidxRank& r : ix->ranks) {
+        r.slots = map_table_slots(r.keys);
+        r.tab.assign(r.slots * SW, 0);
+        ix->keys += r.keys;
+        ix->slots += r.slots;
+    }
+    for (int p = 0; p < n_parts; p++)
+        for (uint64_t i = 0; i < part_records[p]; i++) {
+            const uint64_t* rec = parts[p] + i * (NW + 2);
+            if (!kidx_stored(rec[NW])) continue;
+            KidxRank& r = ix->ranks[kidx_record_owner<NW>(rec, n)];
+            if (!kidx_host_put<NW>(r.tab.data(), r.slots - 1, rec)) { pg_set_error("k-mer index: duplicate key in records"); return PG_EINVAL; }
+        }
+    return PG_OK;
+}
+
+// kidx_host_query over the ranks' tables: every k-mer asks its owner's
+template <int NW>
+void kidx_host_query_sharded(const pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
+                             uint32_t uniform_len, uint64_t* out, uint64_t* summary) {
+    const uint32_t n = (uint32_t)ix->ranks.size();
+    for (uint64_t r = 0; r < n_seqs; r++) {
+        const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, ix->K, r);
+        KidxSummary s = kidx_summary_none();
+        map_roll<NW>(q.rd, 0, q.nk, ix->K, [&](const Kmer<NW>& ck, bool, int j) {
+            const KidxRank& rk = ix->ranks[map_owner<NW>(ck, n)];
+            const uint64_t cnt = kidx_find<NW>(rk.tab.data(), rk.slots - 1, ck);
+            if (out) out[q.base + j] = cnt;
+            kidx_summary_add(s, cnt, j);
+        });
+        if (summary) kidx_summary_store(s, q.nk, summary + r * KIDX_SUMMARY_WORDS);
+    }
 }
 
 template <int NW>
@@ -86,6 +144,12 @@ void kcor_host_correct(const pg_kindex* ix, const uint64_t* packed, const uint64
 }
 
 }  // namespace
+
+uint64_t kidx_chunk_records() {
+    if (const char* e = env_test("SOAPDENOVO2_AMD_KINDEX_CHUNK_RECORDS")) { const long long v = atoll(e); if (v > 0) return (uint64_t)v; }
+    return KIDX_CHUNK_RECORDS;
+}
+
 }  // namespace pg
 
 extern "C" pg_kindex* pg_kindex_build(int device, int K, int mer127, const uint64_t* records, uint64_t n_records, void* stream) {
@@ -104,17 +168,78 @@ extern "C" pg_kindex* pg_kindex_build(int device, int K, int mer127, const uint6
     return rc == PG_OK ? ix : pg::kidx_build_failed(ix, rc);
 }
 
+extern "C" pg_kindex* pg_kindex_build_sharded(const int* devices, int n_devices, int K, int mer127, const uint64_t* const* parts,
+                                              const uint64_t* part_records, const int* part_device, int n_parts, void* stream) {
+    const auto bad = [](const std::string& why) { pg_set_error("pg_kindex_build_sharded: " + why); return pg::kidx_build_failed(nullptr, PG_EINVAL); };
+    const int maxK = mer127 ? 127 : 63;
+    if (K < 13 || K > maxK || (K & 1) == 0) return bad("K must be odd and within 13.." + std::to_string(maxK));
+    if (!devices || n_devices < 1 || n_devices > pg::DEVICE_LIST_MAX_RANKS) return bad("an index is cut over 1 to " + std::to_string(pg::DEVICE_LIST_MAX_RANKS) + " ranks");
+    if (n_parts < 0 || (n_parts && (!parts || !part_records || !part_device))) return bad("null parts, part_records or part_device");
+    const bool host = devices[0] == -1;
+    for (int i = 0; i < n_devices; i++) {
+        if (devices[i] < -1) return bad("bad device " + std::to_string(devices[i]));
+        if ((devices[i] == -1) != host) return bad("the device list mixes -1 (the host twin) with device ordinals");
+    }
+    for (int p = 0; p < n_parts; p++) {
+        if (!parts[p] && part_records[p]) return bad("part " + std::to_string(p) + " is null and has records");
+        if (part_device[p] < -1) return bad("bad device of part " + std::to_string(p));
+        if (host && part_device[p] != -1) return bad("part " + std::to_string(p) + " lies on a device and the host twin takes host parts only");
+    }
+    pg_kindex* ix = new pg_kindex();
+    ix->device = devices[0];
+    ix->K = K;
+    ix->nw = mer127 ? 4 : 2;
+    ix->ranks.resize((size_t)n_devices);
+    for (int i = 0; i < n_devices; i++) ix->ranks[(size_t)i].device = devices[i];
+    const int rc = !host ? pg::kidx_device_build_sharded(ix, parts, part_records, part_device, n_parts, stream)
+                         : mer127 ? pg::kidx_host_build_sharded<4>(ix, parts, part_records, n_parts) : pg::kidx_host_build_sharded<2>(ix, parts, part_records, n_parts);
+    return rc == PG_OK ? ix : pg::kidx_build_failed(ix, rc);
+}
+
+namespace {
+
+// what pg_kindex_query and pg_kindex_query_words ask of a batch alike
+int kidx_query_args(const char* who, const pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
+                    uint32_t uniform_len, uint64_t n_kmers, const uint64_t* out_cnt, const uint64_t* out_summary) {
+    const std::string w = std::string(who) + ": ";
+    if (!ix) { pg_set_error(w + "null index"); return PG_EINVAL; }
+    if (!out_cnt && !out_summary) { pg_set_error(w + "out_cnt and out_summary are both null"); return PG_EINVAL; }
+    if (n_seqs && !packed) { pg_set_error(w + "null sequence buffer"); return PG_EINVAL; }
+    if (n_seqs && !uniform_len && (!word_off || !kmer_base)) { pg_set_error(w + "a ragged batch needs word_off and kmer_base"); return PG_EINVAL; }
+    if (uniform_len) {
+        if (uniform_len > 0x7FFFFFFFu) { pg_set_error(w + "uniform_len out of range"); return PG_EINVAL; }
+        const uint64_t nk = (int)uniform_len >= ix->K ? (uint64_t)uniform_len - ix->K + 1 : 0;
+        if (n_kmers != n_seqs * nk) { pg_set_error(w + "n_kmers does not match n_seqs * max(0, len - K + 1)"); return PG_EINVAL; }
+    }
+    return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_kindex_query_words(pg_kindex* ix, const uint64_t* packed, uint64_t n_words, const uint64_t* word_off, const uint64_t* kmer_base,
+                                     uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* out_cnt, uint64_t* out_summary,
+                                     void* stream) {
+    if (ix && ix->ranks.empty()) return pg_kindex_query(ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_kmers, wave, out_cnt, out_summary, stream);
+    if (int rc = kidx_query_args("pg_kindex_query_words", ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_kmers, out_cnt, out_summary)) return rc;
+    if (n_seqs && uniform_len && n_words < n_seqs * (uint64_t)((uniform_len + 31) / 32) + (uint64_t)ix->nw + 1) {
+        pg_set_error("pg_kindex_query_words: n_words is less than the sequences' words and the nw + 1 readable words behind them");
+        return PG_EINVAL;
+    }
+    if (ix->device >= 0)
+        return pg::kidx_device_query_sharded(ix, packed, n_words, word_off, kmer_base, n_seqs, uniform_len, n_kmers, wave, out_cnt, out_summary, stream);
+    if (ix->nw == 4) pg::kidx_host_query_sharded<4>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
+    else pg::kidx_host_query_sharded<2>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
+    return PG_OK;
+}
+
 extern "C" int pg_kindex_query(pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
                                uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* out_cnt, uint64_t* out_summary, void* stream) {
     if (!ix) { pg_set_error("pg_kindex_query: null index"); return PG_EINVAL; }
-    if (!out_cnt && !out_summary) { pg_set_error("pg_kindex_query: out_cnt and out_summary are both null"); return PG_EINVAL; }
-    if (n_seqs && !packed) { pg_set_error("pg_kindex_query: null sequence buffer"); return PG_EINVAL; }
-    if (n_seqs && !uniform_len && (!word_off || !kmer_base)) { pg_set_error("pg_kindex_query: a ragged batch needs word_off and kmer_base"); return PG_EINVAL; }
-    if (uniform_len) {
-        if (uniform_len > 0x7FFFFFFFu) { pg_set_error("pg_kindex_query: uniform_len out of range"); return PG_EINVAL; }
-        const uint64_t nk = (int)uniform_len >= ix->K ? (uint64_t)uniform_len - ix->K + 1 : 0;
-        if (n_kmers != n_seqs * nk) { pg_set_error("pg_kindex_query: n_kmers does not match n_seqs * max(0, len - K + 1)"); return PG_EINVAL; }
+    if (!ix->ranks.empty()) {
+        pg_set_error("pg_kindex_query: the index is cut over ranks and a batch has to be copied to them: call pg_kindex_query_words, which takes the batch's words");
+        return PG_EINVAL;
     }
+    if (int rc = kidx_query_args("pg_kindex_query", ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_kmers, out_cnt, out_summary)) return rc;
     if (ix->device >= 0) return pg::kidx_device_query(ix, packed, word_off, kmer_base, n_seqs, uniform_len, wave, out_cnt, out_summary, stream);
     if (ix->nw == 4) pg::kidx_host_query<4>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
     else pg::kidx_host_query<2>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
@@ -125,6 +250,11 @@ extern "C" int pg_kindex_correct(pg_kindex* ix, const uint64_t* packed, const ui
                                  uint32_t uniform_len, uint64_t n_words, uint32_t min_cov, uint32_t max_fixes, uint32_t min_run,
                                  uint64_t* packed_out, uint64_t* out_report, void* stream) {
     if (!ix) { pg_set_error("pg_kindex_correct: null index"); return PG_EINVAL; }
+    if (!ix->ranks.empty()) {
+        pg_set_error("pg_kindex_correct: the index is cut over ranks; a read's trials are chains of dependent lookups, which merged rows cannot answer: "
+                     "correct against an index in one table");
+        return PG_ESTATE;
+    }
     if (!min_cov || !min_run || max_fixes > pg::KCOR_MAX_FIXES) { pg_set_error("pg_kindex_correct: min_cov and min_run are at least 1, max_fixes at most 255"); return PG_EINVAL; }
     if (!packed_out) { pg_set_error("pg_kindex_correct: null packed_out"); return PG_EINVAL; }
     if (!n_seqs) return PG_OK;
@@ -146,9 +276,33 @@ extern "C" int pg_kindex_info(const pg_kindex* ix, uint64_t out[4]) {
     if (!ix || !out) { pg_set_error("pg_kindex_info: null argument"); return PG_EINVAL; }
     out[0] = ix->keys;
     out[1] = ix->slots;
-    out[2] = pg::kidx_table_bytes(ix->keys, ix->nw);
+    out[2] = ix->slots * (uint64_t)(ix->nw + 2) * sizeof(uint64_t);             // (cut over ranks: the sum of their tables)
     out[3] = (uint64_t)(int64_t)ix->device;
     return PG_OK;
+}
+
+extern "C" int pg_kindex_ranks(const pg_kindex* ix) {
+    if (!ix) { pg_set_error("pg_kindex_ranks: null index"); return PG_EINVAL; }
+    return (int)ix->ranks.size();
+}
+
+extern "C" int pg_kindex_rank_info(const pg_kindex* ix, int rank, uint64_t out[4]) {
+    if (!ix || !out) { pg_set_error("pg_kindex_rank_info: null argument"); return PG_EINVAL; }
+    if (ix->ranks.empty() && rank == 0) return pg_kindex_info(ix, out);
+    if (rank < 0 || (size_t)rank >= ix->ranks.size()) { pg_set_error("pg_kindex_rank_info: no such rank"); return PG_EINVAL; }
+    const pg::KidxRank& r = ix->ranks[(size_t)rank];
+    out[0] = r.keys;
+    out[1] = r.slots;
+    out[2] = r.slots * (uint64_t)(ix->nw + 2) * sizeof(uint64_t);
+    out[3] = (uint64_t)(int64_t)r.device;
+    return PG_OK;
+}
+
+extern "C" int pg_kindex_query_times(pg_kindex* ix, double out[4]) {
+    if (!ix || !out) { pg_set_error("pg_kindex_query_times: null argument"); return PG_EINVAL; }
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (ix->ranks.empty() || ix->device < 0) return PG_OK;
+    return pg::kidx_device_query_times(ix, out);
 }
 
 extern "C" void pg_kindex_destroy(pg_kindex* ix) {

@@ -17,15 +17,28 @@
 //   kcor_kernel             a lane per read of a batch that already lies in the output buffer: kcor_read (kcorrect.hpp) on the lane's own
 //                           words, in global memory -- the first pass over the read as given is kidx_query_kernel's walk, and a read
 //                           without a weak k-mer ends there; the lanes of a wave diverge in the trials.
+// The index cut over ranks (kindex.hpp; pg_kindex_build_sharded, pg_kindex_query_words):
+//   kidx_count_owners_kernel   a lane per record of a device part, on the device where the part lies: the owners of all n ranks at once
+//                              into an LDS histogram (n <= 256 bins: 1 KB, zeroed and flushed per workgroup), one global atomicAdd per
+//                              non-zero bin per workgroup.  Deleted records are counted: owned_i sizes the table as pg_kindex_build does.
+//   kidx_build_owned_kernel    kidx_build_kernel for the records rank `me` owns: kidx_insert, its spin cap and its flags as they are.
+//   kidx_probe_owned_kernel    the lane and wave splits of the two query kernels; an owned canonical k-mer's answer goes into the rank's
+//                              zeroed rows, every other word is left as it is.  No summary.
+//   kidx_summary_rows_kernel   a wavefront per sequence, four a workgroup, over the merged rows: lanes stride the row (j = lane, lane + 64,
+//                              ...: coalesced), the query wave kernel's butterfly, lane 0 stores.  Sums and minima: the same words.
+// The merge is map_rows_merge_kernel (map_kernels.hip, through map_rows_merge).
 // Both query kernels wait for one random slot read per k-mer (32 B a slot in the 63-mer build, 48 B in the 127-mer one) of a table that
-// is many times the L2; the roll is arithmetic hidden under it.  Nothing here has been measured.
+// is many times the L2; the roll is arithmetic hidden under it.  The measured times, the cut over ranks included, are in DESIGN.md §10.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/soapdenovo2_amd.h"
 #include "arena.hpp"
 #include "device_ctx.hpp"
+#include "env.hpp"
 #include "kcorrect.hpp"
 #include "kindex.hpp"
 
@@ -143,6 +156,83 @@ __global__ __launch_bounds__(256) void kcor_kernel(uint64_t* packed_out, const u
     if (report) report[r] = rep;
 }
 
+// ---- the index cut over ranks: rank `me` of n keeps the records with map_owner(key, n) == me ----
+template <int NW>
+__device__ __forceinline__ Kmer<NW> kidx_record_key(const uint64_t* rec) {
+    Kmer<NW> k;
+#pragma unroll
+    for (int q = 0; q < NW; q++) k.w[q] = rec[q];
+    return k;
+}
+
+template <int NW>
+__global__ __launch_bounds__(256) void kidx_count_owners_kernel(const uint64_t* __restrict__ records, uint64_t n_records, uint32_t n,
+                                                                unsigned long long* counts) {
+    __shared__ uint32_t bins[DEVICE_LIST_MAX_RANKS];
+    for (uint32_t b = threadIdx.x; b < n; b += blockDim.x) bins[b] = 0;
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_records) atomicAdd(&bins[map_owner<NW>(kidx_record_key<NW>(records + i * (NW + 2)), n)], 1u);
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < n; b += blockDim.x)
+        if (const uint32_t c = bins[b]) atomicAdd(counts + b, (unsigned long long)c);
+}
+
+template <int NW>
+__global__ __launch_bounds__(256) void kidx_build_owned_kernel(const uint64_t* __restrict__ records, uint64_t n_records, uint32_t n, uint32_t me,
+                                                               uint64_t* tab, uint64_t mask, uint32_t* flags) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_records) return;
+    const uint64_t* rec = records + i * (NW + 2);
+    const uint64_t cnt = rec[NW];
+    if (!kidx_stored(cnt)) return;                 // deleted by the -d filter: reads as 0
+    const Kmer<NW> k = kidx_record_key<NW>(rec);
+    if (map_owner<NW>(k, n) != me) return;
+    kidx_insert<NW>(tab, mask, k, cnt, flags);
+}
+
+template <int NW, bool WAVE>
+__global__ __launch_bounds__(256) void kidx_probe_owned_kernel(const uint64_t* __restrict__ packed, const uint64_t* __restrict__ word_off,
+                                                               const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len,
+                                                               int K, uint32_t n, uint32_t me, const uint64_t* __restrict__ tab, uint64_t mask,
+                                                               uint64_t* __restrict__ rows) {
+    const uint64_t r = WAVE ? (uint64_t)blockIdx.x * KIDX_WAVES + (threadIdx.x >> 6) : (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_seqs) return;
+    const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, K, r);
+    int j0 = 0, j1 = q.nk;
+    if (WAVE) {                                    // kidx_query_wave_kernel's split
+        const int per = (q.nk + 63) / 64;
+        const int64_t first = (int64_t)(threadIdx.x & 63) * per;
+        j0 = first < q.nk ? (int)first : q.nk;
+        j1 = first + per < q.nk ? (int)(first + per) : q.nk;
+    }
+    uint64_t* row = rows + q.base;
+    map_roll<NW>(q.rd, j0, j1, K, [&](const Kmer<NW>& ck, bool, int j) {
+        if (map_owner<NW>(ck, n) == me) row[j] = kidx_find<NW>(tab, mask, ck);
+    });
+}
+
+__global__ __launch_bounds__(256) void kidx_summary_rows_kernel(const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len, int K,
+                                                                const uint64_t* __restrict__ rows, uint64_t* __restrict__ summary) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t r = (uint64_t)blockIdx.x * KIDX_WAVES + (threadIdx.x >> 6);
+    if (r >= n_seqs) return;                       // (the whole wave; no workgroup barrier follows)
+    // kidx_seq's base and k-mers; the sequence's words are not wanted here
+    const int nk = uniform_len ? ((int)uniform_len >= K ? (int)uniform_len - K + 1 : 0) : (int)(kmer_base[r + 1] - kmer_base[r]);
+    const uint64_t* row = rows + (uniform_len ? r * (uint64_t)nk : kmer_base[r]);
+    KidxSummary s = kidx_summary_none();
+    for (int64_t j = lane; j < nk; j += 64) kidx_summary_add(s, row[j], (int)j);     // (j + 64 can pass 2^31 where nk is close to it)
+    for (int d = 32; d > 0; d >>= 1) {             // (every lane of the wave is here)
+        KidxSummary o;
+        o.present = __shfl_xor(s.present, d);
+        o.cov_sum = __shfl_xor(s.cov_sum, d);
+        o.cov_min = __shfl_xor(s.cov_min, d);
+        o.first_absent = __shfl_xor(s.first_absent, d);
+        kidx_summary_merge(s, o);
+    }
+    if (lane == 0) kidx_summary_store(s, nk, summary + r * KIDX_SUMMARY_WORDS);
+}
+
 namespace {
 
 // f(std::integral_constant<int, NW>) for an index's flavour
@@ -233,7 +323,372 @@ int kcor_device_correct(::pg_kindex* ix, const uint64_t* d_packed, const uint64_
     return PG_OK;
 }
 
+// ---- the index cut over ranks ----
+namespace {
+
+// a device part's count: the stream it runs on (a rank's where one lies on the part's device, else one of its own) and its n bins
+struct KidxPartCount {
+    int device = -1;
+    hipStream_t st = nullptr;
+    bool own_stream = false;
+    unsigned long long* d_bins = nullptr;
+};
+
+void kidx_sync_ranks(::pg_kindex* ix) {
+    for (KidxRank& r : ix->ranks) {
+        if (!r.st) continue;
+        (void)hipSetDevice(r.device);
+        (void)hipStreamSynchronize(r.st);
+    }
+}
+
+// at least `want` words behind *p (the current device's arena); what was there is given up, not copied
+int kidx_reserve(uint64_t** p, uint64_t* cap, uint64_t want) {
+    if (want <= *cap) return PG_OK;
+    if (*p) (void)arena_free(*p);
+    *p = nullptr;
+    *cap = 0;
+    if (arena_malloc(p, want * sizeof(uint64_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        pg_set_error("k-mer index: out of device memory for a batch buffer of " + std::to_string(want * sizeof(uint64_t)) + " bytes");
+        return PG_ENOMEM;
+    }
+    *cap = want;
+    return PG_OK;
+}
+
+int kidx_launch_blocks(uint64_t n_records, unsigned* blocks) {
+    if ((n_records + 255) / 256 > 0x7FFFFFFFULL) { pg_set_error("k-mer index: too many records for one launch"); return PG_EINVAL; }
+    *blocks = (unsigned)((n_records + 255) / 256);
+    return PG_OK;
+}
+
+// the fewest ranks pg_host_kindex_plan says hold n_records on a device with device_bytes free, a rank's table at most table_cap; 0: none
+int kidx_fewest_ranks(uint64_t n_records, int nw, uint64_t device_bytes, uint64_t table_cap) {
+    uint64_t plan[12];
+    for (int n = 1; n <= DEVICE_LIST_MAX_RANKS; n++)
+        if (pg_host_kindex_plan(n_records, nw == 4, n, 0, 0, device_bytes, plan) == PG_OK && plan[9] && plan[0] <= table_cap) return n;
+    return 0;
+}
+
+// kidx_device_build_sharded's work; the caller owns what the streams read and write meanwhile and cleans up after every way out of here
+int kidx_build_ranks(::pg_kindex* ix, const uint64_t* const* parts, const uint64_t* part_records, const int* part_device, int n_parts,
+                     hipStream_t st, std::vector<KidxPartCount>& pc, std::vector<unsigned long long>& bins, std::vector<uint32_t>& flags) {
+    const uint32_t n = (uint32_t)ix->ranks.size();
+    const int rw = ix->nw + 2;
+    const dim3 block(256);
+    unsigned blocks = 0;
+    KidxRank& lead = ix->ranks[0];
+    for (int p = 0; p < n_parts; p++) {
+        if (part_device[p] >= 0) if (int rc = kidx_set_device(part_device[p])) return rc;
+        if (int rc = kidx_launch_blocks(part_records[p], &blocks)) return rc;
+    }
+    // 1. every rank's stream and events; the caller's stream has made the parts, so every stream that reads one goes behind e_begin
+    for (KidxRank& r : ix->ranks) {
+        if (int rc = kidx_set_device(r.device)) return rc;
+        arena_pin_for_process(r.device);
+        KIDX_HIP(hipStreamCreateWithFlags(&r.st, hipStreamNonBlocking));
+        KIDX_HIP(hipEventCreate(&r.e0));
+        KIDX_HIP(hipEventCreate(&r.e1));
+    }
+    KIDX_HIP(hipSetDevice(lead.device));
+    for (hipEvent_t* e : {&ix->e_begin, &ix->e_probed, &ix->e_merged, &ix->e_end}) KIDX_HIP(hipEventCreate(e));
+    KIDX_HIP(hipEventRecord(ix->e_begin, st));
+    // 2. the owners of every part's records: a device part where it lies, a host part by a plain loop
+    for (int p = 0; p < n_parts; p++) {
+        if (!part_records[p]) continue;
+        unsigned long long* out = bins.data() + (size_t)p * n;
+        if (part_device[p] < 0) {
+            kidx_with_nw(ix->nw, [&](auto nw) {
+                constexpr int NW = decltype(nw)::value;
+                for (uint64_t i = 0; i < part_records[p]; i++) {
+                    Kmer<NW> k;
+                    for (int q = 0; q < NW; q++) k.w[q] = parts[p][i * (NW + 2) + q];
+                    out[map_owner<NW>(k, n)]++;
+                }
+            });
+            continue;
+        }
+        KidxPartCount& c = pc[(size_t)p];
+        c.device = part_device[p];
+        KIDX_HIP(hipSetDevice(c.device));
+        for (KidxRank& r : ix->ranks) if (r.device == c.device && !c.st) c.st = r.st;
+        if (!c.st) {
+            KIDX_HIP(hipStreamCreateWithFlags(&c.st, hipStreamNonBlocking));
+            c.own_stream = true;
+        }
+        if (arena_malloc(&c.d_bins, n * sizeof(unsigned long long)) != hipSuccess) {
+            (void)hipGetLastError();
+            pg_set_error("k-mer index: out of device memory for the owners' counts");
+            return PG_ENOMEM;
+        }
+        KIDX_HIP(hipStreamWaitEvent(c.st, ix->e_begin, 0));
+        KIDX_HIP(hipMemsetAsync(c.d_bins, 0, n * sizeof(unsigned long long), c.st));
+        (void)kidx_launch_blocks(part_records[p], &blocks);
+        kidx_with_nw(ix->nw, [&](auto nw) {
+            hipLaunchKernelGGL((kidx_count_owners_kernel<decltype(nw)::value>), dim3(blocks), block, 0, c.st, parts[p], part_records[p], n, c.d_bins);
+        });
+        KIDX_HIP(hipGetLastError());
+        KIDX_HIP(hipMemcpyAsync(out, c.d_bins, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.st));
+    }
+    // the host's first wait: the counts
+    for (KidxPartCount& c : pc) {
+        if (!c.st) continue;
+        KIDX_HIP(hipSetDevice(c.device));
+        KIDX_HIP(hipStreamSynchronize(c.st));
+    }
+    uint64_t total = 0, n_records = 0;
+    for (int p = 0; p < n_parts; p++) n_records += part_records[p];
+    for (uint32_t i = 0; i < n; i++) {
+        KidxRank& r = ix->ranks[i];
+        r.keys = 0;
+        for (int p = 0; p < n_parts; p++) r.keys += bins[(size_t)p * n + i];
+        r.slots = map_table_slots(r.keys);
+        total += r.keys;
+    }
+    if (total != n_records) {
+        pg_set_error("k-mer index: the ranks own " + std::to_string(total) + " records of " + std::to_string(n_records));
+        return PG_EINVAL;
+    }
+    ix->keys = total;
+    ix->slots = 0;
+    for (const KidxRank& r : ix->ranks) ix->slots += r.slots;
+    // 3. does every rank's table, exactly sized, and its chunk buffer fit its device?  Asked before either is allocated
+    const uint64_t chunk = kidx_chunk_records();
+    const char* hook = env_test("SOAPDENOVO2_AMD_KINDEX_BUDGET_MB");
+    const uint64_t table_cap = hook ? (uint64_t)atoll(hook) << 20 : ~0ull;
+    std::vector<uint64_t> chunk_words(n, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        KidxRank& r = ix->ranks[i];
+        if (r.keys)                                // (a rank that owns nothing reads no part)
+            for (int p = 0; p < n_parts; p++)
+                if (part_device[p] != r.device) chunk_words[i] = std::max(chunk_words[i], std::min(chunk, part_records[p]) * (uint64_t)rw);
+        const uint64_t table = kidx_table_bytes(r.keys, ix->nw), with_chunk = table + chunk_words[i] * sizeof(uint64_t);
+        uint64_t free_b = 0;
+        if (int rc = map_device_free_bytes(r.device, &free_b)) return rc;
+        const uint64_t budget = (uint64_t)((double)free_b * 0.85);
+        if (with_chunk <= budget && table <= table_cap) continue;
+        const int fewest = kidx_fewest_ranks(n_records, ix->nw, free_b, table_cap);
+        std::string msg = "k-mer index: the index does not fit: over " + std::to_string(n) + " rank(s), rank " + std::to_string(i) + "'s table is " +
+                          std::to_string(table) + " bytes (" + std::to_string(with_chunk) + " with its chunk buffer) and the budget of device " +
+                          std::to_string(r.device) + " is " + std::to_string(budget) + " bytes";
+        if (hook) msg += "; SOAPDENOVO2_AMD_KINDEX_BUDGET_MB caps a rank's table at " + std::to_string(table_cap) + " bytes";
+        msg += fewest ? ".  " + std::to_string(fewest) + " ranks would hold it" : ".  No number of ranks up to " + std::to_string(DEVICE_LIST_MAX_RANKS) + " holds it";
+        pg_set_error(msg);
+        return PG_ENOMEM;
+    }
+    // 4. the tables, zeroed, and the records: a part on the rank's own device where it lies, any other through the chunk buffer
+    for (uint32_t i = 0; i < n; i++) {
+        KidxRank& r = ix->ranks[i];
+        KIDX_HIP(hipSetDevice(r.device));
+        const size_t bytes = kidx_table_bytes(r.keys, ix->nw);
+        if (arena_malloc(&r.d_tab, bytes) != hipSuccess || arena_malloc(&r.d_flags, sizeof(uint32_t)) != hipSuccess ||
+            (chunk_words[i] && arena_malloc(&r.d_chunk, chunk_words[i] * sizeof(uint64_t)) != hipSuccess)) {
+            (void)hipGetLastError();
+            pg_set_error("k-mer index: out of device memory (rank " + std::to_string(i) + ": a table of " + std::to_string(r.slots) + " slots, " +
+                         std::to_string(bytes >> 20) + " MiB)");
+            return PG_ENOMEM;
+        }
+        KIDX_HIP(hipMemsetAsync(r.d_tab, 0, bytes, r.st));
+        KIDX_HIP(hipMemsetAsync(r.d_flags, 0, sizeof(uint32_t), r.st));
+        KIDX_HIP(hipStreamWaitEvent(r.st, ix->e_begin, 0));
+        for (int p = 0; p < n_parts && r.keys; p++) {                             // (a rank that owns nothing launches no insert)
+            const bool in_place = part_device[p] == r.device;
+            const uint64_t step = in_place ? part_records[p] : chunk;
+            for (uint64_t at = 0; at < part_records[p]; at += step) {
+                const uint64_t m = std::min(step, part_records[p] - at);
+                const uint64_t* src = parts[p] + at * (uint64_t)rw;
+                if (!in_place) {
+                    const size_t b = m * (uint64_t)rw * sizeof(uint64_t);
+                    if (part_device[p] < 0) KIDX_HIP(hipMemcpyAsync(r.d_chunk, src, b, hipMemcpyHostToDevice, r.st));
+                    else KIDX_HIP(hipMemcpyPeerAsync(r.d_chunk, r.device, src, part_device[p], b, r.st));
+                    src = r.d_chunk;
+                }
+                (void)kidx_launch_blocks(m, &blocks);
+                kidx_with_nw(ix->nw, [&](auto nw) {
+                    hipLaunchKernelGGL((kidx_build_owned_kernel<decltype(nw)::value>), dim3(blocks), block, 0, r.st, src, m, n, i, r.d_tab, r.slots - 1,
+                                       r.d_flags);
+                });
+                KIDX_HIP(hipGetLastError());
+            }
+        }
+        KIDX_HIP(hipMemcpyAsync(&flags[i], r.d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, r.st));
+    }
+    // the host's second wait: every rank's inserts
+    uint32_t any = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        KIDX_HIP(hipSetDevice(ix->ranks[i].device));
+        KIDX_HIP(hipStreamSynchronize(ix->ranks[i].st));
+        any |= flags[i];
+    }
+    if (any & KIDX_FLAG_DUP) { pg_set_error("k-mer index: duplicate key in records"); return PG_EINVAL; }
+    if (any & KIDX_FLAG_SPIN) {
+        pg_set_error("k-mer index: the build gave up on a claimed slot after " + std::to_string(KIDX_SPIN_CAP) +
+                     " trips (the slot's key was never published); the index is not complete");
+        return PG_ESPIN;
+    }
+    return PG_OK;
+}
+
+int kidx_query_ranks(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words, const uint64_t* d_word_off, const uint64_t* d_kmer_base,
+                     uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* d_out, uint64_t* d_summary, hipStream_t st) {
+    const uint32_t n = (uint32_t)ix->ranks.size();
+    KidxRank& lead = ix->ranks[0];
+    const uint64_t blocks = wave ? (n_seqs + KIDX_WAVES - 1) / KIDX_WAVES : (n_seqs + 255) / 256;
+    if (blocks > 0x7FFFFFFFULL) { pg_set_error("k-mer index: batch too large for one launch"); return PG_EINVAL; }
+    const dim3 grid((unsigned)blocks), grid_waves((unsigned)((n_seqs + KIDX_WAVES - 1) / KIDX_WAVES)), block(256);
+    // The buffers grow to the largest batch met.  One that has to grow is given back first, and the previous query may still use it: only
+    // then does the host wait, for that query's end
+    bool grow = n > 1 && n_kmers > ix->cap_staging;
+    for (uint32_t i = 0; i < n; i++) {
+        const KidxRank& r = ix->ranks[i];
+        grow = grow || ((i || !d_out) && n_kmers > r.cap_rows);
+        grow = grow || (r.device != lead.device && (n_words > r.cap_packed || (!uniform_len && n_seqs + 1 > r.cap_seqs)));
+    }
+    if (grow && ix->queried) KIDX_HIP(hipEventSynchronize(ix->e_end));
+    KIDX_HIP(hipSetDevice(lead.device));
+    if (ix->queried) KIDX_HIP(hipStreamWaitEvent(st, ix->e_end, 0));             // (another stream than last time's: the staging buffer is one)
+    KIDX_HIP(hipEventRecord(ix->e_begin, st));
+    // every rank: behind the caller's stream and the previous query's end, the batch (in place on the lead's device), zeroed rows, its probe
+    for (uint32_t i = 0; i < n; i++) {
+        KidxRank& r = ix->ranks[i];
+        KIDX_HIP(hipSetDevice(r.device));
+        const uint64_t *packed = d_packed, *word_off = d_word_off, *kmer_base = d_kmer_base;
+        uint64_t* rows = i == 0 && d_out ? d_out : nullptr;
+        if (!rows) {
+            if (int rc = kidx_reserve(&r.d_rows, &r.cap_rows, std::max<uint64_t>(n_kmers, 1))) return rc;
+            rows = r.d_rows;
+        }
+        KIDX_HIP(hipStreamWaitEvent(r.st, ix->e_begin, 0));
+        if (ix->queried) KIDX_HIP(hipStreamWaitEvent(r.st, ix->e_end, 0));
+        if (r.device != lead.device) {
+            if (int rc = kidx_reserve(&r.d_packed, &r.cap_packed, n_words)) return rc;
+            KIDX_HIP(hipMemcpyPeerAsync(r.d_packed, r.device, d_packed, lead.device, n_words * sizeof(uint64_t), r.st));
+            packed = r.d_packed;
+            if (!uniform_len) {
+                uint64_t cap = r.cap_seqs;
+                if (int rc = kidx_reserve(&r.d_word_off, &cap, n_seqs + 1)) return rc;
+                if (int rc = kidx_reserve(&r.d_kmer_base, &r.cap_seqs, n_seqs + 1)) return rc;
+                KIDX_HIP(hipMemcpyPeerAsync(r.d_word_off, r.device, d_word_off, lead.device, n_seqs * sizeof(uint64_t), r.st));
+                KIDX_HIP(hipMemcpyPeerAsync(r.d_kmer_base, r.device, d_kmer_base, lead.device, (n_seqs + 1) * sizeof(uint64_t), r.st));
+                word_off = r.d_word_off;
+                kmer_base = r.d_kmer_base;
+            }
+        }
+        if (n_kmers) KIDX_HIP(hipMemsetAsync(rows, 0, n_kmers * sizeof(uint64_t), r.st));
+        KIDX_HIP(hipEventRecord(r.e0, r.st));
+        kidx_with_nw(ix->nw, [&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            if (wave) hipLaunchKernelGGL((kidx_probe_owned_kernel<NW, true>), grid, block, 0, r.st, packed, word_off, kmer_base, n_seqs, uniform_len, ix->K,
+                                         n, i, r.d_tab, r.slots - 1, rows);
+            else hipLaunchKernelGGL((kidx_probe_owned_kernel<NW, false>), grid, block, 0, r.st, packed, word_off, kmer_base, n_seqs, uniform_len, ix->K,
+                                    n, i, r.d_tab, r.slots - 1, rows);
+        });
+        KIDX_HIP(hipGetLastError());
+        KIDX_HIP(hipEventRecord(r.e1, r.st));
+    }
+    // the caller's stream: behind every rank's probe, the other ranks' rows one after the other through the staging buffer, the summary
+    KIDX_HIP(hipSetDevice(lead.device));
+    uint64_t* rows = d_out ? d_out : lead.d_rows;
+    if (n > 1 && n_kmers) if (int rc = kidx_reserve(&ix->d_staging, &ix->cap_staging, n_kmers)) return rc;
+    for (uint32_t i = 0; i < n; i++) KIDX_HIP(hipStreamWaitEvent(st, ix->ranks[i].e1, 0));
+    KIDX_HIP(hipEventRecord(ix->e_probed, st));
+    for (uint32_t i = 1; i < n && n_kmers; i++) {
+        const KidxRank& r = ix->ranks[i];
+        if (r.device == lead.device) KIDX_HIP(hipMemcpyAsync(ix->d_staging, r.d_rows, n_kmers * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+        else KIDX_HIP(hipMemcpyPeerAsync(ix->d_staging, lead.device, r.d_rows, r.device, n_kmers * sizeof(uint64_t), st));
+        if (int rc = map_rows_merge(rows, ix->d_staging, n_kmers, st)) return rc;
+    }
+    KIDX_HIP(hipEventRecord(ix->e_merged, st));
+    if (d_summary) {
+        hipLaunchKernelGGL(kidx_summary_rows_kernel, grid_waves, block, 0, st, d_kmer_base, n_seqs, uniform_len, ix->K, rows, d_summary);
+        KIDX_HIP(hipGetLastError());
+    }
+    KIDX_HIP(hipEventRecord(ix->e_end, st));
+    ix->queried = true;
+    return PG_OK;
+}
+
+}  // namespace
+
+// ShardedDeviceMapEngine::build's discipline (map_kernels.hip): however the build ended, a failure on one rank leaves the others' streams
+// copying out of the caller's parts and into the vectors below, so every stream is waited for before those and the buffers go
+int kidx_device_build_sharded(::pg_kindex* ix, const uint64_t* const* parts, const uint64_t* part_records, const int* part_device, int n_parts,
+                              void* stream) {
+    const size_t n = ix->ranks.size();
+    std::vector<KidxPartCount> pc((size_t)n_parts);
+    std::vector<unsigned long long> bins((size_t)n_parts * n, 0);
+    std::vector<uint32_t> flags(n, 0);
+    const int rc = kidx_build_ranks(ix, parts, part_records, part_device, n_parts, (hipStream_t)stream, pc, bins, flags);
+    if (rc) kidx_sync_ranks(ix);
+    for (KidxPartCount& c : pc) {
+        if (c.device < 0) continue;
+        (void)hipSetDevice(c.device);
+        if (rc && c.st) (void)hipStreamSynchronize(c.st);
+        if (c.d_bins) (void)arena_free(c.d_bins);
+        if (c.own_stream) (void)hipStreamDestroy(c.st);
+    }
+    for (KidxRank& r : ix->ranks) {
+        if (!r.d_chunk) continue;
+        (void)hipSetDevice(r.device);
+        (void)arena_free(r.d_chunk);
+        r.d_chunk = nullptr;
+    }
+    return rc;
+}
+
+int kidx_device_query_sharded(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words, const uint64_t* d_word_off, const uint64_t* d_kmer_base,
+                              uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream) {
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    if (!n_seqs) return PG_OK;
+    const int rc = kidx_query_ranks(ix, d_packed, n_words, d_word_off, d_kmer_base, n_seqs, uniform_len, n_kmers, wave, d_out, d_summary, (hipStream_t)stream);
+    if (rc) {                                      // no stream is left reading the caller's batch or writing its results
+        kidx_sync_ranks(ix);
+        (void)hipSetDevice(ix->device);
+        (void)hipStreamSynchronize((hipStream_t)stream);
+    }
+    return rc;
+}
+
+int kidx_device_query_times(::pg_kindex* ix, double out[4]) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!ix->queried) return PG_OK;
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    KIDX_HIP(hipEventSynchronize(ix->e_end));
+    float ms = 0;
+    for (const KidxRank& r : ix->ranks) {
+        KIDX_HIP(hipEventElapsedTime(&ms, r.e0, r.e1));
+        out[0] = std::max(out[0], (double)ms);
+    }
+    KIDX_HIP(hipEventElapsedTime(&ms, ix->e_probed, ix->e_merged));
+    out[1] = ms;
+    KIDX_HIP(hipEventElapsedTime(&ms, ix->e_merged, ix->e_end));
+    out[2] = ms;
+    KIDX_HIP(hipEventElapsedTime(&ms, ix->e_begin, ix->e_end));
+    out[3] = ms;
+    return PG_OK;
+}
+
 void kidx_device_free(::pg_kindex* ix) {
+    if (!ix->ranks.empty()) {                      // every stream first: the lead's copies read the other ranks' rows
+        kidx_sync_ranks(ix);
+        for (KidxRank& r : ix->ranks) {
+            if (!r.st) continue;                   // (a build that failed before this rank began: nothing of it is on a device)
+            (void)hipSetDevice(r.device);
+            for (void* p : {(void*)r.d_tab, (void*)r.d_flags, (void*)r.d_chunk, (void*)r.d_packed, (void*)r.d_word_off, (void*)r.d_kmer_base, (void*)r.d_rows})
+                if (p) (void)arena_free(p);        // (waits for the device like hipFree: no query still reads the table)
+            if (r.st) (void)hipStreamDestroy(r.st);
+            for (hipEvent_t e : {r.e0, r.e1}) if (e) (void)hipEventDestroy(e);
+            r = KidxRank();
+        }
+        (void)hipSetDevice(ix->device);
+        if (ix->d_staging) (void)arena_free(ix->d_staging);
+        for (hipEvent_t e : {ix->e_begin, ix->e_probed, ix->e_merged, ix->e_end}) if (e) (void)hipEventDestroy(e);
+        ix->d_staging = nullptr;
+        ix->e_begin = ix->e_probed = ix->e_merged = ix->e_end = nullptr;
+        ix->ranks.clear();
+        return;
+    }
     if (!ix->d_tab && !ix->d_flags) return;
     (void)hipSetDevice(ix->device);
     if (ix->d_tab) (void)arena_free(ix->d_tab);    // (waits for the device like hipFree: no query still reads the table)
@@ -264,6 +719,41 @@ extern "C" pg_kindex* pg_kindex_from_ctx(pg_ctx* c, void* stream) {
         return nullptr;
     }
     pg_kindex* ix = pg_export(c, d_records, n, &got, stream) == PG_OK ? pg_kindex_build(c->device, c->K, c->NW == 4, d_records, got, stream) : nullptr;
+    (void)pg::arena_free(d_records);
+    return ix;
+}
+
+// pg_kindex_build_sharded for a context's own records: its export array as one device part
+extern "C" pg_kindex* pg_kindex_from_ctx_sharded(pg_ctx* c, const int* devices, int n_devices, void* stream) {
+    if (!c) { pg_set_error("pg_kindex_from_ctx_sharded: null context (PG_EINVAL)"); return nullptr; }
+    if (!c->finalized) { pg_set_error("pg_kindex_from_ctx_sharded: call pg_finalize first (PG_ESTATE)"); return nullptr; }
+    const int part_device = c->device;
+    if (devices && n_devices > 0 && devices[0] != c->device && devices[0] >= 0) {
+        // `stream` is the context's, on its device, and the build takes one of the lead's: the records are finished here instead
+        if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
+            pg_set_error("pg_kindex_from_ctx_sharded: the context's stream could not be waited for (PG_ENODEV)");
+            return nullptr;
+        }
+        stream = nullptr;
+    }
+    if (c->engine == 2) {                          // the export array where it lies
+        const uint64_t* d_records = nullptr;
+        uint64_t n = 0;
+        if (pg_export_peek(c, &d_records, &n) != PG_OK) return nullptr;
+        return pg_kindex_build_sharded(devices, n_devices, c->K, c->NW == 4, &d_records, &n, &part_device, 1, stream);
+    }
+    // the global-set engine keeps no export array: one is made for the build and given back
+    uint64_t n = 0, got = 0;
+    if (pg_distinct(c, &n, stream) != PG_OK) return nullptr;
+    uint64_t* d_records = nullptr;
+    if (pg::arena_malloc(&d_records, (n ? n : 1) * (uint64_t)(c->NW + 2) * sizeof(uint64_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        pg_set_error("pg_kindex_from_ctx_sharded: out of device memory for the records (PG_ENOMEM)");
+        return nullptr;
+    }
+    const uint64_t* part = d_records;
+    pg_kindex* ix = pg_export(c, d_records, n, &got, stream) == PG_OK
+                        ? pg_kindex_build_sharded(devices, n_devices, c->K, c->NW == 4, &part, &got, &part_device, 1, stream) : nullptr;
     (void)pg::arena_free(d_records);
     return ix;
 }

@@ -176,6 +176,9 @@ std::unique_ptr<MapEngine> map_engine_host(int K, int nw);
 // host form: n serial tables
 std::unique_ptr<MapEngine> map_engine_device_sharded(const int* devices, int n, int K, int nw);
 std::unique_ptr<MapEngine> map_engine_host_sharded(int n, int K, int nw);
+// map_rows_merge_kernel on `stream` of the current device: d_rows[i] |= d_part[i] for n_words words (the sharded engine's merge of another
+// rank's rows into the lead's, and the k-mer index's, kindex_kernels.hip); PG_OK or PG_ENODEV
+int map_rows_merge(uint64_t* d_rows, const uint64_t* d_part, uint64_t n_words, void* stream);
 // free memory of a device as the arena sees it (the plan's device_bytes); PG_OK or PG_ENODEV
 int map_device_free_bytes(int device, uint64_t* free_bytes);
 // distinct contig ids of a read that the wave kernel's LDS table holds (more: the read is done in passes)

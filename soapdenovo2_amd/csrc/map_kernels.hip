@@ -712,9 +712,7 @@ private:
             R& r = rk_[i];
             if (r.dev == lead.dev) MAP_HIP(hipMemcpyAsync(staging_.p, r.rows.p, n_k * sizeof(uint64_t), hipMemcpyDeviceToDevice, lead.st));
             else MAP_HIP(hipMemcpyPeerAsync(staging_.p, lead.dev, r.rows.p, r.dev, n_k * sizeof(uint64_t), lead.st));
-            const unsigned blocks = (unsigned)std::min<uint64_t>((n_k + 255) / 256, 65536);
-            hipLaunchKernelGGL(map_rows_merge_kernel, dim3(blocks), block, 0, lead.st, lead.rows.p, staging_.p, n_k);
-            MAP_HIP(hipGetLastError());
+            if ((rc = map_rows_merge(lead.rows.p, staging_.p, n_k, lead.st))) return rc;
         }
         MAP_HIP(hipEventRecord(lead.e2, lead.st));
         // 3. the decision, from the finished rows
@@ -887,6 +885,14 @@ std::unique_ptr<MapEngine> map_engine_device_sharded(const int* devices, int n, 
     std::unique_ptr<ShardedDeviceMapEngine> e(new ShardedDeviceMapEngine(devices, n, K, nw));
     if (e->begin() != PG_OK) return nullptr;
     return std::unique_ptr<MapEngine>(e.release());
+}
+
+int map_rows_merge(uint64_t* d_rows, const uint64_t* d_part, uint64_t n_words, void* stream) {
+    if (!n_words) return PG_OK;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n_words + 255) / 256, 65536);
+    hipLaunchKernelGGL(map_rows_merge_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_rows, d_part, n_words);
+    MAP_HIP(hipGetLastError());
+    return PG_OK;
 }
 
 int map_device_free_bytes(int device, uint64_t* free_bytes) {
