@@ -461,6 +461,32 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       bits 63:32 the weak k-mers of the read as given.  Which bases changed is packed XOR packed_out.
  *                       PG_EINVAL: min_cov == 0, min_run == 0, max_fixes > 255, null packed_out.  n_seqs == 0: PG_OK, nothing touched.
  *                       Device memory of the index's device, asynchronous on `stream`; host memory for a host-twin index.
+ *   pg_kindex_trim      one batch of reads trimmed to their longest solid stretch (csrc/ktrim.hpp; the trimming pass a k-mer-spectrum
+ *                       corrector ends with).  The batch is laid out as for pg_kindex_query_words; n_words = its words, the nw + 1
+ *                       readable ones behind the last read included, n_kmers as there.  Solid is pg_kindex_correct's: the answer is not
+ *                       0 and its coverage (bits 31:24) is >= min_cov.  A read's span is its longest run of consecutive solid k-mers,
+ *                       the leftmost one among equals: a run of n k-mers from k-mer j0 on is the bases j0 .. j0 + n + K - 2, so
+ *                       start = j0 and len = n + K - 1; no solid k-mer, or no k-mer at all, gives len = 0.
+ *                       out_span[r] (may be null) = start | len << 32.  A read is kept iff len >= min_len; min_len >= K.
+ *                       packed_out null: spans only, the other outputs are ignored.  Else the kept reads come out in their input
+ *                       order as one ragged batch: kept read i starts at word word_off_out[i], first base in the most significant
+ *                       bits, pad bits zero whatever the input's were (the words pg_pack_read gives); kmer_base_out[0 .. kept] is
+ *                       the exclusive prefix sum of len - K + 1; src_out[i] (may be null) is the input index of kept read i; nw + 1
+ *                       zero words follow the last kept read; out_totals[0..3] = kept reads, their words (without the tail), their
+ *                       k-mers, and the bases removed: those cut off kept reads plus all bases of dropped reads, a read's own length
+ *                       taken as its k-mers + K - 1 (a read shorter than K has no length in a ragged batch's layout and counts as 0
+ *                       bases, in a uniform batch too).  With min_len >= K + 1 the result is a batch for pg_count_reads.
+ *                       The caller provides packed_out: n_words words (the result never needs more), word_off_out and src_out:
+ *                       n_seqs, kmer_base_out: n_seqs + 1, out_totals: 4.  packed_out must not overlap packed.
+ *                       Works on an index cut over ranks too: the spans are taken from the merged rows of pg_kindex_query_words.
+ *                       Device memory of the index's (lead's) device, asynchronous on `stream` with no host wait -- out_totals is
+ *                       read by the caller when it wants the sizes; the index keeps scratch that grows to the largest batch met, and
+ *                       only that growth waits.  Host memory for a host-twin index.
+ *                       PG_EINVAL: min_cov == 0, min_len < K, packed_out == packed, packed_out given with word_off_out,
+ *                       kmer_base_out or out_totals null, out_span and packed_out both null.  n_seqs == 0: PG_OK, the totals zeroed
+ *                       when packed_out is given.
+ *   pg_kindex_trim_times         milliseconds of the last pg_kindex_trim on a device index, from its events, after waiting for its
+ *                       end: out[0] the spans (a cut index: probes and merge included), [1] the scan, [2] the pack, [3] all of it.
  *   pg_kindex_info      out[0] keys (the records the table was made for, deleted ones included), [1] slots, [2] bytes of the table, [3] device (-1 as a 64-bit value: the host twin).
  *                       An index cut over ranks: the totals over its ranks, and the lead's device.
  *
@@ -501,6 +527,11 @@ int pg_kindex_query(pg_kindex *ix, const uint64_t *packed, const uint64_t *word_
 int pg_kindex_correct(pg_kindex *ix, const uint64_t *packed, const uint64_t *word_off, const uint64_t *kmer_base, uint64_t n_seqs,
                       uint32_t uniform_len, uint64_t n_words, uint32_t min_cov, uint32_t max_fixes, uint32_t min_run,
                       uint64_t *packed_out, uint64_t *out_report, void *stream);
+int pg_kindex_trim(pg_kindex *ix, const uint64_t *packed, uint64_t n_words, const uint64_t *word_off, const uint64_t *kmer_base,
+                   uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, uint32_t min_cov, uint32_t min_len, uint64_t *out_span,
+                   uint64_t *packed_out, uint64_t *word_off_out, uint64_t *kmer_base_out, uint64_t *src_out, uint64_t *out_totals,
+                   void *stream);
+int pg_kindex_trim_times(pg_kindex *ix, double out[4]);
 int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
 void pg_kindex_destroy(pg_kindex *ix);
 uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */

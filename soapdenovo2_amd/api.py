@@ -181,6 +181,9 @@ def lib() -> C.CDLL:
     L.pg_kindex_query.argtypes = [C.c_void_p, u64p, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u64p, u64p, C.c_void_p]
     L.pg_kindex_correct.argtypes = [C.c_void_p, u64p, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u64p,
                                     C.c_void_p]
+    L.pg_kindex_trim.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, u64p, u64p,
+                                 u64p, u64p, u64p, u64p, C.c_void_p]
+    L.pg_kindex_trim_times.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_info.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_destroy.argtypes = [C.c_void_p]
     L.pg_kindex_destroy.restype = None
@@ -212,7 +215,7 @@ EXPORTED_SYMBOLS = [
     "pg_map_reads_sharded", "pg_map_hits_sharded", "pg_map_long_reads_sharded", "pg_host_map_owner", "pg_host_map_plan",
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
-    "pg_host_kindex_plan",
+    "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
@@ -875,6 +878,18 @@ def report_fields(report) -> dict:
     return out
 
 
+TRIM_TOTALS_FIELDS = ["kept", "words", "kmers", "bases_removed"]
+
+
+def span_fields(spans) -> dict:
+    """The trim's span words split up: `start` (the first base of a read's longest solid stretch) and `len` (its bases; 0: the read has
+    no solid k-mer).  Takes a numpy array or a torch tensor; returns numpy arrays."""
+    if not isinstance(spans, np.ndarray):
+        spans = spans.cpu().numpy()
+    w = np.ascontiguousarray(spans).view(np.uint64)
+    return {"start": (w & np.uint64(0xffffffff)).astype(np.int64), "len": (w >> np.uint64(32)).astype(np.int64)}
+
+
 def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
     """pg_host_kindex_bytes: the table an index of n_records k-mers cuts (no GPU)."""
     return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
@@ -900,7 +915,7 @@ class KmerIndex:
     `KmerIndex.from_records(records, K)`.  On a GPU the batches and the answers are torch tensors of that device; with device = -1
     (the host twin, no GPU) they are numpy arrays.  An answer is a record's cnt word, 0 for a k-mer that is not in the set.
     An index cut over ranks (`device` a sequence of ordinals, `from_parts`, `KmerCounter.index(devices)`) answers the same queries with
-    the same words; its batches and answers lie on the lead's device, `device`, and it does not correct reads."""
+    the same words; its batches and answers lie on the lead's device, `device`; it trims reads but does not correct them."""
 
     def __init__(self, handle, K: int, mer127: bool, device: int):
         self.h, self.K, self.mer127, self.device = handle, K, mer127, device
@@ -1048,6 +1063,41 @@ class KmerIndex:
         """correct_uniform for reads of any lengths (pack_seqs_ragged); a read shorter than K comes back as it is, flagged."""
         return self._correct(d_packed, d_word_off, d_kmer_base, n_reads, 0, min_cov, max_fixes, min_run, out)
 
+    def _trim(self, packed, word_off, kmer_base, n_reads, uniform_len, n_kmers, min_cov, min_len, pack):
+        n_words = int(packed.size if self.device < 0 else packed.numel())
+        min_len = self.K + 1 if min_len is None else min_len
+        # (one element at least: an empty array has no address)
+        if self.device < 0:
+            new = lambda n: np.zeros(max(n, 1), dtype=np.uint64)
+        else:
+            new = lambda n: self.torch.zeros(max(n, 1), dtype=self.torch.int64, device=f"cuda:{self.device}")
+        spans = new(n_reads)
+        outs = (new(n_words), new(n_reads), new(n_reads + 1), new(n_reads), new(4)) if pack else (None,) * 5
+        _check(lib().pg_kindex_trim(self.h, self._ptr(packed), n_words, self._ptr(word_off), self._ptr(kmer_base), n_reads, uniform_len, n_kmers,
+                                    min_cov, min_len, self._ptr(spans), *[self._ptr(o) for o in outs], self._stream()), "pg_kindex_trim")
+        return (spans[:n_reads],) + outs if pack else spans[:n_reads]
+
+    def trim_uniform(self, d_packed, n_reads: int, read_len: int, min_cov: int, min_len=None, pack: bool = True):
+        """Every read of a batch of reads of read_len bases (pack_reads_uniform; the whole of d_packed is the batch, its readable tail
+        included) trimmed to its longest stretch of solid k-mers (pg_kindex_trim; solid as in correct_uniform).  Returns the span words
+        (span_fields) and, when packing, (spans, packed_out, word_off_out, kmer_base_out, src_out, totals): the reads whose span has
+        min_len bases or more (default K + 1: what KmerCounter.count_ragged takes) as one ragged batch in their input order, src_out the
+        input index of each, totals = TRIM_TOTALS_FIELDS.  The outputs have the capacities the call needs -- packed_out as many words
+        as d_packed, word_off_out and src_out n_reads, kmer_base_out n_reads + 1 -- and totals says how much of them is used; nothing
+        waits for the GPU here, so read totals when the sizes are wanted.  Works on an index cut over ranks as well."""
+        nk = max(0, read_len - self.K + 1)
+        return self._trim(d_packed, None, None, n_reads, read_len, n_reads * nk, min_cov, min_len, pack)
+
+    def trim_ragged(self, d_packed, d_word_off, d_kmer_base, n_reads: int, n_kmers: int, min_cov: int, min_len=None, pack: bool = True):
+        """trim_uniform for reads of any lengths (pack_seqs_ragged); a read shorter than K has no k-mer and is dropped."""
+        return self._trim(d_packed, d_word_off, d_kmer_base, n_reads, 0, n_kmers, min_cov, min_len, pack)
+
+    def trim_times(self) -> dict:
+        """Milliseconds of the last trim of a device index, from its events (pg_kindex_trim_times; waits for the trim)."""
+        out = np.zeros(4, dtype=np.float64)
+        _check(lib().pg_kindex_trim_times(self.h, out.ctypes.data), "pg_kindex_trim_times")
+        return {"span": float(out[0]), "scan": float(out[1]), "pack": float(out[2]), "total": float(out[3])}
+
     def info(self) -> dict:
         out = np.zeros(4, dtype=np.uint64)
         _check(lib().pg_kindex_info(self.h, out.ctypes.data), "pg_kindex_info")
@@ -1132,3 +1182,21 @@ def correct_reads(reads: Sequence[np.ndarray], index: KmerIndex, min_cov: int, m
         out, report = index.correct_ragged(up(words), up(word_off), up(kmer_base), len(reads), min_cov, max_fixes, min_run)
         out, report = out.cpu().numpy().view(np.uint64), report.cpu().numpy().view(np.uint64)
     return [unpack_seq(out[int(word_off[i]):], len(r)) for i, r in enumerate(reads)], report
+
+
+def trim_reads(reads: Sequence[np.ndarray], index: KmerIndex, min_cov: int, min_len=None):
+    """Reads (base-code arrays, any lengths) trimmed to their longest solid stretch against the index: (a list of the base-code arrays of
+    the kept reads, the input index of each as a numpy array, the span words of all reads -- see span_fields)."""
+    words, word_off, kmer_base = pack_seqs_ragged(reads, index.K)
+    n_k = int(kmer_base[-1])
+    if index.device < 0:
+        res = index.trim_ragged(words, word_off, kmer_base, len(reads), n_k, min_cov, min_len)
+    else:
+        t, dev = index.torch, f"cuda:{index.device}"
+        up = lambda a: t.from_numpy(a.view(np.int64)).to(dev)
+        res = [o.cpu().numpy().view(np.uint64) for o in index.trim_ragged(up(words), up(word_off), up(kmer_base), len(reads), n_k, min_cov, min_len)]
+    spans, packed_out, word_off_out, _, src, totals = res
+    n_kept = int(totals[0])
+    lens = span_fields(spans)["len"]
+    kept = [unpack_seq(packed_out[int(word_off_out[i]):], int(lens[int(src[i])])) for i in range(n_kept)]
+    return kept, src[:n_kept].astype(np.int64), spans

@@ -159,4 +159,10 @@ struct pg_kindex {
     uint64_t cap_staging = 0;
     hipEvent_t e_begin = nullptr, e_probed = nullptr, e_merged = nullptr, e_end = nullptr;
     bool queried = false;          // e_end has been recorded
+    // pg_kindex_trim's scratch on `device` (ktrim.hpp): the spans and source indices the caller did not ask for and the scan's block sums.
+    // It grows to the largest batch met; the events are a trim's begin, spans done, scan done, end
+    uint64_t* d_trim = nullptr;
+    uint64_t cap_trim = 0;
+    hipEvent_t e_trim[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool trimmed = false;          // e_trim has been recorded
 };

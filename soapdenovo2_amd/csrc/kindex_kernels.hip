@@ -27,6 +27,18 @@
 //   kidx_summary_rows_kernel   a wavefront per sequence, four a workgroup, over the merged rows: lanes stride the row (j = lane, lane + 64,
 //                              ...: coalesced), the query wave kernel's butterfly, lane 0 stores.  Sums and minima: the same words.
 // The merge is map_rows_merge_kernel (map_kernels.hip, through map_rows_merge).
+// The trim (ktrim.hpp; pg_kindex_trim):
+//   ktrim_span_kernel          a lane per read: kidx_query_kernel's walk and launch shape, the current and the best run of solid k-mers in
+//                              registers (ktrim_span_probe), one span word stored.  The span word is all the scan wants of a read: kept,
+//                              output words and output k-mers are ktrim_counts of it
+//   ktrim_span_rows_kernel     the same tracker over a read's row of merged answers (an index cut over ranks), no probe
+//   the scan                   three kernels over blocks of 256 reads: ktrim_block_sums_kernel (a workgroup's sums of the four counts
+//                              through wave butterflies and LDS), ktrim_scan_sums_kernel (one workgroup: the exclusive scan of the
+//                              workgroups' sums in place, the totals, kmer_base_out's last entry), ktrim_scatter_kernel (the scan
+//                              inside a workgroup again, and every kept read's word_off_out, kmer_base_out and src_out)
+//   ktrim_pack_kernel          a lane per output word, the tail's nw + 1 zero words included: the kept read by binary search in
+//                              word_off_out, the word by ktrim_pack_word.  The launch covers the batch's n_words, which the result never
+//                              passes; how many of those lanes have a word is read from the totals on the device
 // Both query kernels wait for one random slot read per k-mer (32 B a slot in the 63-mer build, 48 B in the 127-mer one) of a table that
 // is many times the L2; the roll is arithmetic hidden under it.  The measured times, the cut over ranks included, are in DESIGN.md §10.
 #include <hip/hip_runtime.h>
@@ -41,6 +53,7 @@
 #include "env.hpp"
 #include "kcorrect.hpp"
 #include "kindex.hpp"
+#include "ktrim.hpp"
 
 namespace pg {
 
@@ -231,6 +244,135 @@ __global__ __launch_bounds__(256) void kidx_summary_rows_kernel(const uint64_t* 
         kidx_summary_merge(s, o);
     }
     if (lane == 0) kidx_summary_store(s, nk, summary + r * KIDX_SUMMARY_WORDS);
+}
+
+// ---- the trim: spans, the scan of the kept reads' counts, the pack ----
+template <int NW>
+__global__ __launch_bounds__(256) void ktrim_span_kernel(const uint64_t* __restrict__ packed, const uint64_t* __restrict__ word_off,
+                                                         const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len, int K,
+                                                         const uint64_t* __restrict__ tab, uint64_t mask, uint32_t min_cov, uint64_t* __restrict__ span) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_seqs) return;
+    const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, K, r);
+    span[r] = ktrim_span_probe<NW>(q.rd, q.nk, K, tab, mask, min_cov);
+}
+
+__global__ __launch_bounds__(256) void ktrim_span_rows_kernel(const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len, int K,
+                                                              const uint64_t* __restrict__ rows, uint32_t min_cov, uint64_t* __restrict__ span) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_seqs) return;
+    const int nk = ktrim_nk(kmer_base, uniform_len, K, r);
+    span[r] = ktrim_span_row(rows + (uniform_len ? r * (uint64_t)nk : kmer_base[r]), nk, K, min_cov);
+}
+
+// read r's counts; a lane past the batch has none
+__device__ __forceinline__ KtrimCounts ktrim_lane_counts(const uint64_t* span, const uint64_t* kmer_base, uint64_t n_seqs, uint32_t uniform_len,
+                                                         int K, uint32_t min_len, uint64_t r) {
+    if (r >= n_seqs) return KtrimCounts{{0, 0, 0, 0}};
+    return ktrim_counts(span[r], ktrim_nk(kmer_base, uniform_len, K, r), K, min_len);
+}
+
+// The inclusive scan of the lanes' counts over a 256-thread workgroup: inside a wave by __shfl_up, the four waves' sums through LDS.
+// Every lane of the workgroup calls it.  c becomes the lane's inclusive sums, and the workgroup's sums are returned
+__device__ __forceinline__ KtrimCounts ktrim_block_scan(KtrimCounts& c, uint64_t (*wave_sums)[KTRIM_COUNTS]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < KTRIM_COUNTS; i++) {
+        uint64_t v = c.c[i];
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t o = __shfl_up(v, d);
+            v += lane >= d ? o : 0;
+        }
+        c.c[i] = v;
+        if (lane == 63) wave_sums[wave][i] = v;
+    }
+    __syncthreads();
+    KtrimCounts all{{0, 0, 0, 0}};
+#pragma unroll
+    for (int i = 0; i < KTRIM_COUNTS; i++)
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            const uint64_t s = wave_sums[w][i];
+            c.c[i] += w < wave ? s : 0;
+            all.c[i] += s;
+        }
+    __syncthreads();                               // (wave_sums may be written again by the caller's next round)
+    return all;
+}
+
+__global__ __launch_bounds__(256) void ktrim_block_sums_kernel(const uint64_t* __restrict__ span, const uint64_t* __restrict__ kmer_base, uint64_t n_seqs,
+                                                               uint32_t uniform_len, int K, uint32_t min_len, uint64_t* __restrict__ sums) {
+    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
+    KtrimCounts c = ktrim_lane_counts(span, kmer_base, n_seqs, uniform_len, K, min_len, (uint64_t)blockIdx.x * 256 + threadIdx.x);
+    const KtrimCounts all = ktrim_block_scan(c, wave_sums);
+    if (threadIdx.x < KTRIM_COUNTS) sums[(uint64_t)blockIdx.x * KTRIM_COUNTS + threadIdx.x] = all.c[threadIdx.x];
+}
+
+// one workgroup: sums[b] becomes the sums of the workgroups before b, 256 of them a round with the carry in registers
+__global__ __launch_bounds__(256) void ktrim_scan_sums_kernel(uint64_t* __restrict__ sums, uint64_t n_blocks, uint64_t* __restrict__ kmer_base_out,
+                                                              uint64_t* __restrict__ totals) {
+    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
+    KtrimCounts carry{{0, 0, 0, 0}};
+    for (uint64_t at = 0; at < n_blocks; at += 256) {                           // (uniform over the workgroup: every lane meets the barriers)
+        const uint64_t b = at + threadIdx.x;
+        KtrimCounts own{{0, 0, 0, 0}};
+        if (b < n_blocks)
+#pragma unroll
+            for (int i = 0; i < KTRIM_COUNTS; i++) own.c[i] = sums[b * KTRIM_COUNTS + i];
+        KtrimCounts c = own;
+        const KtrimCounts all = ktrim_block_scan(c, wave_sums);
+#pragma unroll
+        for (int i = 0; i < KTRIM_COUNTS; i++) {
+            if (b < n_blocks) sums[b * KTRIM_COUNTS + i] = carry.c[i] + c.c[i] - own.c[i];
+            carry.c[i] += all.c[i];
+        }
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < KTRIM_COUNTS; i++) totals[i] = carry.c[i];
+        kmer_base_out[carry.c[0]] = carry.c[2];
+    }
+}
+
+__global__ __launch_bounds__(256) void ktrim_scatter_kernel(const uint64_t* __restrict__ span, const uint64_t* __restrict__ kmer_base, uint64_t n_seqs,
+                                                            uint32_t uniform_len, int K, uint32_t min_len, const uint64_t* __restrict__ sums,
+                                                            uint64_t* __restrict__ word_off_out, uint64_t* __restrict__ kmer_base_out,
+                                                            uint64_t* __restrict__ src_out) {
+    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const KtrimCounts own = ktrim_lane_counts(span, kmer_base, n_seqs, uniform_len, K, min_len, r);
+    KtrimCounts c = own;
+    (void)ktrim_block_scan(c, wave_sums);
+    if (!own.c[0]) return;                         // (no barrier follows)
+    const uint64_t* before = sums + (uint64_t)blockIdx.x * KTRIM_COUNTS;
+    const uint64_t i = before[0] + c.c[0] - 1;     // the kept reads before this one
+    word_off_out[i] = before[1] + c.c[1] - own.c[1];
+    kmer_base_out[i] = before[2] + c.c[2] - own.c[2];
+    src_out[i] = r;
+}
+
+__global__ __launch_bounds__(256) void ktrim_pack_kernel(const uint64_t* __restrict__ packed, const uint64_t* __restrict__ word_off, uint32_t uniform_len,
+                                                         const uint64_t* __restrict__ span, const uint64_t* __restrict__ word_off_out,
+                                                         const uint64_t* __restrict__ src_out, const uint64_t* __restrict__ totals, int tail,
+                                                         uint64_t n_words, uint64_t* __restrict__ packed_out) {
+    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t n_kept = totals[0], words = totals[1];
+    if (w >= words) {
+        if (w < words + (uint64_t)tail && w < n_words) packed_out[w] = 0;       // the readable words behind the last kept read
+        return;
+    }
+    uint64_t lo = 0, hi = n_kept;                  // the last kept read that starts at or before word w: word_off_out[lo] <= w
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        const bool up = word_off_out[mid] <= w;
+        lo = up ? mid : lo;
+        hi = up ? hi : mid;
+    }
+    const uint64_t r = src_out[lo], sp = span[r];
+    const uint64_t* rd = packed + (uniform_len ? r * (uint64_t)((uniform_len + 31) / 32) : word_off[r]);
+    // ktrim_pack_word loads two source words whatever the shift: the second one of a read's last output word may be the next read's
+    // first word or, for the batch's last read, the first of the nw + 1 readable tail words -- never past the batch
+    packed_out[w] = ktrim_pack_word(rd, ktrim_start(sp), ktrim_len(sp), w - word_off_out[lo]);
 }
 
 namespace {
@@ -650,6 +792,95 @@ int kidx_device_query_sharded(::pg_kindex* ix, const uint64_t* d_packed, uint64_
     return rc;
 }
 
+// ---- the trim ----
+namespace {
+
+void ktrim_free(::pg_kindex* ix) {
+    if (ix->d_trim) (void)arena_free(ix->d_trim);
+    for (hipEvent_t& e : ix->e_trim) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    ix->d_trim = nullptr;
+    ix->cap_trim = 0;
+    ix->trimmed = false;
+}
+
+}  // namespace
+
+int ktrim_device_trim(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words, const uint64_t* d_word_off, const uint64_t* d_kmer_base,
+                      uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, uint32_t min_cov, uint32_t min_len, uint64_t* d_span,
+                      uint64_t* d_packed_out, uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_src_out, uint64_t* d_totals,
+                      void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    if (!n_seqs) {
+        if (d_packed_out) KIDX_HIP(hipMemsetAsync(d_totals, 0, KTRIM_COUNTS * sizeof(uint64_t), st));
+        return PG_OK;
+    }
+    const uint64_t n_blocks = (n_seqs + 255) / 256, pack_blocks = (n_words + 255) / 256;
+    if (n_blocks > 0x7FFFFFFFULL || pack_blocks > 0x7FFFFFFFULL) { pg_set_error("k-mer index: batch too large for one launch"); return PG_EINVAL; }
+    // Scratch: the spans and the source indices where the caller takes none, and the workgroups' sums.  It grows to the largest batch
+    // met: the buffer is given back first, and arena_free waits for the device as hipFree does, so no earlier trim still uses it --
+    // the only place the host waits
+    const uint64_t want = (d_span ? 0 : n_seqs) + (d_packed_out ? (d_src_out ? 0 : n_seqs) + n_blocks * KTRIM_COUNTS : 0);
+    if (int rc = kidx_reserve(&ix->d_trim, &ix->cap_trim, std::max<uint64_t>(want, 1))) return rc;
+    uint64_t* next = ix->d_trim;
+    if (!d_span) { d_span = next; next += n_seqs; }
+    if (d_packed_out && !d_src_out) { d_src_out = next; next += n_seqs; }
+    uint64_t* d_sums = next;
+    for (hipEvent_t& e : ix->e_trim) if (!e) KIDX_HIP(hipEventCreate(&e));
+    if (ix->trimmed) KIDX_HIP(hipStreamWaitEvent(st, ix->e_trim[3], 0));         // (another stream than last time's: the scratch is one)
+    KIDX_HIP(hipEventRecord(ix->e_trim[0], st));
+    const dim3 grid((unsigned)n_blocks), block(256);
+    if (ix->ranks.empty()) {
+        kidx_with_nw(ix->nw, [&](auto nw) {
+            hipLaunchKernelGGL((ktrim_span_kernel<decltype(nw)::value>), grid, block, 0, st, d_packed, d_word_off, d_kmer_base, n_seqs, uniform_len, ix->K,
+                               ix->d_tab, ix->slots - 1, min_cov, d_span);
+        });
+        KIDX_HIP(hipGetLastError());
+    } else {
+        // every rank probes the k-mers it owns and the lead's row buffer receives the merged answers (no counts or summary for the caller)
+        if (int rc = kidx_device_query_sharded(ix, d_packed, n_words, d_word_off, d_kmer_base, n_seqs, uniform_len, n_kmers, 0, nullptr, nullptr, stream))
+            return rc;
+        hipLaunchKernelGGL(ktrim_span_rows_kernel, grid, block, 0, st, d_kmer_base, n_seqs, uniform_len, ix->K, ix->ranks[0].d_rows, min_cov, d_span);
+        KIDX_HIP(hipGetLastError());
+        KIDX_HIP(hipEventRecord(ix->e_end, st));   // the next query's ranks zero the rows: they wait for this read of them too
+    }
+    KIDX_HIP(hipEventRecord(ix->e_trim[1], st));
+    if (d_packed_out) {
+        hipLaunchKernelGGL(ktrim_block_sums_kernel, grid, block, 0, st, d_span, d_kmer_base, n_seqs, uniform_len, ix->K, min_len, d_sums);
+        hipLaunchKernelGGL(ktrim_scan_sums_kernel, dim3(1), block, 0, st, d_sums, n_blocks, d_kmer_base_out, d_totals);
+        hipLaunchKernelGGL(ktrim_scatter_kernel, grid, block, 0, st, d_span, d_kmer_base, n_seqs, uniform_len, ix->K, min_len, d_sums, d_word_off_out,
+                           d_kmer_base_out, d_src_out);
+        KIDX_HIP(hipGetLastError());
+    }
+    KIDX_HIP(hipEventRecord(ix->e_trim[2], st));
+    if (d_packed_out) {
+        hipLaunchKernelGGL(ktrim_pack_kernel, dim3((unsigned)pack_blocks), block, 0, st, d_packed, d_word_off, uniform_len, d_span, d_word_off_out, d_src_out,
+                           d_totals, ix->nw + 1, n_words, d_packed_out);
+        KIDX_HIP(hipGetLastError());
+    }
+    KIDX_HIP(hipEventRecord(ix->e_trim[3], st));
+    ix->trimmed = true;
+    return PG_OK;
+}
+
+int ktrim_device_times(::pg_kindex* ix, double out[4]) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!ix->trimmed) return PG_OK;
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    KIDX_HIP(hipEventSynchronize(ix->e_trim[3]));
+    float ms = 0;
+    for (int i = 0; i < 3; i++) {
+        KIDX_HIP(hipEventElapsedTime(&ms, ix->e_trim[i], ix->e_trim[i + 1]));
+        out[i] = ms;
+    }
+    KIDX_HIP(hipEventElapsedTime(&ms, ix->e_trim[0], ix->e_trim[3]));
+    out[3] = ms;
+    return PG_OK;
+}
+
 int kidx_device_query_times(::pg_kindex* ix, double out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
     if (!ix->queried) return PG_OK;
@@ -670,6 +901,10 @@ int kidx_device_query_times(::pg_kindex* ix, double out[4]) {
 }
 
 void kidx_device_free(::pg_kindex* ix) {
+    if (ix->d_trim || ix->e_trim[0]) {             // (arena_free waits for the device: no trim still uses the scratch)
+        (void)hipSetDevice(ix->device);
+        ktrim_free(ix);
+    }
     if (!ix->ranks.empty()) {                      // every stream first: the lead's copies read the other ranks' rows
         kidx_sync_ranks(ix);
         for (KidxRank& r : ix->ranks) {
