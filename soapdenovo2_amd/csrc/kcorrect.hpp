@@ -139,7 +139,6 @@ PG_HD uint64_t kcor_read(uint64_t* rd, int nk, int K, const uint64_t* tab, uint6
 }
 
 // the device engine (kindex_kernels.hip): d_out already holds the batch
-int kcor_device_correct(::pg_kindex* ix, const uint64_t* d_packed, const uint64_t* d_word_off, const uint64_t* d_kmer_base, uint64_t n_seqs,
-                        uint32_t uniform_len, uint64_t n_words, const KcorParams& pr, uint64_t* d_packed_out, uint64_t* d_report, void* stream);
+int kcor_device_correct(::pg_kindex* ix, const KidxBatch& b, const KcorParams& pr, uint64_t* d_packed_out, uint64_t* d_report, void* stream);
 
 }  // namespace pg

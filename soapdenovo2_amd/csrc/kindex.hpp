@@ -10,24 +10,27 @@
 // State: 0 empty, 1 claimed (key being written), 2 published; the keys of the records are distinct by contract, and a
 // build that meets a key twice fails.  The build side stays with each engine (kindex_kernels.hip: a CAS protocol, kindex_host.cpp: a
 // serial insert); the read side -- kidx_find (map_index.hpp), kidx_stretch and the per-sequence summary below -- is one piece of code
-// for the two query kernels and the host twin.
+// for the query kernel and the host twin.
 //
-// A batch of sequences is laid out as pg_count_reads' batches are: pg_pack_read words, either all of uniform_len bases (sequence r at
-// word r * pg_packed_words(uniform_len)) or with d_word_off[n] + d_kmer_base[n + 1].  A sequence of len bases has max(0, len - K + 1)
-// k-mers: one of exactly K bases has one (the "K + 1" rule is pregraph's reader's, not the query's).  Behind the last sequence NW + 1
-// words (3 in the 63-mer build, 5 in the 127-mer one) must be readable: read_kmer<NW> loads NW + 1 words from the one that holds the
-// k-mer's first base on.  A sequence without k-mers is never read.
+// A batch of sequences (KidxBatch) is laid out as pg_count_reads' batches are: pg_pack_read words, either all of uniform_len bases
+// (sequence r at word r * pg_packed_words(uniform_len)) or with word_off[n] + kmer_base[n + 1].  A sequence of len bases has
+// max(0, len - K + 1) k-mers: one of exactly K bases has one (the "K + 1" rule is pregraph's reader's, not the query's).  Behind the
+// last sequence NW + 1 words (3 in the 63-mer build, 5 in the 127-mer one) must be readable: read_kmer<NW> loads NW + 1 words from the
+// one that holds the k-mer's first base on.  A sequence without k-mers is never read.
 //
 // The index cut over ranks (pg_kindex_build_sharded): rank i of n holds the stored records whose canonical key has map_owner(key, n) == i
 // (map_index.hpp: the hash's bits 40 and up, modulo n) in a table of its own -- map_table_slots(owned_i) slots, the same slot format,
 // cut from the arena of devices[i]; owned_i counts the records the rank owns, the deleted ones among them included, so that
-// sum(owned_i) == n_records and a one-rank cut is pg_kindex_build's table.  A rank that owns nothing keeps a zeroed table of the smallest
-// size.  Rank 0 is the lead: a batch and its answers lie on its device.  A key has one owner and 0 means "absent", so the ranks' rows of
-// a batch -- each rank probes the keys it owns into zeroed rows -- OR together into the answers (map_rows_merge_kernel), and the
-// summary is taken from the finished rows.  The host twin is n serial tables with the same cut.
+// sum(owned_i) == n_records and a one-rank cut is pg_kindex_build's table: map_owner(key, 1) == 0 for every key.  So there is one
+// shape of index, pg_kindex::ranks, and pg_kindex_build's single table is ranks[0] of an index that is not `cut`.  A rank that owns
+// nothing keeps a zeroed table of the smallest size.  Rank 0 is the lead: a batch and its answers lie on its device.  A key has one
+// owner and 0 means "absent", so the ranks' rows of a batch -- each rank probes the keys it owns into zeroed rows -- OR together into
+// the answers (map_rows_merge_kernel), and the summary is taken from the finished rows.  The host twin is n serial tables with the
+// same cut (kidx_host_find).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
+#include <type_traits>
 #include <vector>
 
 #include "map_index.hpp"
@@ -90,18 +93,56 @@ PG_HD void kidx_stretch(const uint64_t* rd, int j0, int j1, int K, const uint64_
     });
 }
 
-// sequence r of a batch: its words, its k-mers and where its answers go (uniform_len != 0: word_off / kmer_base are not read)
+// the key of a record in export format: its first NW words
+template <int NW>
+PG_HD Kmer<NW> kidx_record_key(const uint64_t* rec) {
+    Kmer<NW> k;
+#pragma unroll
+    for (int q = 0; q < NW; q++) k.w[q] = rec[q];
+    return k;
+}
+
+// A batch as the ABI hands it over.  uniform_len != 0: word_off / kmer_base are not read.  n_words (the packed words, the NW + 1 readable
+// ones behind the last sequence included) and n_kmers are what the caller states; an entry point that takes neither leaves them 0
+struct KidxBatch {
+    const uint64_t *packed, *word_off, *kmer_base;
+    uint64_t n_seqs;
+    uint32_t uniform_len;
+    uint64_t n_words, n_kmers;
+};
+
+// sequence r of a batch: its k-mers and where its answers go (kidx_row: the words are not touched), and its words (kidx_seq)
+struct KidxRow {
+    uint64_t base;
+    int nk;
+};
 struct KidxSeq {
     const uint64_t* rd;
     uint64_t base;
     int nk;
 };
-PG_HD KidxSeq kidx_seq(const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint32_t uniform_len, int K, uint64_t r) {
-    if (uniform_len) {
-        const int nk = (int)uniform_len >= K ? (int)uniform_len - K + 1 : 0;
-        return KidxSeq{packed + r * (uint64_t)((uniform_len + 31) / 32), r * (uint64_t)nk, nk};
+PG_HD int kidx_uniform_nk(uint32_t len, int K) { return (int)len >= K ? (int)len - K + 1 : 0; }
+PG_HD KidxRow kidx_row(const KidxBatch& b, int K, uint64_t r) {
+    if (b.uniform_len) {
+        const int nk = kidx_uniform_nk(b.uniform_len, K);
+        return KidxRow{r * (uint64_t)nk, nk};
     }
-    return KidxSeq{packed + word_off[r], kmer_base[r], (int)(kmer_base[r + 1] - kmer_base[r])};
+    return KidxRow{b.kmer_base[r], (int)(b.kmer_base[r + 1] - b.kmer_base[r])};
+}
+// (one branch, not kidx_row's and another: a ragged batch's loads of word_off and kmer_base stay in flight together)
+PG_HD KidxSeq kidx_seq(const KidxBatch& b, int K, uint64_t r) {
+    if (b.uniform_len) {
+        const int nk = kidx_uniform_nk(b.uniform_len, K);
+        return KidxSeq{b.packed + r * (uint64_t)((b.uniform_len + 31) / 32), r * (uint64_t)nk, nk};
+    }
+    return KidxSeq{b.packed + b.word_off[r], b.kmer_base[r], (int)(b.kmer_base[r + 1] - b.kmer_base[r])};
+}
+
+// f(std::integral_constant<int, NW>) for an index's flavour
+template <typename F>
+inline void kidx_with_nw(int nw, F f) {
+    if (nw == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 4>{});
 }
 
 inline uint64_t kidx_table_bytes(uint64_t n_records, int nw) { return map_table_slots(n_records) * (uint64_t)(nw + 2) * sizeof(uint64_t); }
@@ -113,7 +154,8 @@ inline uint64_t kidx_table_bytes(uint64_t n_records, int nw) { return map_table_
 constexpr uint64_t KIDX_CHUNK_RECORDS = 1ull << 22;
 uint64_t kidx_chunk_records();
 
-// a rank of an index cut over ranks.  The device engine fills the device half, the host twin `tab`
+// a rank of an index: the one table of pg_kindex_build, or one of a cut.  The device engine fills the device half, the host twin `tab`.
+// The stream, the events and the batch buffers are a cut's: a rank of an index in one table has none
 struct KidxRank {
     int device = -1;
     uint64_t keys = 0, slots = 0;  // the records it owns (deleted ones included), the slots of its table
@@ -128,31 +170,34 @@ struct KidxRank {
     uint64_t cap_packed = 0, cap_seqs = 0, cap_rows = 0;
 };
 
-// the device engine (kindex_kernels.hip); the table is cut from the arena of ix->device.  PG_OK or a PG_E* code with pg_set_error done
+// what every entry point that takes a batch asks of it alike; `noun` is what the messages call a sequence ("sequence", "read")
+enum : unsigned {
+    KIDX_ARGS_KMERS = 1u,          // a uniform batch's n_kmers is n_seqs * max(0, len - K + 1)
+    KIDX_ARGS_WORDS = 2u,          // a uniform batch's n_words holds the sequences' words and the nw + 1 readable ones
+    KIDX_ARGS_TAIL = 4u,           // any batch's n_words holds the nw + 1 readable ones
+};
+int kidx_batch_args(const char* who, const ::pg_kindex* ix, const KidxBatch& b, const char* noun, unsigned checks);
+
+// the device engine (kindex_kernels.hip); a table is cut from the arena of its rank's device.  PG_OK or a PG_E* code with pg_set_error done
 int kidx_device_build(::pg_kindex* ix, const uint64_t* d_records, uint64_t n_records, void* stream);
-int kidx_device_query(::pg_kindex* ix, const uint64_t* d_packed, const uint64_t* d_word_off, const uint64_t* d_kmer_base, uint64_t n_seqs,
-                      uint32_t uniform_len, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream);
+int kidx_device_query(::pg_kindex* ix, const KidxBatch& b, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream);
 void kidx_device_free(::pg_kindex* ix);
 // the index cut over ix->ranks (their `device` set): part p = part_records[p] records on device part_device[p], or in host memory (-1)
 int kidx_device_build_sharded(::pg_kindex* ix, const uint64_t* const* parts, const uint64_t* part_records, const int* part_device, int n_parts,
                               void* stream);
-int kidx_device_query_sharded(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words, const uint64_t* d_word_off, const uint64_t* d_kmer_base,
-                              uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream);
+int kidx_device_query_sharded(::pg_kindex* ix, const KidxBatch& b, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream);
 // the last sharded query's milliseconds from its events, after waiting for its end: the slowest rank's probe, the merge, the summary, all of it
 int kidx_device_query_times(::pg_kindex* ix, double out[4]);
 
 }  // namespace pg
 
 struct pg_kindex {
-    int device = -1;               // -1: the host twin
+    int device = -1;               // the lead's (rank 0's); -1: the host twin
     int K = 0, nw = 2;
-    uint64_t keys = 0, slots = 0;   // the records the table was made for (the deleted ones among them are not stored), its slots
-    uint64_t* d_tab = nullptr;     // device: slots * (nw + 2) words of the arena
-    uint32_t* d_flags = nullptr;   // device: the build's flags (KIDX_FLAG_*)
-    std::vector<uint64_t> tab;     // host twin
-    // An index cut over ranks (pg_kindex_build_sharded): one entry a rank, rank 0 the lead; `device` is then the lead's, keys the sum over
-    // the ranks and slots the sum of their tables', and d_tab / tab stay empty.  Empty: one table, the fields above
+    // One entry a rank, never empty, rank 0 the lead.  cut: pg_kindex_build_sharded made the index, a batch is copied to the ranks and
+    // their rows merged (pg_kindex_query_words); else pg_kindex_build did and ranks[0] is the one table, asked in place
     std::vector<pg::KidxRank> ranks;
+    bool cut = false;
     // the lead's alone: the buffer the other ranks' rows arrive in, and the events of a query on the caller's stream -- its begin, every
     // rank's probe waited for, merged, its end (which the next query's ranks wait for: the row buffers are reused)
     uint64_t* d_staging = nullptr;
@@ -166,3 +211,14 @@ struct pg_kindex {
     hipEvent_t e_trim[4] = {nullptr, nullptr, nullptr, nullptr};
     bool trimmed = false;          // e_trim has been recorded
 };
+
+namespace pg {
+
+// the host twin's lookup: the canonical k-mer ck in its owner's table (one rank: map_owner is 0)
+template <int NW>
+inline uint64_t kidx_host_find(const ::pg_kindex* ix, const Kmer<NW>& ck) {
+    const KidxRank& r = ix->ranks[map_owner<NW>(ck, (uint32_t)ix->ranks.size())];
+    return kidx_find<NW>(r.tab.data(), r.slots - 1, ck);
+}
+
+}  // namespace pg

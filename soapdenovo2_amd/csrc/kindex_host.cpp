@@ -1,7 +1,7 @@
 // kindex_host.cpp -- the k-mer index's C ABI (pg_kindex_*, include/soapdenovo2_amd.h section 3) and its host twin (device = -1): the same
-// table built by a serial insert, the same lookups and summary (kindex.hpp: kidx_stretch, KidxSummary) over host memory.  What the CPU
+// tables built by a serial insert, the same lookups and summary (kindex.hpp: kidx_host_find, KidxSummary) over host memory.  What the CPU
 // tests run, and the device path's yardstick.  The index cut over ranks (pg_kindex_build_sharded with a device list of -1s) is n such
-// tables with the device's cut: a k-mer is looked up in the table of map_owner(key, n).
+// tables with the device's cut: a k-mer is looked up in the table of map_owner(key, n); pg_kindex_build's one table is the case n = 1.
 #include <stdlib.h>
 #include <string.h>
 #include <string>
@@ -41,8 +41,7 @@ pg_kindex* kidx_build_failed(pg_kindex* ix, int rc) {
 template <int NW>
 bool kidx_host_put(uint64_t* tab, uint64_t mask, const uint64_t* rec) {
     constexpr int SW = map_slot_words<NW>();
-    Kmer<NW> k;
-    for (int q = 0; q < NW; q++) k.w[q] = rec[q];
+    const Kmer<NW> k = kidx_record_key<NW>(rec);
     for (uint64_t e = map_home<NW>(k, mask);; e = (e + 1) & mask) {
         uint64_t* sl = tab + e * SW;
         if (sl[NW + 1] == KIDX_EMPTY) {
@@ -57,62 +56,35 @@ bool kidx_host_put(uint64_t* tab, uint64_t mask, const uint64_t* rec) {
     }
 }
 
+// the ranks' serial tables (pg_kindex_build: one rank, one part): the owners counted first, every rank's table made for exactly the
+// records it owns, then the inserts
 template <int NW>
-int kidx_host_build(pg_kindex* ix, const uint64_t* records, uint64_t n_records) {
-    constexpr int SW = map_slot_words<NW>();
-    ix->keys = n_records;
-    ix->slots = map_table_slots(n_records);
-    ix->tab.assign(ix->slots * SW, 0);
-    for (uint64_t i = 0; i < n_records; i++) {
-        const uint64_t* rec = records + i * (NW + 2);
-        if (!kidx_stored(rec[NW])) continue;
-        if (!kidx_host_put<NW>(ix->tab.data(), ix->slots - 1, rec)) { pg_set_error("k-mer index: duplicate key in records"); return PG_EINVAL; }
-    }
-    return PG_OK;
-}
-
-template <int NW>
-uint32_t kidx_record_owner(const uint64_t* rec, uint32_t n) {
-    Kmer<NW> k;
-    for (int q = 0; q < NW; q++) k.w[q] = rec[q];
-    return map_owner<NW>(k, n);
-}
-
-// n serial tables: the owners counted first, every rank's table made for exactly the records it owns, then the inserts
-template <int NW>
-int kidx_host_build_sharded(pg_kindex* ix, const uint64_t* const* parts, const uint64_t* part_records, int n_parts) {
-    constexpr int SW = map_slot_words<NW>();
+int kidx_host_build(pg_kindex* ix, const uint64_t* const* parts, const uint64_t* part_records, int n_parts) {
     const uint32_t n = (uint32_t)ix->ranks.size();
     for (int p = 0; p < n_parts; p++)
-        for (uint64_t i = 0; i < part_records[p]; i++) ix->ranks[kidx_record_owner<NW>(parts[p] + i * (NW + 2), n)].keys++;
-    ix->keys = ix->slots = 0;
+        for (uint64_t i = 0; i < part_records[p]; i++) ix->ranks[map_owner<NW>(kidx_record_key<NW>(parts[p] + i * (NW + 2)), n)].keys++;
     for (KidxRank& r : ix->ranks) {
         r.slots = map_table_slots(r.keys);
-        r.tab.assign(r.slots * SW, 0);
-        ix->keys += r.keys;
-        ix->slots += r.slots;
+        r.tab.assign(r.slots * map_slot_words<NW>(), 0);
     }
     for (int p = 0; p < n_parts; p++)
         for (uint64_t i = 0; i < part_records[p]; i++) {
             const uint64_t* rec = parts[p] + i * (NW + 2);
             if (!kidx_stored(rec[NW])) continue;
-            KidxRank& r = ix->ranks[kidx_record_owner<NW>(rec, n)];
+            KidxRank& r = ix->ranks[map_owner<NW>(kidx_record_key<NW>(rec), n)];
             if (!kidx_host_put<NW>(r.tab.data(), r.slots - 1, rec)) { pg_set_error("k-mer index: duplicate key in records"); return PG_EINVAL; }
         }
     return PG_OK;
 }
 
-// kidx_host_query over the ranks' tables: every k-mer asks its owner's
+// the query kernel's walk over the ranks' tables: every k-mer asks its owner's
 template <int NW>
-void kidx_host_query_sharded(const pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
-                             uint32_t uniform_len, uint64_t* out, uint64_t* summary) {
-    const uint32_t n = (uint32_t)ix->ranks.size();
-    for (uint64_t r = 0; r < n_seqs; r++) {
-        const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, ix->K, r);
+void kidx_host_query(const pg_kindex* ix, const KidxBatch& b, uint64_t* out, uint64_t* summary) {
+    for (uint64_t r = 0; r < b.n_seqs; r++) {
+        const KidxSeq q = kidx_seq(b, ix->K, r);
         KidxSummary s = kidx_summary_none();
         map_roll<NW>(q.rd, 0, q.nk, ix->K, [&](const Kmer<NW>& ck, bool, int j) {
-            const KidxRank& rk = ix->ranks[map_owner<NW>(ck, n)];
-            const uint64_t cnt = kidx_find<NW>(rk.tab.data(), rk.slots - 1, ck);
+            const uint64_t cnt = kidx_host_find<NW>(ix, ck);
             if (out) out[q.base + j] = cnt;
             kidx_summary_add(s, cnt, j);
         });
@@ -120,27 +92,29 @@ void kidx_host_query_sharded(const pg_kindex* ix, const uint64_t* packed, const 
     }
 }
 
+// the host twin of kcor_kernel (an index in one table): the copy first, then kcor_read on every read's own words of the output
 template <int NW>
-void kidx_host_query(const pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
-                     uint32_t uniform_len, uint64_t* out, uint64_t* summary) {
-    for (uint64_t r = 0; r < n_seqs; r++) {
-        const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, ix->K, r);
-        KidxSummary s = kidx_summary_none();
-        kidx_stretch<NW>(q.rd, 0, q.nk, ix->K, ix->tab.data(), ix->slots - 1, out ? out + q.base : nullptr, s);
-        if (summary) kidx_summary_store(s, q.nk, summary + r * KIDX_SUMMARY_WORDS);
+void kcor_host_correct(const pg_kindex* ix, KidxBatch b, const KcorParams& pr, uint64_t* packed_out, uint64_t* report) {
+    const KidxRank& t = ix->ranks[0];
+    if (packed_out != b.packed) memmove(packed_out, b.packed, b.n_words * sizeof(uint64_t));
+    b.packed = packed_out;
+    for (uint64_t r = 0; r < b.n_seqs; r++) {
+        const KidxSeq q = kidx_seq(b, ix->K, r);
+        const uint64_t rep = kcor_read<NW>(packed_out + (q.rd - packed_out), q.nk, ix->K, t.tab.data(), t.slots - 1, pr);
+        if (report) report[r] = rep;
     }
 }
 
-// the host twin of kcor_kernel: the copy first, then kcor_read on every read's own words of the output
-template <int NW>
-void kcor_host_correct(const pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
-                       uint32_t uniform_len, uint64_t n_words, const KcorParams& pr, uint64_t* packed_out, uint64_t* report) {
-    if (packed_out != packed) memmove(packed_out, packed, n_words * sizeof(uint64_t));
-    for (uint64_t r = 0; r < n_seqs; r++) {
-        const KidxSeq q = kidx_seq(packed_out, word_off, kmer_base, uniform_len, ix->K, r);
-        const uint64_t rep = kcor_read<NW>(packed_out + (q.rd - packed_out), q.nk, ix->K, ix->tab.data(), ix->slots - 1, pr);
-        if (report) report[r] = rep;
-    }
+// a new index of n ranks; rank i's device is devices[i]
+pg_kindex* kidx_new(const int* devices, int n, int K, int mer127, bool cut) {
+    pg_kindex* ix = new pg_kindex();
+    ix->device = devices[0];
+    ix->K = K;
+    ix->nw = mer127 ? 4 : 2;
+    ix->cut = cut;
+    ix->ranks.resize((size_t)n);
+    for (int i = 0; i < n; i++) ix->ranks[(size_t)i].device = devices[i];
+    return ix;
 }
 
 }  // namespace
@@ -159,12 +133,10 @@ extern "C" pg_kindex* pg_kindex_build(int device, int K, int mer127, const uint6
         return pg::kidx_build_failed(nullptr, PG_EINVAL);
     }
     if (device < -1 || (!records && n_records)) { pg_set_error("pg_kindex_build: bad device or null records"); return pg::kidx_build_failed(nullptr, PG_EINVAL); }
-    pg_kindex* ix = new pg_kindex();
-    ix->device = device;
-    ix->K = K;
-    ix->nw = mer127 ? 4 : 2;
-    const int rc = device >= 0 ? pg::kidx_device_build(ix, records, n_records, stream)
-                               : mer127 ? pg::kidx_host_build<4>(ix, records, n_records) : pg::kidx_host_build<2>(ix, records, n_records);
+    pg_kindex* ix = pg::kidx_new(&device, 1, K, mer127, false);
+    int rc = PG_OK;
+    if (device >= 0) rc = pg::kidx_device_build(ix, records, n_records, stream);
+    else pg::kidx_with_nw(ix->nw, [&](auto nw) { rc = pg::kidx_host_build<decltype(nw)::value>(ix, &records, &n_records, 1); });
     return rc == PG_OK ? ix : pg::kidx_build_failed(ix, rc);
 }
 
@@ -185,32 +157,40 @@ extern "C" pg_kindex* pg_kindex_build_sharded(const int* devices, int n_devices,
         if (part_device[p] < -1) return bad("bad device of part " + std::to_string(p));
         if (host && part_device[p] != -1) return bad("part " + std::to_string(p) + " lies on a device and the host twin takes host parts only");
     }
-    pg_kindex* ix = new pg_kindex();
-    ix->device = devices[0];
-    ix->K = K;
-    ix->nw = mer127 ? 4 : 2;
-    ix->ranks.resize((size_t)n_devices);
-    for (int i = 0; i < n_devices; i++) ix->ranks[(size_t)i].device = devices[i];
-    const int rc = !host ? pg::kidx_device_build_sharded(ix, parts, part_records, part_device, n_parts, stream)
-                         : mer127 ? pg::kidx_host_build_sharded<4>(ix, parts, part_records, n_parts) : pg::kidx_host_build_sharded<2>(ix, parts, part_records, n_parts);
+    pg_kindex* ix = pg::kidx_new(devices, n_devices, K, mer127, true);
+    int rc = PG_OK;
+    if (!host) rc = pg::kidx_device_build_sharded(ix, parts, part_records, part_device, n_parts, stream);
+    else pg::kidx_with_nw(ix->nw, [&](auto nw) { rc = pg::kidx_host_build<decltype(nw)::value>(ix, parts, part_records, n_parts); });
     return rc == PG_OK ? ix : pg::kidx_build_failed(ix, rc);
+}
+
+int pg::kidx_batch_args(const char* who, const pg_kindex* ix, const KidxBatch& b, const char* noun, unsigned checks) {
+    const std::string w = std::string(who) + ": ", s = noun;
+    if (!ix) { pg_set_error(w + "null index"); return PG_EINVAL; }
+    if (b.n_seqs && !b.packed) { pg_set_error(w + "null " + s + " buffer"); return PG_EINVAL; }
+    if (b.n_seqs && !b.uniform_len && (!b.word_off || !b.kmer_base)) { pg_set_error(w + "a ragged batch needs word_off and kmer_base"); return PG_EINVAL; }
+    if (b.uniform_len > 0x7FFFFFFFu) { pg_set_error(w + "uniform_len out of range"); return PG_EINVAL; }
+    if (b.uniform_len && (checks & KIDX_ARGS_KMERS)) {
+        const uint64_t nk = (int)b.uniform_len >= ix->K ? (uint64_t)b.uniform_len - ix->K + 1 : 0;
+        if (b.n_kmers != b.n_seqs * nk) { pg_set_error(w + "n_kmers does not match n_seqs * max(0, len - K + 1)"); return PG_EINVAL; }
+    }
+    if (b.n_seqs && b.uniform_len && (checks & KIDX_ARGS_WORDS) && b.n_words < b.n_seqs * (uint64_t)((b.uniform_len + 31) / 32) + (uint64_t)ix->nw + 1) {
+        pg_set_error(w + "n_words is less than the " + s + "s' words and the nw + 1 readable words behind them");
+        return PG_EINVAL;
+    }
+    if (b.n_seqs && (checks & KIDX_ARGS_TAIL) && b.n_words < (uint64_t)ix->nw + 1) { pg_set_error(w + "n_words does not hold the nw + 1 readable words"); return PG_EINVAL; }
+    return PG_OK;
 }
 
 namespace {
 
-// what pg_kindex_query and pg_kindex_query_words ask of a batch alike
-int kidx_query_args(const char* who, const pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
-                    uint32_t uniform_len, uint64_t n_kmers, const uint64_t* out_cnt, const uint64_t* out_summary) {
-    const std::string w = std::string(who) + ": ";
-    if (!ix) { pg_set_error(w + "null index"); return PG_EINVAL; }
-    if (!out_cnt && !out_summary) { pg_set_error(w + "out_cnt and out_summary are both null"); return PG_EINVAL; }
-    if (n_seqs && !packed) { pg_set_error(w + "null sequence buffer"); return PG_EINVAL; }
-    if (n_seqs && !uniform_len && (!word_off || !kmer_base)) { pg_set_error(w + "a ragged batch needs word_off and kmer_base"); return PG_EINVAL; }
-    if (uniform_len) {
-        if (uniform_len > 0x7FFFFFFFu) { pg_set_error(w + "uniform_len out of range"); return PG_EINVAL; }
-        const uint64_t nk = (int)uniform_len >= ix->K ? (uint64_t)uniform_len - ix->K + 1 : 0;
-        if (n_kmers != n_seqs * nk) { pg_set_error(w + "n_kmers does not match n_seqs * max(0, len - K + 1)"); return PG_EINVAL; }
-    }
+// pg_kindex_query (an index in one table: n_words is not stated) and pg_kindex_query_words (a cut one: KIDX_ARGS_WORDS too)
+int kidx_query(const char* who, pg_kindex* ix, const pg::KidxBatch& b, unsigned checks, int wave, uint64_t* out_cnt, uint64_t* out_summary, void* stream) {
+    if (ix && !out_cnt && !out_summary) { pg_set_error(std::string(who) + ": out_cnt and out_summary are both null"); return PG_EINVAL; }
+    if (int rc = pg::kidx_batch_args(who, ix, b, "sequence", checks)) return rc;
+    if (ix->device >= 0)
+        return ix->cut ? pg::kidx_device_query_sharded(ix, b, wave, out_cnt, out_summary, stream) : pg::kidx_device_query(ix, b, wave, out_cnt, out_summary, stream);
+    pg::kidx_with_nw(ix->nw, [&](auto nw) { pg::kidx_host_query<decltype(nw)::value>(ix, b, out_cnt, out_summary); });
     return PG_OK;
 }
 
@@ -219,38 +199,26 @@ int kidx_query_args(const char* who, const pg_kindex* ix, const uint64_t* packed
 extern "C" int pg_kindex_query_words(pg_kindex* ix, const uint64_t* packed, uint64_t n_words, const uint64_t* word_off, const uint64_t* kmer_base,
                                      uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* out_cnt, uint64_t* out_summary,
                                      void* stream) {
-    if (ix && ix->ranks.empty()) return pg_kindex_query(ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_kmers, wave, out_cnt, out_summary, stream);
-    if (int rc = kidx_query_args("pg_kindex_query_words", ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_kmers, out_cnt, out_summary)) return rc;
-    if (n_seqs && uniform_len && n_words < n_seqs * (uint64_t)((uniform_len + 31) / 32) + (uint64_t)ix->nw + 1) {
-        pg_set_error("pg_kindex_query_words: n_words is less than the sequences' words and the nw + 1 readable words behind them");
-        return PG_EINVAL;
-    }
-    if (ix->device >= 0)
-        return pg::kidx_device_query_sharded(ix, packed, n_words, word_off, kmer_base, n_seqs, uniform_len, n_kmers, wave, out_cnt, out_summary, stream);
-    if (ix->nw == 4) pg::kidx_host_query_sharded<4>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
-    else pg::kidx_host_query_sharded<2>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
-    return PG_OK;
+    if (ix && !ix->cut) return pg_kindex_query(ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_kmers, wave, out_cnt, out_summary, stream);
+    return kidx_query("pg_kindex_query_words", ix, pg::KidxBatch{packed, word_off, kmer_base, n_seqs, uniform_len, n_words, n_kmers},
+                      pg::KIDX_ARGS_KMERS | pg::KIDX_ARGS_WORDS, wave, out_cnt, out_summary, stream);
 }
 
 extern "C" int pg_kindex_query(pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
                                uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* out_cnt, uint64_t* out_summary, void* stream) {
-    if (!ix) { pg_set_error("pg_kindex_query: null index"); return PG_EINVAL; }
-    if (!ix->ranks.empty()) {
+    if (ix && ix->cut) {
         pg_set_error("pg_kindex_query: the index is cut over ranks and a batch has to be copied to them: call pg_kindex_query_words, which takes the batch's words");
         return PG_EINVAL;
     }
-    if (int rc = kidx_query_args("pg_kindex_query", ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_kmers, out_cnt, out_summary)) return rc;
-    if (ix->device >= 0) return pg::kidx_device_query(ix, packed, word_off, kmer_base, n_seqs, uniform_len, wave, out_cnt, out_summary, stream);
-    if (ix->nw == 4) pg::kidx_host_query<4>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
-    else pg::kidx_host_query<2>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, out_cnt, out_summary);
-    return PG_OK;
+    return kidx_query("pg_kindex_query", ix, pg::KidxBatch{packed, word_off, kmer_base, n_seqs, uniform_len, 0, n_kmers}, pg::KIDX_ARGS_KMERS, wave, out_cnt,
+                      out_summary, stream);
 }
 
 extern "C" int pg_kindex_correct(pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
                                  uint32_t uniform_len, uint64_t n_words, uint32_t min_cov, uint32_t max_fixes, uint32_t min_run,
                                  uint64_t* packed_out, uint64_t* out_report, void* stream) {
     if (!ix) { pg_set_error("pg_kindex_correct: null index"); return PG_EINVAL; }
-    if (!ix->ranks.empty()) {
+    if (ix->cut) {
         pg_set_error("pg_kindex_correct: the index is cut over ranks; a read's trials are chains of dependent lookups, which merged rows cannot answer: "
                      "correct against an index in one table");
         return PG_ESTATE;
@@ -258,37 +226,16 @@ extern "C" int pg_kindex_correct(pg_kindex* ix, const uint64_t* packed, const ui
     if (!min_cov || !min_run || max_fixes > pg::KCOR_MAX_FIXES) { pg_set_error("pg_kindex_correct: min_cov and min_run are at least 1, max_fixes at most 255"); return PG_EINVAL; }
     if (!packed_out) { pg_set_error("pg_kindex_correct: null packed_out"); return PG_EINVAL; }
     if (!n_seqs) return PG_OK;
-    if (!packed) { pg_set_error("pg_kindex_correct: null read buffer"); return PG_EINVAL; }
-    if (!uniform_len && (!word_off || !kmer_base)) { pg_set_error("pg_kindex_correct: a ragged batch needs word_off and kmer_base"); return PG_EINVAL; }
-    if (uniform_len > 0x7FFFFFFFu) { pg_set_error("pg_kindex_correct: uniform_len out of range"); return PG_EINVAL; }
-    if (uniform_len && n_words < n_seqs * (uint64_t)((uniform_len + 31) / 32) + (uint64_t)ix->nw + 1) {
-        pg_set_error("pg_kindex_correct: n_words is less than the reads' words and the nw + 1 readable words behind them");
-        return PG_EINVAL;
-    }
+    const pg::KidxBatch b{packed, word_off, kmer_base, n_seqs, uniform_len, n_words, 0};
+    if (int rc = pg::kidx_batch_args("pg_kindex_correct", ix, b, "read", pg::KIDX_ARGS_WORDS)) return rc;
     const pg::KcorParams pr{min_cov, max_fixes, min_run};
-    if (ix->device >= 0) return pg::kcor_device_correct(ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_words, pr, packed_out, out_report, stream);
-    if (ix->nw == 4) pg::kcor_host_correct<4>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_words, pr, packed_out, out_report);
-    else pg::kcor_host_correct<2>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, n_words, pr, packed_out, out_report);
+    if (ix->device >= 0) return pg::kcor_device_correct(ix, b, pr, packed_out, out_report, stream);
+    pg::kidx_with_nw(ix->nw, [&](auto nw) { pg::kcor_host_correct<decltype(nw)::value>(ix, b, pr, packed_out, out_report); });
     return PG_OK;
-}
-
-extern "C" int pg_kindex_info(const pg_kindex* ix, uint64_t out[4]) {
-    if (!ix || !out) { pg_set_error("pg_kindex_info: null argument"); return PG_EINVAL; }
-    out[0] = ix->keys;
-    out[1] = ix->slots;
-    out[2] = ix->slots * (uint64_t)(ix->nw + 2) * sizeof(uint64_t);             // (cut over ranks: the sum of their tables)
-    out[3] = (uint64_t)(int64_t)ix->device;
-    return PG_OK;
-}
-
-extern "C" int pg_kindex_ranks(const pg_kindex* ix) {
-    if (!ix) { pg_set_error("pg_kindex_ranks: null index"); return PG_EINVAL; }
-    return (int)ix->ranks.size();
 }
 
 extern "C" int pg_kindex_rank_info(const pg_kindex* ix, int rank, uint64_t out[4]) {
     if (!ix || !out) { pg_set_error("pg_kindex_rank_info: null argument"); return PG_EINVAL; }
-    if (ix->ranks.empty() && rank == 0) return pg_kindex_info(ix, out);
     if (rank < 0 || (size_t)rank >= ix->ranks.size()) { pg_set_error("pg_kindex_rank_info: no such rank"); return PG_EINVAL; }
     const pg::KidxRank& r = ix->ranks[(size_t)rank];
     out[0] = r.keys;
@@ -298,10 +245,28 @@ extern "C" int pg_kindex_rank_info(const pg_kindex* ix, int rank, uint64_t out[4
     return PG_OK;
 }
 
+// the sums over the ranks' tables, on the lead's device
+extern "C" int pg_kindex_info(const pg_kindex* ix, uint64_t out[4]) {
+    if (!ix || !out) { pg_set_error("pg_kindex_info: null argument"); return PG_EINVAL; }
+    out[0] = out[1] = out[2] = 0;
+    for (int i = 0; i < (int)ix->ranks.size(); i++) {
+        uint64_t r[4];
+        (void)pg_kindex_rank_info(ix, i, r);
+        for (int q = 0; q < 3; q++) out[q] += r[q];
+    }
+    out[3] = (uint64_t)(int64_t)ix->device;
+    return PG_OK;
+}
+
+extern "C" int pg_kindex_ranks(const pg_kindex* ix) {
+    if (!ix) { pg_set_error("pg_kindex_ranks: null index"); return PG_EINVAL; }
+    return ix->cut ? (int)ix->ranks.size() : 0;
+}
+
 extern "C" int pg_kindex_query_times(pg_kindex* ix, double out[4]) {
     if (!ix || !out) { pg_set_error("pg_kindex_query_times: null argument"); return PG_EINVAL; }
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (ix->ranks.empty() || ix->device < 0) return PG_OK;
+    if (!ix->cut || ix->device < 0) return PG_OK;
     return pg::kidx_device_query_times(ix, out);
 }
 

@@ -1,7 +1,9 @@
 // kindex_kernels.hip -- the k-mer index on the GPU (kindex.hpp: layout, sequence rules, the shared read side).
 //
 //   kidx_build_kernel       a lane per record of a device array in export format ((NW + 2) words a record, any order: what pg_export,
-//                           pg_export_peek, pg_export_take and pg_sort_records leave).  The protocol is map_index_kernel's
+//                           pg_export_peek, pg_export_take and pg_sort_records leave), for rank `me` of n: the records it owns
+//                           (map_owner); n == 1, pg_kindex_build's table and a one-rank cut alike, skips the owner under that
+//                           launch-uniform condition.  The protocol is map_index_kernel's
 //                           (map_kernels.hip): a new key is claimed with a CAS on its state word, key and value are written, and the
 //                           state is published with a release store; a lane that meets a claimed slot looks at the same slot again on its
 //                           next trip round the loop -- nobody waits inside a branch for a lane of its own wavefront.  The trips spent on
@@ -9,23 +11,23 @@
 //                           with PG_ESPIN.  The keys are distinct by contract: a lane that meets its own key published raises
 //                           KIDX_FLAG_DUP, leaves the slot as it is, and the build fails with PG_EINVAL.  A record the -d filter deleted
 //                           (kidx_stored, kindex.hpp) is passed over.
-//   kidx_query_kernel       a lane per sequence, for read-sized sequences: kidx_stretch over the whole sequence, the summary in registers.
-//   kidx_query_wave_kernel  a wavefront per sequence, four sequences a 256-thread workgroup, for contig-sized sequences: lane l takes
-//                           ceil(nk / 64) consecutive k-mers (one read_kmer, then rolling: map_read_wave_kernel's split), the summary
-//                           through a __shfl_xor butterfly, lane 0 writes it.  No LDS, no workgroup barrier: a wave without a sequence
+//   kidx_query_kernel       <NW, WAVE>, an index in one table.  The lane form: a lane per sequence, for read-sized sequences:
+//                           kidx_stretch over the whole sequence, the summary in registers.  The wave form: a wavefront per sequence,
+//                           four sequences a 256-thread workgroup, for contig-sized sequences: lane l takes ceil(nk / 64) consecutive
+//                           k-mers (kidx_wave_split: one read_kmer, then rolling), the summary through a __shfl_xor butterfly
+//                           (kidx_summary_wave_reduce), lane 0 writes it.  No LDS, no workgroup barrier: a wave without a sequence
 //                           just ends.
 //   kcor_kernel             a lane per read of a batch that already lies in the output buffer: kcor_read (kcorrect.hpp) on the lane's own
-//                           words, in global memory -- the first pass over the read as given is kidx_query_kernel's walk, and a read
+//                           words, in global memory -- the first pass over the read as given is the query kernel's lane walk, and a read
 //                           without a weak k-mer ends there; the lanes of a wave diverge in the trials.
 // The index cut over ranks (kindex.hpp; pg_kindex_build_sharded, pg_kindex_query_words):
 //   kidx_count_owners_kernel   a lane per record of a device part, on the device where the part lies: the owners of all n ranks at once
 //                              into an LDS histogram (n <= 256 bins: 1 KB, zeroed and flushed per workgroup), one global atomicAdd per
 //                              non-zero bin per workgroup.  Deleted records are counted: owned_i sizes the table as pg_kindex_build does.
-//   kidx_build_owned_kernel    kidx_build_kernel for the records rank `me` owns: kidx_insert, its spin cap and its flags as they are.
-//   kidx_probe_owned_kernel    the lane and wave splits of the two query kernels; an owned canonical k-mer's answer goes into the rank's
+//   kidx_probe_owned_kernel    the lane and wave splits of the query kernel; an owned canonical k-mer's answer goes into the rank's
 //                              zeroed rows, every other word is left as it is.  No summary.
 //   kidx_summary_rows_kernel   a wavefront per sequence, four a workgroup, over the merged rows: lanes stride the row (j = lane, lane + 64,
-//                              ...: coalesced), the query wave kernel's butterfly, lane 0 stores.  Sums and minima: the same words.
+//                              ...: coalesced), the query kernel's butterfly, lane 0 stores.  Sums and minima: the same words.
 // The merge is map_rows_merge_kernel (map_kernels.hip, through map_rows_merge).
 // The trim (ktrim.hpp; pg_kindex_trim):
 //   ktrim_span_kernel          a lane per read: kidx_query_kernel's walk and launch shape, the current and the best run of solid k-mers in
@@ -39,7 +41,9 @@
 //   ktrim_pack_kernel          a lane per output word, the tail's nw + 1 zero words included: the kept read by binary search in
 //                              word_off_out, the word by ktrim_pack_word.  The launch covers the batch's n_words, which the result never
 //                              passes; how many of those lanes have a word is read from the totals on the device
-// Both query kernels wait for one random slot read per k-mer (32 B a slot in the 63-mer build, 48 B in the 127-mer one) of a table that
+// A batch reaches every kernel as one KidxBatch by value (kindex.hpp), and the host side builds a table the same way whether it is
+// pg_kindex_build's or a rank's of a cut (kidx_rank_table, kidx_rank_insert, kidx_build_verdict).
+// Both forms of the query kernel wait for one random slot read per k-mer (32 B a slot in the 63-mer build, 48 B in the 127-mer one) of a table that
 // is many times the L2; the roll is arithmetic hidden under it.  The measured times, the cut over ranks included, are in DESIGN.md §10.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -103,51 +107,37 @@ __device__ __forceinline__ void kidx_insert(uint64_t* tab, uint64_t mask, const 
     }
 }
 
+// rank `me` of n keeps the records with map_owner(key, n) == me; n == 1 (uniform over the launch): every record, and no owner is worked out
 template <int NW>
-__global__ __launch_bounds__(256) void kidx_build_kernel(const uint64_t* __restrict__ records, uint64_t n_records, uint64_t* tab, uint64_t mask,
-                                                         uint32_t* flags) {
+__global__ __launch_bounds__(256) void kidx_build_kernel(const uint64_t* __restrict__ records, uint64_t n_records, uint32_t n, uint32_t me,
+                                                         uint64_t* tab, uint64_t mask, uint32_t* flags) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_records) return;
     const uint64_t* rec = records + i * (NW + 2);
     const uint64_t cnt = rec[NW];
     if (!kidx_stored(cnt)) return;                 // deleted by the -d filter: reads as 0
-    Kmer<NW> k;
-#pragma unroll
-    for (int q = 0; q < NW; q++) k.w[q] = rec[q];
+    const Kmer<NW> k = kidx_record_key<NW>(rec);
+    if (n != 1 && map_owner<NW>(k, n) != me) return;
     kidx_insert<NW>(tab, mask, k, cnt, flags);
 }
 
-template <int NW>
-__global__ __launch_bounds__(256) void kidx_query_kernel(const uint64_t* __restrict__ packed, const uint64_t* __restrict__ word_off,
-                                                         const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len, int K,
-                                                         const uint64_t* __restrict__ tab, uint64_t mask, uint64_t* __restrict__ out,
-                                                         uint64_t* __restrict__ summary) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_seqs) return;
-    const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, K, r);
-    KidxSummary s = kidx_summary_none();
-    kidx_stretch<NW>(q.rd, 0, q.nk, K, tab, mask, out ? out + q.base : nullptr, s);
-    if (summary) kidx_summary_store(s, q.nk, summary + r * KIDX_SUMMARY_WORDS);
+// the sequence of this lane (a lane a sequence) or of its wave (KIDX_WAVES sequences a 256-thread workgroup)
+template <bool WAVE>
+__device__ __forceinline__ uint64_t kidx_seq_index() {
+    return WAVE ? (uint64_t)blockIdx.x * KIDX_WAVES + (threadIdx.x >> 6) : (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 }
 
-template <int NW>
-__global__ __launch_bounds__(256) void kidx_query_wave_kernel(const uint64_t* __restrict__ packed, const uint64_t* __restrict__ word_off,
-                                                              const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len,
-                                                              int K, const uint64_t* __restrict__ tab, uint64_t mask,
-                                                              uint64_t* __restrict__ out, uint64_t* __restrict__ summary) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t r = (uint64_t)blockIdx.x * KIDX_WAVES + wave;
-    if (r >= n_seqs) return;                       // (the whole wave; no workgroup barrier follows)
-    const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, K, r);
-    KidxSummary s = kidx_summary_none();
-    if (q.nk) {                                    // (wave-uniform)
-        const int per = (q.nk + 63) / 64;
-        const int64_t first = (int64_t)lane * per;                                      // (64 * per can pass 2^31 where nk is close to it)
-        const int j0 = first < q.nk ? (int)first : q.nk, j1 = first + per < q.nk ? (int)(first + per) : q.nk;
-        kidx_stretch<NW>(q.rd, j0, j1, K, tab, mask, out ? out + q.base : nullptr, s);
-    }
-    if (!summary) return;
-    for (int d = 32; d > 0; d >>= 1) {             // (every lane of the wave is here)
+// a wave's split of a sequence of nk k-mers: lane l takes the ceil(nk / 64) consecutive k-mers j0 .. j1 - 1 (map_read_wave_kernel's split)
+__device__ __forceinline__ void kidx_wave_split(int nk, int lane, int* j0, int* j1) {
+    const int per = (nk + 63) / 64;
+    const int64_t first = (int64_t)lane * per;     // (64 * per can pass 2^31 where nk is close to it)
+    *j0 = first < nk ? (int)first : nk;
+    *j1 = first + per < nk ? (int)(first + per) : nk;
+}
+
+// the lanes' summaries merged through a __shfl_xor butterfly: every lane of the wave calls it, and every lane ends with the wave's
+__device__ __forceinline__ void kidx_summary_wave_reduce(KidxSummary& s) {
+    for (int d = 32; d > 0; d >>= 1) {
         KidxSummary o;
         o.present = __shfl_xor(s.present, d);
         o.cov_sum = __shfl_xor(s.cov_sum, d);
@@ -155,29 +145,35 @@ __global__ __launch_bounds__(256) void kidx_query_wave_kernel(const uint64_t* __
         o.first_absent = __shfl_xor(s.first_absent, d);
         kidx_summary_merge(s, o);
     }
-    if (lane == 0) kidx_summary_store(s, q.nk, summary + r * KIDX_SUMMARY_WORDS);
+}
+
+template <int NW, bool WAVE>
+__global__ __launch_bounds__(256) void kidx_query_kernel(KidxBatch b, int K, const uint64_t* __restrict__ tab, uint64_t mask, uint64_t* __restrict__ out,
+                                                         uint64_t* __restrict__ summary) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t r = kidx_seq_index<WAVE>();
+    if (r >= b.n_seqs) return;                     // (WAVE: the whole wave; no workgroup barrier follows)
+    const KidxSeq q = kidx_seq(b, K, r);
+    KidxSummary s = kidx_summary_none();
+    int j0 = 0, j1 = q.nk;
+    if (WAVE) kidx_wave_split(q.nk, lane, &j0, &j1);
+    if (!WAVE || q.nk) kidx_stretch<NW>(q.rd, j0, j1, K, tab, mask, out ? out + q.base : nullptr, s);   // (q.nk: wave-uniform)
+    if (!summary) return;
+    if (WAVE) kidx_summary_wave_reduce(s);         // (every lane of the wave is here)
+    if (!WAVE || lane == 0) kidx_summary_store(s, q.nk, summary + r * KIDX_SUMMARY_WORDS);
 }
 
 template <int NW>
-__global__ __launch_bounds__(256) void kcor_kernel(uint64_t* packed_out, const uint64_t* __restrict__ word_off, const uint64_t* __restrict__ kmer_base,
-                                                   uint64_t n_seqs, uint32_t uniform_len, int K, const uint64_t* __restrict__ tab, uint64_t mask,
-                                                   KcorParams pr, uint64_t* __restrict__ report) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_seqs) return;
-    const KidxSeq q = kidx_seq(packed_out, word_off, kmer_base, uniform_len, K, r);
-    const uint64_t rep = kcor_read<NW>(packed_out + (q.rd - packed_out), q.nk, K, tab, mask, pr);
+__global__ __launch_bounds__(256) void kcor_kernel(KidxBatch b, int K, const uint64_t* __restrict__ tab, uint64_t mask, KcorParams pr,
+                                                   uint64_t* __restrict__ report) {
+    const uint64_t r = kidx_seq_index<false>();
+    if (r >= b.n_seqs) return;
+    const KidxSeq q = kidx_seq(b, K, r);           // (b.packed is the output buffer, which already holds the batch)
+    const uint64_t rep = kcor_read<NW>(const_cast<uint64_t*>(q.rd), q.nk, K, tab, mask, pr);
     if (report) report[r] = rep;
 }
 
-// ---- the index cut over ranks: rank `me` of n keeps the records with map_owner(key, n) == me ----
-template <int NW>
-__device__ __forceinline__ Kmer<NW> kidx_record_key(const uint64_t* rec) {
-    Kmer<NW> k;
-#pragma unroll
-    for (int q = 0; q < NW; q++) k.w[q] = rec[q];
-    return k;
-}
-
+// ---- the index cut over ranks ----
 template <int NW>
 __global__ __launch_bounds__(256) void kidx_count_owners_kernel(const uint64_t* __restrict__ records, uint64_t n_records, uint32_t n,
                                                                 unsigned long long* counts) {
@@ -191,85 +187,54 @@ __global__ __launch_bounds__(256) void kidx_count_owners_kernel(const uint64_t* 
         if (const uint32_t c = bins[b]) atomicAdd(counts + b, (unsigned long long)c);
 }
 
-template <int NW>
-__global__ __launch_bounds__(256) void kidx_build_owned_kernel(const uint64_t* __restrict__ records, uint64_t n_records, uint32_t n, uint32_t me,
-                                                               uint64_t* tab, uint64_t mask, uint32_t* flags) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_records) return;
-    const uint64_t* rec = records + i * (NW + 2);
-    const uint64_t cnt = rec[NW];
-    if (!kidx_stored(cnt)) return;                 // deleted by the -d filter: reads as 0
-    const Kmer<NW> k = kidx_record_key<NW>(rec);
-    if (map_owner<NW>(k, n) != me) return;
-    kidx_insert<NW>(tab, mask, k, cnt, flags);
-}
-
 template <int NW, bool WAVE>
-__global__ __launch_bounds__(256) void kidx_probe_owned_kernel(const uint64_t* __restrict__ packed, const uint64_t* __restrict__ word_off,
-                                                               const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len,
-                                                               int K, uint32_t n, uint32_t me, const uint64_t* __restrict__ tab, uint64_t mask,
+__global__ __launch_bounds__(256) void kidx_probe_owned_kernel(KidxBatch b, int K, uint32_t n, uint32_t me, const uint64_t* __restrict__ tab, uint64_t mask,
                                                                uint64_t* __restrict__ rows) {
-    const uint64_t r = WAVE ? (uint64_t)blockIdx.x * KIDX_WAVES + (threadIdx.x >> 6) : (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_seqs) return;
-    const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, K, r);
+    const uint64_t r = kidx_seq_index<WAVE>();
+    if (r >= b.n_seqs) return;
+    const KidxSeq q = kidx_seq(b, K, r);
     int j0 = 0, j1 = q.nk;
-    if (WAVE) {                                    // kidx_query_wave_kernel's split
-        const int per = (q.nk + 63) / 64;
-        const int64_t first = (int64_t)(threadIdx.x & 63) * per;
-        j0 = first < q.nk ? (int)first : q.nk;
-        j1 = first + per < q.nk ? (int)(first + per) : q.nk;
-    }
+    if (WAVE) kidx_wave_split(q.nk, threadIdx.x & 63, &j0, &j1);
     uint64_t* row = rows + q.base;
     map_roll<NW>(q.rd, j0, j1, K, [&](const Kmer<NW>& ck, bool, int j) {
         if (map_owner<NW>(ck, n) == me) row[j] = kidx_find<NW>(tab, mask, ck);
     });
 }
 
-__global__ __launch_bounds__(256) void kidx_summary_rows_kernel(const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len, int K,
-                                                                const uint64_t* __restrict__ rows, uint64_t* __restrict__ summary) {
+__global__ __launch_bounds__(256) void kidx_summary_rows_kernel(KidxBatch b, int K, const uint64_t* __restrict__ rows, uint64_t* __restrict__ summary) {
     const int lane = threadIdx.x & 63;
-    const uint64_t r = (uint64_t)blockIdx.x * KIDX_WAVES + (threadIdx.x >> 6);
-    if (r >= n_seqs) return;                       // (the whole wave; no workgroup barrier follows)
-    // kidx_seq's base and k-mers; the sequence's words are not wanted here
-    const int nk = uniform_len ? ((int)uniform_len >= K ? (int)uniform_len - K + 1 : 0) : (int)(kmer_base[r + 1] - kmer_base[r]);
-    const uint64_t* row = rows + (uniform_len ? r * (uint64_t)nk : kmer_base[r]);
+    const uint64_t r = kidx_seq_index<true>();
+    if (r >= b.n_seqs) return;                     // (the whole wave; no workgroup barrier follows)
+    const KidxRow w = kidx_row(b, K, r);
+    const uint64_t* row = rows + w.base;
     KidxSummary s = kidx_summary_none();
-    for (int64_t j = lane; j < nk; j += 64) kidx_summary_add(s, row[j], (int)j);     // (j + 64 can pass 2^31 where nk is close to it)
-    for (int d = 32; d > 0; d >>= 1) {             // (every lane of the wave is here)
-        KidxSummary o;
-        o.present = __shfl_xor(s.present, d);
-        o.cov_sum = __shfl_xor(s.cov_sum, d);
-        o.cov_min = __shfl_xor(s.cov_min, d);
-        o.first_absent = __shfl_xor(s.first_absent, d);
-        kidx_summary_merge(s, o);
-    }
-    if (lane == 0) kidx_summary_store(s, nk, summary + r * KIDX_SUMMARY_WORDS);
+    for (int64_t j = lane; j < w.nk; j += 64) kidx_summary_add(s, row[j], (int)j);   // (j + 64 can pass 2^31 where nk is close to it)
+    kidx_summary_wave_reduce(s);                   // (every lane of the wave is here)
+    if (lane == 0) kidx_summary_store(s, w.nk, summary + r * KIDX_SUMMARY_WORDS);
 }
 
 // ---- the trim: spans, the scan of the kept reads' counts, the pack ----
 template <int NW>
-__global__ __launch_bounds__(256) void ktrim_span_kernel(const uint64_t* __restrict__ packed, const uint64_t* __restrict__ word_off,
-                                                         const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len, int K,
-                                                         const uint64_t* __restrict__ tab, uint64_t mask, uint32_t min_cov, uint64_t* __restrict__ span) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_seqs) return;
-    const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, K, r);
+__global__ __launch_bounds__(256) void ktrim_span_kernel(KidxBatch b, int K, const uint64_t* __restrict__ tab, uint64_t mask, uint32_t min_cov,
+                                                         uint64_t* __restrict__ span) {
+    const uint64_t r = kidx_seq_index<false>();
+    if (r >= b.n_seqs) return;
+    const KidxSeq q = kidx_seq(b, K, r);
     span[r] = ktrim_span_probe<NW>(q.rd, q.nk, K, tab, mask, min_cov);
 }
 
-__global__ __launch_bounds__(256) void ktrim_span_rows_kernel(const uint64_t* __restrict__ kmer_base, uint64_t n_seqs, uint32_t uniform_len, int K,
-                                                              const uint64_t* __restrict__ rows, uint32_t min_cov, uint64_t* __restrict__ span) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_seqs) return;
-    const int nk = ktrim_nk(kmer_base, uniform_len, K, r);
-    span[r] = ktrim_span_row(rows + (uniform_len ? r * (uint64_t)nk : kmer_base[r]), nk, K, min_cov);
+__global__ __launch_bounds__(256) void ktrim_span_rows_kernel(KidxBatch b, int K, const uint64_t* __restrict__ rows, uint32_t min_cov,
+                                                              uint64_t* __restrict__ span) {
+    const uint64_t r = kidx_seq_index<false>();
+    if (r >= b.n_seqs) return;
+    const KidxRow w = kidx_row(b, K, r);
+    span[r] = ktrim_span_row(rows + w.base, w.nk, K, min_cov);
 }
 
 // read r's counts; a lane past the batch has none
-__device__ __forceinline__ KtrimCounts ktrim_lane_counts(const uint64_t* span, const uint64_t* kmer_base, uint64_t n_seqs, uint32_t uniform_len,
-                                                         int K, uint32_t min_len, uint64_t r) {
-    if (r >= n_seqs) return KtrimCounts{{0, 0, 0, 0}};
-    return ktrim_counts(span[r], ktrim_nk(kmer_base, uniform_len, K, r), K, min_len);
+__device__ __forceinline__ KtrimCounts ktrim_lane_counts(const uint64_t* span, const KidxBatch& b, int K, uint32_t min_len, uint64_t r) {
+    if (r >= b.n_seqs) return KtrimCounts{{0, 0, 0, 0}};
+    return ktrim_counts(span[r], kidx_row(b, K, r).nk, K, min_len);
 }
 
 // The inclusive scan of the lanes' counts over a 256-thread workgroup: inside a wave by __shfl_up, the four waves' sums through LDS.
@@ -300,10 +265,10 @@ __device__ __forceinline__ KtrimCounts ktrim_block_scan(KtrimCounts& c, uint64_t
     return all;
 }
 
-__global__ __launch_bounds__(256) void ktrim_block_sums_kernel(const uint64_t* __restrict__ span, const uint64_t* __restrict__ kmer_base, uint64_t n_seqs,
-                                                               uint32_t uniform_len, int K, uint32_t min_len, uint64_t* __restrict__ sums) {
+__global__ __launch_bounds__(256) void ktrim_block_sums_kernel(const uint64_t* __restrict__ span, KidxBatch b, int K, uint32_t min_len,
+                                                               uint64_t* __restrict__ sums) {
     __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
-    KtrimCounts c = ktrim_lane_counts(span, kmer_base, n_seqs, uniform_len, K, min_len, (uint64_t)blockIdx.x * 256 + threadIdx.x);
+    KtrimCounts c = ktrim_lane_counts(span, b, K, min_len, (uint64_t)blockIdx.x * 256 + threadIdx.x);
     const KtrimCounts all = ktrim_block_scan(c, wave_sums);
     if (threadIdx.x < KTRIM_COUNTS) sums[(uint64_t)blockIdx.x * KTRIM_COUNTS + threadIdx.x] = all.c[threadIdx.x];
 }
@@ -334,13 +299,13 @@ __global__ __launch_bounds__(256) void ktrim_scan_sums_kernel(uint64_t* __restri
     }
 }
 
-__global__ __launch_bounds__(256) void ktrim_scatter_kernel(const uint64_t* __restrict__ span, const uint64_t* __restrict__ kmer_base, uint64_t n_seqs,
-                                                            uint32_t uniform_len, int K, uint32_t min_len, const uint64_t* __restrict__ sums,
+__global__ __launch_bounds__(256) void ktrim_scatter_kernel(const uint64_t* __restrict__ span, KidxBatch b, int K, uint32_t min_len,
+                                                            const uint64_t* __restrict__ sums,
                                                             uint64_t* __restrict__ word_off_out, uint64_t* __restrict__ kmer_base_out,
                                                             uint64_t* __restrict__ src_out) {
     __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
     const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const KtrimCounts own = ktrim_lane_counts(span, kmer_base, n_seqs, uniform_len, K, min_len, r);
+    const KtrimCounts own = ktrim_lane_counts(span, b, K, min_len, r);
     KtrimCounts c = own;
     (void)ktrim_block_scan(c, wave_sums);
     if (!own.c[0]) return;                         // (no barrier follows)
@@ -377,13 +342,6 @@ __global__ __launch_bounds__(256) void ktrim_pack_kernel(const uint64_t* __restr
 
 namespace {
 
-// f(std::integral_constant<int, NW>) for an index's flavour
-template <typename F>
-void kidx_with_nw(int nw, F f) {
-    if (nw == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 4>{});
-}
-
 int kidx_set_device(int dev) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { pg_set_error("k-mer index: no HIP device"); return PG_ENODEV; }
@@ -392,33 +350,53 @@ int kidx_set_device(int dev) {
     return PG_OK;
 }
 
-}  // namespace
+// the workgroups of a launch over n items, `per` of them a workgroup; `what` is too many or too large for one launch
+int kidx_launch_blocks(uint64_t n, unsigned per, const char* what, dim3* grid) {
+    const uint64_t blocks = (n + per - 1) / per;
+    if (blocks > 0x7FFFFFFFULL) { pg_set_error(std::string("k-mer index: ") + what + " for one launch"); return PG_EINVAL; }
+    *grid = dim3((unsigned)blocks);
+    return PG_OK;
+}
+int kidx_record_blocks(uint64_t n_records, dim3* grid) { return kidx_launch_blocks(n_records, 256, "too many records", grid); }
+// a lane a sequence, or a wave a sequence
+int kidx_batch_blocks(uint64_t n_seqs, bool wave, dim3* grid) { return kidx_launch_blocks(n_seqs, wave ? KIDX_WAVES : 256, "batch too large", grid); }
 
-int kidx_device_build(::pg_kindex* ix, const uint64_t* d_records, uint64_t n_records, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = kidx_set_device(ix->device)) return rc;
-    if ((n_records + 255) / 256 > 0x7FFFFFFFULL) { pg_set_error("k-mer index: too many records for one launch"); return PG_EINVAL; }
-    arena_pin_for_process(ix->device);
-    ix->keys = n_records;
-    ix->slots = map_table_slots(n_records);
-    const size_t bytes = kidx_table_bytes(n_records, ix->nw);
-    if (arena_malloc(&ix->d_tab, bytes) != hipSuccess || arena_malloc(&ix->d_flags, sizeof(uint32_t)) != hipSuccess) {
+// f(std::integral_constant<int, NW>) launches a kernel of the index's flavour
+template <typename F>
+int kidx_launch(const ::pg_kindex* ix, F f) {
+    kidx_with_nw(ix->nw, f);
+    KIDX_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+// ---- a rank's build, for pg_kindex_build's one table and a cut's ranks alike: on the rank's device, on stream st ----
+// the table for r.keys records and the flags, from the arena, zeroed
+int kidx_rank_table(KidxRank& r, int nw, hipStream_t st) {
+    r.slots = map_table_slots(r.keys);
+    const size_t bytes = kidx_table_bytes(r.keys, nw);
+    if (arena_malloc(&r.d_tab, bytes) != hipSuccess || arena_malloc(&r.d_flags, sizeof(uint32_t)) != hipSuccess) {
         (void)hipGetLastError();
-        pg_set_error("k-mer index: out of device memory for a table of " + std::to_string(ix->slots) + " slots (" + std::to_string(bytes >> 20) + " MiB)");
+        pg_set_error("k-mer index: out of device memory for a table of " + std::to_string(r.slots) + " slots (" + std::to_string(bytes >> 20) + " MiB)");
         return PG_ENOMEM;
     }
-    KIDX_HIP(hipMemsetAsync(ix->d_tab, 0, bytes, st));
-    KIDX_HIP(hipMemsetAsync(ix->d_flags, 0, sizeof(uint32_t), st));
-    if (n_records) {
-        const dim3 grid((unsigned)((n_records + 255) / 256)), block(256);
-        kidx_with_nw(ix->nw, [&](auto nw) {
-            hipLaunchKernelGGL((kidx_build_kernel<decltype(nw)::value>), grid, block, 0, st, d_records, n_records, ix->d_tab, ix->slots - 1, ix->d_flags);
-        });
-        KIDX_HIP(hipGetLastError());
-    }
-    uint32_t flags = 0;
-    KIDX_HIP(hipMemcpyAsync(&flags, ix->d_flags, sizeof flags, hipMemcpyDeviceToHost, st));
-    KIDX_HIP(hipStreamSynchronize(st));
+    KIDX_HIP(hipMemsetAsync(r.d_tab, 0, bytes, st));
+    KIDX_HIP(hipMemsetAsync(r.d_flags, 0, sizeof(uint32_t), st));
+    return PG_OK;
+}
+
+// the m records at d_records that rank `me` of n owns go into its table
+int kidx_rank_insert(const ::pg_kindex* ix, uint32_t me, const uint64_t* d_records, uint64_t m, hipStream_t st) {
+    const KidxRank& r = ix->ranks[me];
+    dim3 grid;
+    if (int rc = kidx_record_blocks(m, &grid)) return rc;
+    return kidx_launch(ix, [&](auto nw) {
+        hipLaunchKernelGGL((kidx_build_kernel<decltype(nw)::value>), grid, dim3(256), 0, st, d_records, m, (uint32_t)ix->ranks.size(), me, r.d_tab, r.slots - 1,
+                           r.d_flags);
+    });
+}
+
+// what the ranks' flags, read back once their streams were waited for, say of the build
+int kidx_build_verdict(uint32_t flags) {
     if (flags & KIDX_FLAG_DUP) { pg_set_error("k-mer index: duplicate key in records"); return PG_EINVAL; }
     if (flags & KIDX_FLAG_SPIN) {
         pg_set_error("k-mer index: the build gave up on a claimed slot after " + std::to_string(KIDX_SPIN_CAP) +
@@ -428,41 +406,53 @@ int kidx_device_build(::pg_kindex* ix, const uint64_t* d_records, uint64_t n_rec
     return PG_OK;
 }
 
-int kidx_device_query(::pg_kindex* ix, const uint64_t* d_packed, const uint64_t* d_word_off, const uint64_t* d_kmer_base, uint64_t n_seqs,
-                      uint32_t uniform_len, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream) {
+}  // namespace
+
+// one table: the caller's stream, no owners to count, no stream or event of the index's own
+int kidx_device_build(::pg_kindex* ix, const uint64_t* d_records, uint64_t n_records, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = kidx_set_device(ix->device)) return rc;
-    if (!n_seqs) return PG_OK;
-    const uint64_t blocks = wave ? (n_seqs + KIDX_WAVES - 1) / KIDX_WAVES : (n_seqs + 255) / 256;
-    if (blocks > 0x7FFFFFFFULL) { pg_set_error("k-mer index: batch too large for one launch"); return PG_EINVAL; }
-    const dim3 grid((unsigned)blocks), block(256);
-    kidx_with_nw(ix->nw, [&](auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        if (wave) hipLaunchKernelGGL((kidx_query_wave_kernel<NW>), grid, block, 0, st, d_packed, d_word_off, d_kmer_base, n_seqs, uniform_len, ix->K,
-                                     ix->d_tab, ix->slots - 1, d_out, d_summary);
-        else hipLaunchKernelGGL((kidx_query_kernel<NW>), grid, block, 0, st, d_packed, d_word_off, d_kmer_base, n_seqs, uniform_len, ix->K, ix->d_tab,
-                                ix->slots - 1, d_out, d_summary);
-    });
-    KIDX_HIP(hipGetLastError());
-    return PG_OK;
+    KidxRank& r = ix->ranks[0];
+    dim3 grid;
+    if (int rc = kidx_set_device(r.device)) return rc;
+    if (int rc = kidx_record_blocks(n_records, &grid)) return rc;
+    arena_pin_for_process(r.device);
+    r.keys = n_records;
+    if (int rc = kidx_rank_table(r, ix->nw, st)) return rc;
+    if (n_records) if (int rc = kidx_rank_insert(ix, 0, d_records, n_records, st)) return rc;
+    uint32_t flags = 0;
+    KIDX_HIP(hipMemcpyAsync(&flags, r.d_flags, sizeof flags, hipMemcpyDeviceToHost, st));
+    KIDX_HIP(hipStreamSynchronize(st));
+    return kidx_build_verdict(flags);
 }
 
-int kcor_device_correct(::pg_kindex* ix, const uint64_t* d_packed, const uint64_t* d_word_off, const uint64_t* d_kmer_base, uint64_t n_seqs,
-                        uint32_t uniform_len, uint64_t n_words, const KcorParams& pr, uint64_t* d_packed_out, uint64_t* d_report, void* stream) {
+int kidx_device_query(::pg_kindex* ix, const KidxBatch& b, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    const KidxRank& t = ix->ranks[0];
+    dim3 grid;
     if (int rc = kidx_set_device(ix->device)) return rc;
-    if (!n_seqs) return PG_OK;
-    const uint64_t blocks = (n_seqs + 255) / 256;
-    if (blocks > 0x7FFFFFFFULL) { pg_set_error("k-mer index: batch too large for one launch"); return PG_EINVAL; }
-    // the copy first -- pad bits and the readable tail with it -- then every lane works on its own words of the output
-    if (d_packed_out != d_packed) KIDX_HIP(hipMemcpyAsync(d_packed_out, d_packed, n_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    const dim3 grid((unsigned)blocks), block(256);
-    kidx_with_nw(ix->nw, [&](auto nw) {
-        hipLaunchKernelGGL((kcor_kernel<decltype(nw)::value>), grid, block, 0, st, d_packed_out, d_word_off, d_kmer_base, n_seqs, uniform_len, ix->K,
-                           ix->d_tab, ix->slots - 1, pr, d_report);
+    if (!b.n_seqs) return PG_OK;
+    if (int rc = kidx_batch_blocks(b.n_seqs, wave, &grid)) return rc;
+    return kidx_launch(ix, [&](auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        if (wave) hipLaunchKernelGGL((kidx_query_kernel<NW, true>), grid, dim3(256), 0, st, b, ix->K, t.d_tab, t.slots - 1, d_out, d_summary);
+        else hipLaunchKernelGGL((kidx_query_kernel<NW, false>), grid, dim3(256), 0, st, b, ix->K, t.d_tab, t.slots - 1, d_out, d_summary);
     });
-    KIDX_HIP(hipGetLastError());
-    return PG_OK;
+}
+
+int kcor_device_correct(::pg_kindex* ix, const KidxBatch& b, const KcorParams& pr, uint64_t* d_packed_out, uint64_t* d_report, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const KidxRank& t = ix->ranks[0];
+    dim3 grid;
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    if (!b.n_seqs) return PG_OK;
+    if (int rc = kidx_batch_blocks(b.n_seqs, false, &grid)) return rc;
+    // the copy first -- pad bits and the readable tail with it -- then every lane works on its own words of the output
+    if (d_packed_out != b.packed) KIDX_HIP(hipMemcpyAsync(d_packed_out, b.packed, b.n_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    KidxBatch o = b;
+    o.packed = d_packed_out;
+    return kidx_launch(ix, [&](auto nw) {
+        hipLaunchKernelGGL((kcor_kernel<decltype(nw)::value>), grid, dim3(256), 0, st, o, ix->K, t.d_tab, t.slots - 1, pr, d_report);
+    });
 }
 
 // ---- the index cut over ranks ----
@@ -499,12 +489,6 @@ int kidx_reserve(uint64_t** p, uint64_t* cap, uint64_t want) {
     return PG_OK;
 }
 
-int kidx_launch_blocks(uint64_t n_records, unsigned* blocks) {
-    if ((n_records + 255) / 256 > 0x7FFFFFFFULL) { pg_set_error("k-mer index: too many records for one launch"); return PG_EINVAL; }
-    *blocks = (unsigned)((n_records + 255) / 256);
-    return PG_OK;
-}
-
 // the fewest ranks pg_host_kindex_plan says hold n_records on a device with device_bytes free, a rank's table at most table_cap; 0: none
 int kidx_fewest_ranks(uint64_t n_records, int nw, uint64_t device_bytes, uint64_t table_cap) {
     uint64_t plan[12];
@@ -518,12 +502,11 @@ int kidx_build_ranks(::pg_kindex* ix, const uint64_t* const* parts, const uint64
                      hipStream_t st, std::vector<KidxPartCount>& pc, std::vector<unsigned long long>& bins, std::vector<uint32_t>& flags) {
     const uint32_t n = (uint32_t)ix->ranks.size();
     const int rw = ix->nw + 2;
-    const dim3 block(256);
-    unsigned blocks = 0;
+    dim3 grid;
     KidxRank& lead = ix->ranks[0];
     for (int p = 0; p < n_parts; p++) {
         if (part_device[p] >= 0) if (int rc = kidx_set_device(part_device[p])) return rc;
-        if (int rc = kidx_launch_blocks(part_records[p], &blocks)) return rc;
+        if (int rc = kidx_record_blocks(part_records[p], &grid)) return rc;
     }
     // 1. every rank's stream and events; the caller's stream has made the parts, so every stream that reads one goes behind e_begin
     for (KidxRank& r : ix->ranks) {
@@ -543,11 +526,7 @@ int kidx_build_ranks(::pg_kindex* ix, const uint64_t* const* parts, const uint64
         if (part_device[p] < 0) {
             kidx_with_nw(ix->nw, [&](auto nw) {
                 constexpr int NW = decltype(nw)::value;
-                for (uint64_t i = 0; i < part_records[p]; i++) {
-                    Kmer<NW> k;
-                    for (int q = 0; q < NW; q++) k.w[q] = parts[p][i * (NW + 2) + q];
-                    out[map_owner<NW>(k, n)]++;
-                }
+                for (uint64_t i = 0; i < part_records[p]; i++) out[map_owner<NW>(kidx_record_key<NW>(parts[p] + i * (NW + 2)), n)]++;
             });
             continue;
         }
@@ -566,11 +545,11 @@ int kidx_build_ranks(::pg_kindex* ix, const uint64_t* const* parts, const uint64
         }
         KIDX_HIP(hipStreamWaitEvent(c.st, ix->e_begin, 0));
         KIDX_HIP(hipMemsetAsync(c.d_bins, 0, n * sizeof(unsigned long long), c.st));
-        (void)kidx_launch_blocks(part_records[p], &blocks);
-        kidx_with_nw(ix->nw, [&](auto nw) {
-            hipLaunchKernelGGL((kidx_count_owners_kernel<decltype(nw)::value>), dim3(blocks), block, 0, c.st, parts[p], part_records[p], n, c.d_bins);
-        });
-        KIDX_HIP(hipGetLastError());
+        (void)kidx_record_blocks(part_records[p], &grid);
+        if (int rc = kidx_launch(ix, [&](auto nw) {
+                hipLaunchKernelGGL((kidx_count_owners_kernel<decltype(nw)::value>), grid, dim3(256), 0, c.st, parts[p], part_records[p], n, c.d_bins);
+            }))
+            return rc;
         KIDX_HIP(hipMemcpyAsync(out, c.d_bins, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.st));
     }
     // the host's first wait: the counts
@@ -585,16 +564,12 @@ int kidx_build_ranks(::pg_kindex* ix, const uint64_t* const* parts, const uint64
         KidxRank& r = ix->ranks[i];
         r.keys = 0;
         for (int p = 0; p < n_parts; p++) r.keys += bins[(size_t)p * n + i];
-        r.slots = map_table_slots(r.keys);
         total += r.keys;
     }
     if (total != n_records) {
         pg_set_error("k-mer index: the ranks own " + std::to_string(total) + " records of " + std::to_string(n_records));
         return PG_EINVAL;
     }
-    ix->keys = total;
-    ix->slots = 0;
-    for (const KidxRank& r : ix->ranks) ix->slots += r.slots;
     // 3. does every rank's table, exactly sized, and its chunk buffer fit its device?  Asked before either is allocated
     const uint64_t chunk = kidx_chunk_records();
     const char* hook = env_test("SOAPDENOVO2_AMD_KINDEX_BUDGET_MB");
@@ -623,16 +598,12 @@ int kidx_build_ranks(::pg_kindex* ix, const uint64_t* const* parts, const uint64
     for (uint32_t i = 0; i < n; i++) {
         KidxRank& r = ix->ranks[i];
         KIDX_HIP(hipSetDevice(r.device));
-        const size_t bytes = kidx_table_bytes(r.keys, ix->nw);
-        if (arena_malloc(&r.d_tab, bytes) != hipSuccess || arena_malloc(&r.d_flags, sizeof(uint32_t)) != hipSuccess ||
-            (chunk_words[i] && arena_malloc(&r.d_chunk, chunk_words[i] * sizeof(uint64_t)) != hipSuccess)) {
+        if (int rc = kidx_rank_table(r, ix->nw, r.st)) return rc;
+        if (chunk_words[i] && arena_malloc(&r.d_chunk, chunk_words[i] * sizeof(uint64_t)) != hipSuccess) {
             (void)hipGetLastError();
-            pg_set_error("k-mer index: out of device memory (rank " + std::to_string(i) + ": a table of " + std::to_string(r.slots) + " slots, " +
-                         std::to_string(bytes >> 20) + " MiB)");
+            pg_set_error("k-mer index: out of device memory for rank " + std::to_string(i) + "'s chunk buffer");
             return PG_ENOMEM;
         }
-        KIDX_HIP(hipMemsetAsync(r.d_tab, 0, bytes, r.st));
-        KIDX_HIP(hipMemsetAsync(r.d_flags, 0, sizeof(uint32_t), r.st));
         KIDX_HIP(hipStreamWaitEvent(r.st, ix->e_begin, 0));
         for (int p = 0; p < n_parts && r.keys; p++) {                             // (a rank that owns nothing launches no insert)
             const bool in_place = part_device[p] == r.device;
@@ -646,12 +617,7 @@ int kidx_build_ranks(::pg_kindex* ix, const uint64_t* const* parts, const uint64
                     else KIDX_HIP(hipMemcpyPeerAsync(r.d_chunk, r.device, src, part_device[p], b, r.st));
                     src = r.d_chunk;
                 }
-                (void)kidx_launch_blocks(m, &blocks);
-                kidx_with_nw(ix->nw, [&](auto nw) {
-                    hipLaunchKernelGGL((kidx_build_owned_kernel<decltype(nw)::value>), dim3(blocks), block, 0, r.st, src, m, n, i, r.d_tab, r.slots - 1,
-                                       r.d_flags);
-                });
-                KIDX_HIP(hipGetLastError());
+                if (int rc = kidx_rank_insert(ix, i, src, m, r.st)) return rc;
             }
         }
         KIDX_HIP(hipMemcpyAsync(&flags[i], r.d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, r.st));
@@ -663,29 +629,23 @@ int kidx_build_ranks(::pg_kindex* ix, const uint64_t* const* parts, const uint64
         KIDX_HIP(hipStreamSynchronize(ix->ranks[i].st));
         any |= flags[i];
     }
-    if (any & KIDX_FLAG_DUP) { pg_set_error("k-mer index: duplicate key in records"); return PG_EINVAL; }
-    if (any & KIDX_FLAG_SPIN) {
-        pg_set_error("k-mer index: the build gave up on a claimed slot after " + std::to_string(KIDX_SPIN_CAP) +
-                     " trips (the slot's key was never published); the index is not complete");
-        return PG_ESPIN;
-    }
-    return PG_OK;
+    return kidx_build_verdict(any);
 }
 
-int kidx_query_ranks(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words, const uint64_t* d_word_off, const uint64_t* d_kmer_base,
-                     uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* d_out, uint64_t* d_summary, hipStream_t st) {
+int kidx_query_ranks(::pg_kindex* ix, const KidxBatch& b, int wave, uint64_t* d_out, uint64_t* d_summary, hipStream_t st) {
     const uint32_t n = (uint32_t)ix->ranks.size();
+    const uint64_t n_words = b.n_words, n_seqs = b.n_seqs, n_kmers = b.n_kmers;
     KidxRank& lead = ix->ranks[0];
-    const uint64_t blocks = wave ? (n_seqs + KIDX_WAVES - 1) / KIDX_WAVES : (n_seqs + 255) / 256;
-    if (blocks > 0x7FFFFFFFULL) { pg_set_error("k-mer index: batch too large for one launch"); return PG_EINVAL; }
-    const dim3 grid((unsigned)blocks), grid_waves((unsigned)((n_seqs + KIDX_WAVES - 1) / KIDX_WAVES)), block(256);
+    dim3 grid, grid_waves;
+    if (int rc = kidx_batch_blocks(n_seqs, wave, &grid)) return rc;
+    if (d_summary) if (int rc = kidx_batch_blocks(n_seqs, true, &grid_waves)) return rc;
     // The buffers grow to the largest batch met.  One that has to grow is given back first, and the previous query may still use it: only
     // then does the host wait, for that query's end
     bool grow = n > 1 && n_kmers > ix->cap_staging;
     for (uint32_t i = 0; i < n; i++) {
         const KidxRank& r = ix->ranks[i];
         grow = grow || ((i || !d_out) && n_kmers > r.cap_rows);
-        grow = grow || (r.device != lead.device && (n_words > r.cap_packed || (!uniform_len && n_seqs + 1 > r.cap_seqs)));
+        grow = grow || (r.device != lead.device && (n_words > r.cap_packed || (!b.uniform_len && n_seqs + 1 > r.cap_seqs)));
     }
     if (grow && ix->queried) KIDX_HIP(hipEventSynchronize(ix->e_end));
     KIDX_HIP(hipSetDevice(lead.device));
@@ -695,7 +655,7 @@ int kidx_query_ranks(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words
     for (uint32_t i = 0; i < n; i++) {
         KidxRank& r = ix->ranks[i];
         KIDX_HIP(hipSetDevice(r.device));
-        const uint64_t *packed = d_packed, *word_off = d_word_off, *kmer_base = d_kmer_base;
+        KidxBatch mine = b;                        // the rank's view of the batch: in place on the lead's device, else its copy
         uint64_t* rows = i == 0 && d_out ? d_out : nullptr;
         if (!rows) {
             if (int rc = kidx_reserve(&r.d_rows, &r.cap_rows, std::max<uint64_t>(n_kmers, 1))) return rc;
@@ -705,28 +665,26 @@ int kidx_query_ranks(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words
         if (ix->queried) KIDX_HIP(hipStreamWaitEvent(r.st, ix->e_end, 0));
         if (r.device != lead.device) {
             if (int rc = kidx_reserve(&r.d_packed, &r.cap_packed, n_words)) return rc;
-            KIDX_HIP(hipMemcpyPeerAsync(r.d_packed, r.device, d_packed, lead.device, n_words * sizeof(uint64_t), r.st));
-            packed = r.d_packed;
-            if (!uniform_len) {
+            KIDX_HIP(hipMemcpyPeerAsync(r.d_packed, r.device, b.packed, lead.device, n_words * sizeof(uint64_t), r.st));
+            mine.packed = r.d_packed;
+            if (!b.uniform_len) {
                 uint64_t cap = r.cap_seqs;
                 if (int rc = kidx_reserve(&r.d_word_off, &cap, n_seqs + 1)) return rc;
                 if (int rc = kidx_reserve(&r.d_kmer_base, &r.cap_seqs, n_seqs + 1)) return rc;
-                KIDX_HIP(hipMemcpyPeerAsync(r.d_word_off, r.device, d_word_off, lead.device, n_seqs * sizeof(uint64_t), r.st));
-                KIDX_HIP(hipMemcpyPeerAsync(r.d_kmer_base, r.device, d_kmer_base, lead.device, (n_seqs + 1) * sizeof(uint64_t), r.st));
-                word_off = r.d_word_off;
-                kmer_base = r.d_kmer_base;
+                KIDX_HIP(hipMemcpyPeerAsync(r.d_word_off, r.device, b.word_off, lead.device, n_seqs * sizeof(uint64_t), r.st));
+                KIDX_HIP(hipMemcpyPeerAsync(r.d_kmer_base, r.device, b.kmer_base, lead.device, (n_seqs + 1) * sizeof(uint64_t), r.st));
+                mine.word_off = r.d_word_off;
+                mine.kmer_base = r.d_kmer_base;
             }
         }
         if (n_kmers) KIDX_HIP(hipMemsetAsync(rows, 0, n_kmers * sizeof(uint64_t), r.st));
         KIDX_HIP(hipEventRecord(r.e0, r.st));
-        kidx_with_nw(ix->nw, [&](auto nw) {
-            constexpr int NW = decltype(nw)::value;
-            if (wave) hipLaunchKernelGGL((kidx_probe_owned_kernel<NW, true>), grid, block, 0, r.st, packed, word_off, kmer_base, n_seqs, uniform_len, ix->K,
-                                         n, i, r.d_tab, r.slots - 1, rows);
-            else hipLaunchKernelGGL((kidx_probe_owned_kernel<NW, false>), grid, block, 0, r.st, packed, word_off, kmer_base, n_seqs, uniform_len, ix->K,
-                                    n, i, r.d_tab, r.slots - 1, rows);
-        });
-        KIDX_HIP(hipGetLastError());
+        if (int rc = kidx_launch(ix, [&](auto nw) {
+                constexpr int NW = decltype(nw)::value;
+                if (wave) hipLaunchKernelGGL((kidx_probe_owned_kernel<NW, true>), grid, dim3(256), 0, r.st, mine, ix->K, n, i, r.d_tab, r.slots - 1, rows);
+                else hipLaunchKernelGGL((kidx_probe_owned_kernel<NW, false>), grid, dim3(256), 0, r.st, mine, ix->K, n, i, r.d_tab, r.slots - 1, rows);
+            }))
+            return rc;
         KIDX_HIP(hipEventRecord(r.e1, r.st));
     }
     // the caller's stream: behind every rank's probe, the other ranks' rows one after the other through the staging buffer, the summary
@@ -743,7 +701,7 @@ int kidx_query_ranks(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words
     }
     KIDX_HIP(hipEventRecord(ix->e_merged, st));
     if (d_summary) {
-        hipLaunchKernelGGL(kidx_summary_rows_kernel, grid_waves, block, 0, st, d_kmer_base, n_seqs, uniform_len, ix->K, rows, d_summary);
+        hipLaunchKernelGGL(kidx_summary_rows_kernel, grid_waves, dim3(256), 0, st, b, ix->K, rows, d_summary);
         KIDX_HIP(hipGetLastError());
     }
     KIDX_HIP(hipEventRecord(ix->e_end, st));
@@ -779,11 +737,10 @@ int kidx_device_build_sharded(::pg_kindex* ix, const uint64_t* const* parts, con
     return rc;
 }
 
-int kidx_device_query_sharded(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words, const uint64_t* d_word_off, const uint64_t* d_kmer_base,
-                              uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream) {
+int kidx_device_query_sharded(::pg_kindex* ix, const KidxBatch& b, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream) {
     if (int rc = kidx_set_device(ix->device)) return rc;
-    if (!n_seqs) return PG_OK;
-    const int rc = kidx_query_ranks(ix, d_packed, n_words, d_word_off, d_kmer_base, n_seqs, uniform_len, n_kmers, wave, d_out, d_summary, (hipStream_t)stream);
+    if (!b.n_seqs) return PG_OK;
+    const int rc = kidx_query_ranks(ix, b, wave, d_out, d_summary, (hipStream_t)stream);
     if (rc) {                                      // no stream is left reading the caller's batch or writing its results
         kidx_sync_ranks(ix);
         (void)hipSetDevice(ix->device);
@@ -808,18 +765,19 @@ void ktrim_free(::pg_kindex* ix) {
 
 }  // namespace
 
-int ktrim_device_trim(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words, const uint64_t* d_word_off, const uint64_t* d_kmer_base,
-                      uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, uint32_t min_cov, uint32_t min_len, uint64_t* d_span,
-                      uint64_t* d_packed_out, uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_src_out, uint64_t* d_totals,
-                      void* stream) {
+int ktrim_device_trim(::pg_kindex* ix, const KidxBatch& b, uint32_t min_cov, uint32_t min_len, uint64_t* d_span, uint64_t* d_packed_out,
+                      uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_src_out, uint64_t* d_totals, void* stream) {
     hipStream_t st = (hipStream_t)stream;
+    const uint64_t n_seqs = b.n_seqs;
     if (int rc = kidx_set_device(ix->device)) return rc;
     if (!n_seqs) {
         if (d_packed_out) KIDX_HIP(hipMemsetAsync(d_totals, 0, KTRIM_COUNTS * sizeof(uint64_t), st));
         return PG_OK;
     }
-    const uint64_t n_blocks = (n_seqs + 255) / 256, pack_blocks = (n_words + 255) / 256;
-    if (n_blocks > 0x7FFFFFFFULL || pack_blocks > 0x7FFFFFFFULL) { pg_set_error("k-mer index: batch too large for one launch"); return PG_EINVAL; }
+    dim3 grid, pack_grid;
+    if (int rc = kidx_batch_blocks(n_seqs, false, &grid)) return rc;
+    if (int rc = kidx_launch_blocks(b.n_words, 256, "batch too large", &pack_grid)) return rc;
+    const uint64_t n_blocks = grid.x;
     // Scratch: the spans and the source indices where the caller takes none, and the workgroups' sums.  It grows to the largest batch
     // met: the buffer is given back first, and arena_free waits for the device as hipFree does, so no earlier trim still uses it --
     // the only place the host waits
@@ -832,33 +790,32 @@ int ktrim_device_trim(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_word
     for (hipEvent_t& e : ix->e_trim) if (!e) KIDX_HIP(hipEventCreate(&e));
     if (ix->trimmed) KIDX_HIP(hipStreamWaitEvent(st, ix->e_trim[3], 0));         // (another stream than last time's: the scratch is one)
     KIDX_HIP(hipEventRecord(ix->e_trim[0], st));
-    const dim3 grid((unsigned)n_blocks), block(256);
-    if (ix->ranks.empty()) {
-        kidx_with_nw(ix->nw, [&](auto nw) {
-            hipLaunchKernelGGL((ktrim_span_kernel<decltype(nw)::value>), grid, block, 0, st, d_packed, d_word_off, d_kmer_base, n_seqs, uniform_len, ix->K,
-                               ix->d_tab, ix->slots - 1, min_cov, d_span);
-        });
-        KIDX_HIP(hipGetLastError());
+    const dim3 block(256);
+    const KidxRank& lead = ix->ranks[0];
+    if (!ix->cut) {
+        if (int rc = kidx_launch(ix, [&](auto nw) {
+                hipLaunchKernelGGL((ktrim_span_kernel<decltype(nw)::value>), grid, block, 0, st, b, ix->K, lead.d_tab, lead.slots - 1, min_cov, d_span);
+            }))
+            return rc;
     } else {
         // every rank probes the k-mers it owns and the lead's row buffer receives the merged answers (no counts or summary for the caller)
-        if (int rc = kidx_device_query_sharded(ix, d_packed, n_words, d_word_off, d_kmer_base, n_seqs, uniform_len, n_kmers, 0, nullptr, nullptr, stream))
-            return rc;
-        hipLaunchKernelGGL(ktrim_span_rows_kernel, grid, block, 0, st, d_kmer_base, n_seqs, uniform_len, ix->K, ix->ranks[0].d_rows, min_cov, d_span);
+        if (int rc = kidx_device_query_sharded(ix, b, 0, nullptr, nullptr, stream)) return rc;
+        hipLaunchKernelGGL(ktrim_span_rows_kernel, grid, block, 0, st, b, ix->K, lead.d_rows, min_cov, d_span);
         KIDX_HIP(hipGetLastError());
         KIDX_HIP(hipEventRecord(ix->e_end, st));   // the next query's ranks zero the rows: they wait for this read of them too
     }
     KIDX_HIP(hipEventRecord(ix->e_trim[1], st));
     if (d_packed_out) {
-        hipLaunchKernelGGL(ktrim_block_sums_kernel, grid, block, 0, st, d_span, d_kmer_base, n_seqs, uniform_len, ix->K, min_len, d_sums);
+        hipLaunchKernelGGL(ktrim_block_sums_kernel, grid, block, 0, st, d_span, b, ix->K, min_len, d_sums);
         hipLaunchKernelGGL(ktrim_scan_sums_kernel, dim3(1), block, 0, st, d_sums, n_blocks, d_kmer_base_out, d_totals);
-        hipLaunchKernelGGL(ktrim_scatter_kernel, grid, block, 0, st, d_span, d_kmer_base, n_seqs, uniform_len, ix->K, min_len, d_sums, d_word_off_out,
+        hipLaunchKernelGGL(ktrim_scatter_kernel, grid, block, 0, st, d_span, b, ix->K, min_len, d_sums, d_word_off_out,
                            d_kmer_base_out, d_src_out);
         KIDX_HIP(hipGetLastError());
     }
     KIDX_HIP(hipEventRecord(ix->e_trim[2], st));
     if (d_packed_out) {
-        hipLaunchKernelGGL(ktrim_pack_kernel, dim3((unsigned)pack_blocks), block, 0, st, d_packed, d_word_off, uniform_len, d_span, d_word_off_out, d_src_out,
-                           d_totals, ix->nw + 1, n_words, d_packed_out);
+        hipLaunchKernelGGL(ktrim_pack_kernel, pack_grid, block, 0, st, b.packed, b.word_off, b.uniform_len, d_span, d_word_off_out, d_src_out,
+                           d_totals, ix->nw + 1, b.n_words, d_packed_out);
         KIDX_HIP(hipGetLastError());
     }
     KIDX_HIP(hipEventRecord(ix->e_trim[3], st));
@@ -905,63 +862,69 @@ void kidx_device_free(::pg_kindex* ix) {
         (void)hipSetDevice(ix->device);
         ktrim_free(ix);
     }
-    if (!ix->ranks.empty()) {                      // every stream first: the lead's copies read the other ranks' rows
-        kidx_sync_ranks(ix);
-        for (KidxRank& r : ix->ranks) {
-            if (!r.st) continue;                   // (a build that failed before this rank began: nothing of it is on a device)
-            (void)hipSetDevice(r.device);
-            for (void* p : {(void*)r.d_tab, (void*)r.d_flags, (void*)r.d_chunk, (void*)r.d_packed, (void*)r.d_word_off, (void*)r.d_kmer_base, (void*)r.d_rows})
-                if (p) (void)arena_free(p);        // (waits for the device like hipFree: no query still reads the table)
-            if (r.st) (void)hipStreamDestroy(r.st);
-            for (hipEvent_t e : {r.e0, r.e1}) if (e) (void)hipEventDestroy(e);
-            r = KidxRank();
-        }
-        (void)hipSetDevice(ix->device);
-        if (ix->d_staging) (void)arena_free(ix->d_staging);
-        for (hipEvent_t e : {ix->e_begin, ix->e_probed, ix->e_merged, ix->e_end}) if (e) (void)hipEventDestroy(e);
-        ix->d_staging = nullptr;
-        ix->e_begin = ix->e_probed = ix->e_merged = ix->e_end = nullptr;
-        ix->ranks.clear();
-        return;
+    kidx_sync_ranks(ix);                           // every stream first: the lead's copies read the other ranks' rows
+    for (KidxRank& r : ix->ranks) {
+        if (!r.st && !r.d_tab && !r.d_flags) continue;   // (a build that failed before this rank began: nothing of it is on a device)
+        (void)hipSetDevice(r.device);
+        for (void* p : {(void*)r.d_tab, (void*)r.d_flags, (void*)r.d_chunk, (void*)r.d_packed, (void*)r.d_word_off, (void*)r.d_kmer_base, (void*)r.d_rows})
+            if (p) (void)arena_free(p);            // (waits for the device like hipFree: no query still reads the table)
+        if (r.st) (void)hipStreamDestroy(r.st);    // (a rank of an index in one table has no stream or events)
+        for (hipEvent_t e : {r.e0, r.e1}) if (e) (void)hipEventDestroy(e);
+        r = KidxRank();
     }
-    if (!ix->d_tab && !ix->d_flags) return;
+    if (!ix->d_staging && !ix->e_begin) return;
     (void)hipSetDevice(ix->device);
-    if (ix->d_tab) (void)arena_free(ix->d_tab);    // (waits for the device like hipFree: no query still reads the table)
-    if (ix->d_flags) (void)arena_free(ix->d_flags);
-    ix->d_tab = nullptr;
-    ix->d_flags = nullptr;
+    if (ix->d_staging) (void)arena_free(ix->d_staging);
+    for (hipEvent_t e : {ix->e_begin, ix->e_probed, ix->e_merged, ix->e_end}) if (e) (void)hipEventDestroy(e);
+    ix->d_staging = nullptr;
+    ix->e_begin = ix->e_probed = ix->e_merged = ix->e_end = nullptr;
 }
 
 }  // namespace pg
 
-// pg_kindex_build for a context's own records (the host half of the ABI is kindex_host.cpp's)
-extern "C" pg_kindex* pg_kindex_from_ctx(pg_ctx* c, void* stream) {
-    if (!c) { pg_set_error("pg_kindex_from_ctx: null context (PG_EINVAL)"); return nullptr; }
-    if (!c->finalized) { pg_set_error("pg_kindex_from_ctx: call pg_finalize first (PG_ESTATE)"); return nullptr; }
-    if (c->engine == 2) {                          // the export array where it lies
+namespace {
+
+// build(d_records, n) for a finalized context's own records: the export array where it lies, or -- the global-set engine keeps none --
+// one that is made for the build and given back
+template <typename F>
+pg_kindex* kidx_from_ctx(const std::string& who, pg_ctx* c, void* stream, F build) {
+    if (c->engine == 2) {
         const uint64_t* d_records = nullptr;
         uint64_t n = 0;
         if (pg_export_peek(c, &d_records, &n) != PG_OK) return nullptr;
-        return pg_kindex_build(c->device, c->K, c->NW == 4, d_records, n, stream);
+        return build(d_records, n);
     }
-    // the global-set engine keeps no export array: one is made for the build and given back
     uint64_t n = 0, got = 0;
     if (pg_distinct(c, &n, stream) != PG_OK) return nullptr;
     uint64_t* d_records = nullptr;
     if (pg::arena_malloc(&d_records, (n ? n : 1) * (uint64_t)(c->NW + 2) * sizeof(uint64_t)) != hipSuccess) {
         (void)hipGetLastError();
-        pg_set_error("pg_kindex_from_ctx: out of device memory for the records (PG_ENOMEM)");
+        pg_set_error(who + ": out of device memory for the records (PG_ENOMEM)");
         return nullptr;
     }
-    pg_kindex* ix = pg_export(c, d_records, n, &got, stream) == PG_OK ? pg_kindex_build(c->device, c->K, c->NW == 4, d_records, got, stream) : nullptr;
+    pg_kindex* ix = pg_export(c, d_records, n, &got, stream) == PG_OK ? build(d_records, got) : nullptr;
     (void)pg::arena_free(d_records);
     return ix;
 }
 
+bool kidx_ctx_ready(const std::string& who, const pg_ctx* c) {
+    if (!c) { pg_set_error(who + ": null context (PG_EINVAL)"); return false; }
+    if (!c->finalized) { pg_set_error(who + ": call pg_finalize first (PG_ESTATE)"); return false; }
+    return true;
+}
+
+}  // namespace
+
+// pg_kindex_build for a context's own records (the host half of the ABI is kindex_host.cpp's)
+extern "C" pg_kindex* pg_kindex_from_ctx(pg_ctx* c, void* stream) {
+    if (!kidx_ctx_ready("pg_kindex_from_ctx", c)) return nullptr;
+    return kidx_from_ctx("pg_kindex_from_ctx", c, stream,
+                         [&](const uint64_t* d_records, uint64_t n) { return pg_kindex_build(c->device, c->K, c->NW == 4, d_records, n, stream); });
+}
+
 // pg_kindex_build_sharded for a context's own records: its export array as one device part
 extern "C" pg_kindex* pg_kindex_from_ctx_sharded(pg_ctx* c, const int* devices, int n_devices, void* stream) {
-    if (!c) { pg_set_error("pg_kindex_from_ctx_sharded: null context (PG_EINVAL)"); return nullptr; }
-    if (!c->finalized) { pg_set_error("pg_kindex_from_ctx_sharded: call pg_finalize first (PG_ESTATE)"); return nullptr; }
+    if (!kidx_ctx_ready("pg_kindex_from_ctx_sharded", c)) return nullptr;
     const int part_device = c->device;
     if (devices && n_devices > 0 && devices[0] != c->device && devices[0] >= 0) {
         // `stream` is the context's, on its device, and the build takes one of the lead's: the records are finished here instead
@@ -971,24 +934,7 @@ extern "C" pg_kindex* pg_kindex_from_ctx_sharded(pg_ctx* c, const int* devices, 
         }
         stream = nullptr;
     }
-    if (c->engine == 2) {                          // the export array where it lies
-        const uint64_t* d_records = nullptr;
-        uint64_t n = 0;
-        if (pg_export_peek(c, &d_records, &n) != PG_OK) return nullptr;
+    return kidx_from_ctx("pg_kindex_from_ctx_sharded", c, stream, [&](const uint64_t* d_records, uint64_t n) {
         return pg_kindex_build_sharded(devices, n_devices, c->K, c->NW == 4, &d_records, &n, &part_device, 1, stream);
-    }
-    // the global-set engine keeps no export array: one is made for the build and given back
-    uint64_t n = 0, got = 0;
-    if (pg_distinct(c, &n, stream) != PG_OK) return nullptr;
-    uint64_t* d_records = nullptr;
-    if (pg::arena_malloc(&d_records, (n ? n : 1) * (uint64_t)(c->NW + 2) * sizeof(uint64_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        pg_set_error("pg_kindex_from_ctx_sharded: out of device memory for the records (PG_ENOMEM)");
-        return nullptr;
-    }
-    const uint64_t* part = d_records;
-    pg_kindex* ix = pg_export(c, d_records, n, &got, stream) == PG_OK
-                        ? pg_kindex_build_sharded(devices, n_devices, c->K, c->NW == 4, &part, &got, &part_device, 1, stream) : nullptr;
-    (void)pg::arena_free(d_records);
-    return ix;
+    });
 }

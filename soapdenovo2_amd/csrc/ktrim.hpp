@@ -71,11 +71,6 @@ PG_HD KtrimCounts ktrim_counts(uint64_t span, int nk, int K, uint32_t min_len) {
     return KtrimCounts{{kept ? 1u : 0u, kept ? (uint64_t)((len + 31) / 32) : 0, kept ? (uint64_t)(len - (uint32_t)K + 1) : 0, given - (kept ? len : 0)}};
 }
 
-// nk of sequence r alone (kidx_seq's, without the words)
-PG_HD int ktrim_nk(const uint64_t* kmer_base, uint32_t uniform_len, int K, uint64_t r) {
-    return uniform_len ? ((int)uniform_len >= K ? (int)uniform_len - K + 1 : 0) : (int)(kmer_base[r + 1] - kmer_base[r]);
-}
-
 // Output word q of a kept read: bases start + 32 q .. of the source read rd, a 128-bit funnel of two source words.  The second word is
 // loaded whether the shift needs it or not: it is the read's next word, the next read's first, or -- behind the batch's last read --
 // one of the nw + 1 readable tail words.  The last word's pad bits are cleared
@@ -89,10 +84,8 @@ PG_HD uint64_t ktrim_pack_word(const uint64_t* rd, uint32_t start, uint32_t len,
 }
 
 // the device engine (kindex_kernels.hip): one table or cut over ranks alike.  d_packed_out null: spans only
-int ktrim_device_trim(::pg_kindex* ix, const uint64_t* d_packed, uint64_t n_words, const uint64_t* d_word_off, const uint64_t* d_kmer_base,
-                      uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, uint32_t min_cov, uint32_t min_len, uint64_t* d_span,
-                      uint64_t* d_packed_out, uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_src_out, uint64_t* d_totals,
-                      void* stream);
+int ktrim_device_trim(::pg_kindex* ix, const KidxBatch& b, uint32_t min_cov, uint32_t min_len, uint64_t* d_span, uint64_t* d_packed_out,
+                      uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_src_out, uint64_t* d_totals, void* stream);
 // the last trim's milliseconds from its events, after waiting for its end: span (a cut index: probes and merge included), scan, pack, all of it
 int ktrim_device_times(::pg_kindex* ix, double out[4]);
 

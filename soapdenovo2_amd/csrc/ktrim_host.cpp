@@ -13,27 +13,18 @@ void pg_set_error(const std::string& s);
 namespace pg {
 namespace {
 
-// the host twin of pg_kindex_trim: every read's span (an index cut over ranks: every k-mer asks its owner's table), then the kept reads
-// one after the other -- the serial form of the scan -- and their words through ktrim_pack_word
+// the host twin of pg_kindex_trim: every read's span (every k-mer asks its owner's table: kidx_host_find), then the kept reads one after
+// the other -- the serial form of the scan -- and their words through ktrim_pack_word
 template <int NW>
-void ktrim_host_trim(const pg_kindex* ix, const uint64_t* packed, const uint64_t* word_off, const uint64_t* kmer_base, uint64_t n_seqs,
-                     uint32_t uniform_len, uint32_t min_cov, uint32_t min_len, uint64_t* out_span, uint64_t* packed_out, uint64_t* word_off_out,
-                     uint64_t* kmer_base_out, uint64_t* src_out, uint64_t* out_totals) {
+void ktrim_host_trim(const pg_kindex* ix, const KidxBatch& b, uint32_t min_cov, uint32_t min_len, uint64_t* out_span, uint64_t* packed_out,
+                     uint64_t* word_off_out, uint64_t* kmer_base_out, uint64_t* src_out, uint64_t* out_totals) {
     const int K = ix->K;
-    const uint32_t n = (uint32_t)ix->ranks.size();
     KtrimCounts total{{0, 0, 0, 0}};
-    for (uint64_t r = 0; r < n_seqs; r++) {
-        const KidxSeq q = kidx_seq(packed, word_off, kmer_base, uniform_len, K, r);
-        uint64_t span;
-        if (n) {
-            KtrimRun t = ktrim_run_none();
-            map_roll<NW>(q.rd, 0, q.nk, K, [&](const Kmer<NW>& ck, bool, int j) {
-                const KidxRank& rk = ix->ranks[map_owner<NW>(ck, n)];
-                ktrim_run_add(t, kcor_solid_word(kidx_find<NW>(rk.tab.data(), rk.slots - 1, ck), min_cov), j);
-            });
-            span = ktrim_span_word(t, K);
-        } else
-            span = ktrim_span_probe<NW>(q.rd, q.nk, K, ix->tab.data(), ix->slots - 1, min_cov);
+    for (uint64_t r = 0; r < b.n_seqs; r++) {
+        const KidxSeq q = kidx_seq(b, K, r);
+        KtrimRun t = ktrim_run_none();
+        map_roll<NW>(q.rd, 0, q.nk, K, [&](const Kmer<NW>& ck, bool, int j) { ktrim_run_add(t, kcor_solid_word(kidx_host_find<NW>(ix, ck), min_cov), j); });
+        const uint64_t span = ktrim_span_word(t, K);
         if (out_span) out_span[r] = span;
         if (!packed_out) continue;
         const KtrimCounts c = ktrim_counts(span, q.nk, K, min_len);
@@ -66,29 +57,18 @@ extern "C" int pg_kindex_trim(pg_kindex* ix, const uint64_t* packed, uint64_t n_
         return PG_EINVAL;
     }
     if (!packed_out && !out_span) { pg_set_error("pg_kindex_trim: out_span and packed_out are both null"); return PG_EINVAL; }
-    if (n_seqs && !packed) { pg_set_error("pg_kindex_trim: null read buffer"); return PG_EINVAL; }
-    if (n_seqs && !uniform_len && (!word_off || !kmer_base)) { pg_set_error("pg_kindex_trim: a ragged batch needs word_off and kmer_base"); return PG_EINVAL; }
-    if (uniform_len > 0x7FFFFFFFu) { pg_set_error("pg_kindex_trim: uniform_len out of range"); return PG_EINVAL; }
-    if (n_seqs && uniform_len) {
-        const uint64_t nk = (int)uniform_len >= ix->K ? (uint64_t)uniform_len - ix->K + 1 : 0;
-        if (n_kmers != n_seqs * nk) { pg_set_error("pg_kindex_trim: n_kmers does not match n_seqs * max(0, len - K + 1)"); return PG_EINVAL; }
-        if (n_words < n_seqs * (uint64_t)((uniform_len + 31) / 32) + (uint64_t)ix->nw + 1) {
-            pg_set_error("pg_kindex_trim: n_words is less than the reads' words and the nw + 1 readable words behind them");
-            return PG_EINVAL;
-        }
-    }
-    if (n_seqs && n_words < (uint64_t)ix->nw + 1) { pg_set_error("pg_kindex_trim: n_words does not hold the nw + 1 readable words"); return PG_EINVAL; }
+    const pg::KidxBatch b{packed, word_off, kmer_base, n_seqs, uniform_len, n_words, n_kmers};
+    // (an empty batch's counts are not looked at)
+    if (int rc = pg::kidx_batch_args("pg_kindex_trim", ix, b, "read", n_seqs ? pg::KIDX_ARGS_KMERS | pg::KIDX_ARGS_WORDS | pg::KIDX_ARGS_TAIL : 0u)) return rc;
     if (ix->device >= 0)
-        return pg::ktrim_device_trim(ix, packed, n_words, word_off, kmer_base, n_seqs, uniform_len, n_kmers, min_cov, min_len, out_span, packed_out,
-                                     word_off_out, kmer_base_out, src_out, out_totals, stream);
+        return pg::ktrim_device_trim(ix, b, min_cov, min_len, out_span, packed_out, word_off_out, kmer_base_out, src_out, out_totals, stream);
     if (!n_seqs) {
         if (packed_out) for (int i = 0; i < pg::KTRIM_COUNTS; i++) out_totals[i] = 0;
         return PG_OK;
     }
-    if (ix->nw == 4) pg::ktrim_host_trim<4>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, min_cov, min_len, out_span, packed_out, word_off_out,
-                                            kmer_base_out, src_out, out_totals);
-    else pg::ktrim_host_trim<2>(ix, packed, word_off, kmer_base, n_seqs, uniform_len, min_cov, min_len, out_span, packed_out, word_off_out,
-                                kmer_base_out, src_out, out_totals);
+    pg::kidx_with_nw(ix->nw, [&](auto nw) {
+        pg::ktrim_host_trim<decltype(nw)::value>(ix, b, min_cov, min_len, out_span, packed_out, word_off_out, kmer_base_out, src_out, out_totals);
+    });
     return PG_OK;
 }
 

@@ -3,7 +3,7 @@
 // sanitised).  Both flavours: the distinct k-mers of a random genome as records in 3 heap parts of exactly their sizes, an index over 3
 // ranks and one in one table, and ragged and uniform batches whose words lie on the heap with exactly NW + 1 words of tail behind the
 // last sequence -- the reach read_kmer is allowed.  Every answer and summary word of the two indexes must agree, and some k-mers must be
-// present and some absent.  The device engine is not linked: its entry points are stubs that fail.
+// present and some absent.  The device engine is not linked: its entry points are stubs that fail (kindex_engine_stubs.hpp).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,26 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "../include/soapdenovo2_amd.h"
-#include "kcorrect.hpp"
-#include "kindex.hpp"
-
-static std::string g_err;
-void pg_set_error(const std::string& s) { g_err = s; }
-extern "C" const char* pg_last_error(void) { return g_err.c_str(); }
-
-namespace pg {
-static int no_device() { pg_set_error("no device engine in this program"); return PG_ENODEV; }
-int kidx_device_build(::pg_kindex*, const uint64_t*, uint64_t, void*) { return no_device(); }
-int kidx_device_query(::pg_kindex*, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t, uint32_t, int, uint64_t*, uint64_t*, void*) { return no_device(); }
-void kidx_device_free(::pg_kindex*) {}
-int kidx_device_build_sharded(::pg_kindex*, const uint64_t* const*, const uint64_t*, const int*, int, void*) { return no_device(); }
-int kidx_device_query_sharded(::pg_kindex*, const uint64_t*, uint64_t, const uint64_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, int, uint64_t*,
-                              uint64_t*, void*) { return no_device(); }
-int kidx_device_query_times(::pg_kindex*, double*) { return no_device(); }
-int kcor_device_correct(::pg_kindex*, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, const KcorParams&, uint64_t*,
-                        uint64_t*, void*) { return no_device(); }
-}  // namespace pg
+#include "kindex_engine_stubs.hpp"
 
 #define CHECK(cond)                                                                             \
     do {                                                                                        \

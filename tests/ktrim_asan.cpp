@@ -4,7 +4,7 @@
 // reads with substitutions whose words lie on the heap with exactly NW + 1 words of tail (ones, like every pad bit), and every output
 // buffer on the heap at exactly the capacity the header states: packed_out n_words, word_off_out and src_out n_seqs, kmer_base_out
 // n_seqs + 1, out_totals 4.  The two indexes must agree word for word, and the output is checked against a base-by-base repack of the
-// spans.  The device engine is not linked: its entry points are stubs that fail.
+// spans.  The device engine is not linked: its entry points are stubs that fail (kindex_engine_stubs.hpp).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,30 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "../include/soapdenovo2_amd.h"
-#include "kcorrect.hpp"
-#include "kindex.hpp"
-#include "ktrim.hpp"
-
-static std::string g_err;
-void pg_set_error(const std::string& s) { g_err = s; }
-extern "C" const char* pg_last_error(void) { return g_err.c_str(); }
-
-namespace pg {
-static int no_device() { pg_set_error("no device engine in this program"); return PG_ENODEV; }
-int kidx_device_build(::pg_kindex*, const uint64_t*, uint64_t, void*) { return no_device(); }
-int kidx_device_query(::pg_kindex*, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t, uint32_t, int, uint64_t*, uint64_t*, void*) { return no_device(); }
-void kidx_device_free(::pg_kindex*) {}
-int kidx_device_build_sharded(::pg_kindex*, const uint64_t* const*, const uint64_t*, const int*, int, void*) { return no_device(); }
-int kidx_device_query_sharded(::pg_kindex*, const uint64_t*, uint64_t, const uint64_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, int, uint64_t*,
-                              uint64_t*, void*) { return no_device(); }
-int kidx_device_query_times(::pg_kindex*, double*) { return no_device(); }
-int kcor_device_correct(::pg_kindex*, const uint64_t*, const uint64_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, const KcorParams&, uint64_t*,
-                        uint64_t*, void*) { return no_device(); }
-int ktrim_device_trim(::pg_kindex*, const uint64_t*, uint64_t, const uint64_t*, const uint64_t*, uint64_t, uint32_t, uint64_t, uint32_t, uint32_t,
-                      uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, void*) { return no_device(); }
-int ktrim_device_times(::pg_kindex*, double*) { return no_device(); }
-}  // namespace pg
+#include "kindex_engine_stubs.hpp"
 
 #define CHECK(cond)                                                                             \
     do {                                                                                        \

@@ -1,5 +1,5 @@
 """The k-mer index cut over ranks on the GPU, every rank on GPU 0 (an ordinal may repeat: a rank is a table, a stream and its buffers):
-kidx_count_owners_kernel, kidx_build_owned_kernel, kidx_probe_owned_kernel, the rows' merge and kidx_summary_rows_kernel
+kidx_count_owners_kernel, kidx_build_kernel for an owner, kidx_probe_owned_kernel, the rows' merge and kidx_summary_rows_kernel
 (csrc/kindex_kernels.hip) against the independent model (tests/kindex_model.py), against the index in one table on the device and
 against the host twin, on the cases of tests/test_kindex_sharded_host.py -- but the duplicate key, which stays on the host twin: no test
 here is built around making a kernel fail.  Ranks on different physical GPUs are not run here.  All comparisons are of integers and
@@ -100,6 +100,37 @@ def test_same_words_as_one_table_and_as_the_host_twin(flavour, name):
         for wave in (False, True):
             assert (ix.words(seqs, wave) == want).all(), (n, wave)
         ix.close()
+
+
+@pytest.mark.parametrize("name", ["one", "n513"])
+@pytest.mark.parametrize("flavour", S.WIDE, ids=E.flavour_id)
+def test_one_table_is_a_one_rank_cut(flavour, name):
+    """pg_kindex_build's table is rank 0 of a cut over one rank: the build kernel with n == 1 works no owner out, whichever entry made
+    the index.  The same records -- a deleted one among them: `one` gets a deleted record of `n513` behind its own -- as an index in one
+    table, as a one-rank cut and as the host twin: the same keys, slots and bytes, and with the lane and the wave query the same
+    answers and summaries, which are the model's."""
+    K, mer127 = flavour
+    records = E.table(name, K, mer127)[0]
+    nw = records.shape[1] - 2
+    if name == "one":
+        more = E.table("n513", K, mer127)[0][1:]                               # (n513's first key is `one`'s)
+        records = np.concatenate([records, more[(more[:, nw] >> np.uint64(32 + 25)) & np.uint64(1) == 1][:1]])
+        assert len(records) == 2
+    assert ((records[:, nw] >> np.uint64(32 + 25)) & np.uint64(1)).any() and not ((records[:, nw] >> np.uint64(32 + 25)) & np.uint64(1)).all()
+    seqs = E.sequences(K)[0] + E.wave_sequences(K)[0][:8]
+    made = [E.Index(records, K, mer127, 0), S.Index(records, K, mer127, gpu(1)), E.Index(records, K, mer127, -1)]
+    assert [x.ix.sharded for x in made] == [False, True, False]
+    infos = [x.ix.info() for x in made]
+    assert all((i["keys"], i["slots"], i["bytes"]) == (len(records), M.table_slots(len(records)), api.host_kindex_bytes(len(records), mer127)) for i in infos)
+    assert all(len(i["ranks"]) == 1 and {k: i["ranks"][0][k] for k in ("keys", "slots", "bytes")} == {k: i[k] for k in ("keys", "slots", "bytes")} for i in infos)
+    want = made[2].check_ragged(seqs, what="host twin")
+    assert want[0].any() and not want[0].all()                               # (some k-mers present, some absent)
+    for x, what in zip(made[:2], ("one table", "one-rank cut")):
+        for wave in (False, True):
+            cnt, summ = x.check_ragged(seqs, wave, "%s wave=%s" % (what, wave))
+            assert (cnt == want[0]).all() and (summ == want[1]).all(), (what, wave)
+    for x in made:
+        x.close()
 
 
 @pytest.mark.parametrize("flavour", S.WIDE, ids=E.flavour_id)
