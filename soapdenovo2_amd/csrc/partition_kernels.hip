@@ -173,40 +173,49 @@ __device__ __forceinline__ uint32_t fastdiv1(uint32_t i, uint32_t d, uint32_t in
 // profiles/r02_k1k2_rewrite_ab.json.)
 //   load  the tile's reads as dword strings (hi dword of every 64-bit word first)
 //   A     thread = (read, 16 positions): m-mer values from two dwords, compile-time funnel shifts
-//   B     thread = (read, S k-mers): window minima with w + S reads (suffix / core / prefix), partition ids, run-start bits
-//   D     thread = the same segment: one LDS atomic reserves its items, every start bit finds the next start
-//   E     one lane per run: slot in the partition's stream (or the owner's send region), record from the dword string
+//   B     thread = (read, S k-mers): window minima with w + S reads (suffix / core / prefix), partition ids, run-start bits; one LDS
+//         atomic reserves the segment's places in the tile's item list, every start bit becomes an item (read, first k-mer | partition id)
+//   E     one lane per item: the run ends at the read's next start bit; slot in the partition's stream (or the owner's send region),
+//         record from the dword string
+// A read's row holds its dword string, its m-mer values and its start bits; the partition ids of its k-mers stay in phase B's registers
+// (only a run's first k-mer needs its id: 4.55 of 88 at 150 bp, K = 63), so the LDS a read takes -- which is what bounds the reads a CU
+// has in flight, profiles/k1_tile_life.json -- is 764 bytes there instead of 1016.
+// The item list holds sa.icap items for the whole tile (launch_tiled).  A segment whose reservation does not fit stores nothing and
+// raises `overflow`; such a tile forgets its list and is walked again segment by segment, a few reads at a time with one lane a read: tile_segment again from
+// the value rows (still intact), items that fit for certain, phase E on them.  Real reads do not get there; PG_K1_ITEM_CAP (test hook) sends every tile.
 // Lanes of a wave take different reads (read index fastest), so the row stride -- forced odd -- is the bank stride.
 // RAGGED: the reads of the batch have their own lengths (prlHashReads.c:642-648: lenBuffer[r], any read of K + 1 bases and more is
 // chopped the same way).  The tile's rows are as long as the batch's longest read needs; a read's length and first ordinal sit in LDS
 // beside its row, a segment past the read's last k-mer has no start bits, and everything else is the uniform kernel.
-struct SegArg { int R, np, npad, wsd, nseg, nca; uint32_t inv_R, inv_wpr; };
+struct SegArg { int R, np, npad, wsd, nseg, nca, icap; uint32_t inv_R, inv_wpr; };
 
 // W: the window length (m-mers a k-mer) at compile time, with 16-mers (0: whatever the geometry says) -- the loops of phase B
 // unroll into loads with immediate offsets, phase A loses its shifts by 32 - 2m.
 template <int NW, bool ROUTE, int S, int W = 0, bool RAGGED = false>
+#if defined(PG_MEASURE) && defined(PG_K1_WAVES)
+__attribute__((amdgpu_waves_per_eu(PG_K1_WAVES, PG_K1_WAVES)))          // (the A/B of the register budget: make MEASURE=1 XDEF=PG_K1_WAVES=8)
+#endif
 __global__ __launch_bounds__(BLOCK) void skm_scatter_seg_kernel(ReadsArg a, E2Dev e, DevCounters* ctr, SegArg sa, RouteArg ro) {
     constexpr int PW = E2Cfg<NW>::PW, RW = PW + 1;
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    const int R = sa.R, np = sa.np, npad = sa.npad, wsd = sa.wsd, nseg = sa.nseg, nca = sa.nca;
+    const int R = sa.R, np = sa.np, npad = sa.npad, wsd = sa.wsd, nseg = sa.nseg, nca = sa.nca, icap = sa.icap;
     const int wpr = (int)a.wpr, kpr = (int)a.kpr, len = (int)a.uniform_len;      // (RAGGED: wpr, kpr, np = the longest read's)
     uint32_t* dw = (uint32_t*)smem_raw;                           // R * wsd   dword strings
-    uint32_t* v0 = dw + (size_t)R * wsd;                          // R * npad  m-mer values; the item list after B
-    // (odd row strides here too: lanes of a wave take different reads, so the row stride is the bank stride -- nseg * S = 88 and nseg = 8 at 150 bp, K = 63
+    uint32_t* v0 = dw + (size_t)R * wsd;                          // R * npad  m-mer values
+    // (odd row strides here too: lanes of a wave take different reads, so the row stride is the bank stride -- nseg = 8 at 150 bp, K = 63
     //  put a wave's 64 rows on 8 banks each: SQ_LDS_BANK_CONFLICT was 2.2x the LDS issue cycles of this kernel, profiles/r04p_pmc_sq_bench20M.json)
-    const int kpad = (nseg * S) | 1;                              // partition ids: whole segments, so a segment stores all S of its ids
     const int mpad = nseg | 1;
-    uint32_t* pids = v0 + (size_t)R * npad;                       // R * kpad
-    uint32_t* smask = pids + (size_t)R * kpad;                    // R * mpad  run-start bits
-    uint32_t* ranks = smask + (size_t)R * mpad;                   // R * kpr   (ROUTE only)
-    uint32_t* items = v0;
+    uint32_t* smask = v0 + (size_t)R * npad;                      // R * mpad  run-start bits
+    uint32_t* ikey = smask + (size_t)R * mpad;                    // icap      items: read << 24 | first k-mer << 12
+    uint32_t* ipid = ikey + icap;                                 // icap      ... and the partition id
+    uint32_t* ranks = ipid + icap;                                // icap      (ROUTE only)
     // RAGGED: per read its first k-mer among the batch's (8-byte aligned: the rows above are dwords) and its length
-    uint64_t* rkb = (uint64_t*)(((uintptr_t)(ranks + (ROUTE ? (size_t)R * kpr : 0)) + 7) & ~(uintptr_t)7);
+    uint64_t* rkb = (uint64_t*)(((uintptr_t)(ranks + (ROUTE ? icap : 0)) + 7) & ~(uintptr_t)7);
     int* rlen = (int*)(rkb + R);
-    __shared__ unsigned int n_items;
+    __shared__ unsigned int n_items, overflow;
     const uint64_t r0 = (uint64_t)blockIdx.x * R;
     const int nr = (int)min((uint64_t)R, a.n_reads - r0);
-    if (threadIdx.x == 0) n_items = 0;
+    if (threadIdx.x == 0) { n_items = 0; overflow = 0; }
     if (RAGGED) {
         for (int r = threadIdx.x; r < nr; r += BLOCK) {
             const uint64_t kb = a.cls_len ? a.cls_kb[r0 + r] : a.kmer_base[r0 + r];
@@ -241,73 +250,80 @@ __global__ __launch_bounds__(BLOCK) void skm_scatter_seg_kernel(ReadsArg a, E2De
     // (Phase B with the block minima of a read shared between its segments -- suffix minima first, a barrier, cores from three block minima instead of
     //  37 values: 29 LDS loads a segment instead of 59 -- was built and measured in round 5: 62.3 ms against 57.0 per 200 M reads on one box,
     //  profiles/r05c_k1_shared_minima_ab.json.  The loads it saves have immediate offsets and pipeline; the barrier and the second pass do not.)
-    for (int t = threadIdx.x; t < R * nseg; t += BLOCK) {
-        const int seg = (int)fastdiv1(t, R, sa.inv_R), r = t - seg * R;
-        if (r >= nr) continue;
-        const int j0 = seg * S;
-        const int kpr_r = RAGGED ? rlen[r] - e.g.K + 1 : kpr, np_r = RAGGED ? rlen[r] - m + 1 : np;
-        const int cnt = min(S, kpr_r - j0);
-        if (RAGGED && cnt <= 0) { smask[r * mpad + seg] = 0; continue; }       // behind the read's last k-mer
-        uint32_t pid[S];
-        const uint32_t mk = tile_segment<S, W>(v0 + r * npad, np_r, j0, cnt, w, e.g.nmax, e.g.part_mul, pid);
-        smask[r * mpad + seg] = mk;
-#pragma unroll
-        for (int i = 0; i < S; i++) pids[r * kpad + j0 + i] = pid[i];
-    }
-    __syncthreads();                                              // v0 is dead from here: the item list takes its place
-    for (int t = threadIdx.x; t < R * nseg; t += BLOCK) {
-        const int seg = (int)fastdiv1(t, R, sa.inv_R), r = t - seg * R;
-        uint32_t mk = r < nr ? smask[r * mpad + seg] : 0u;
-        if (mk) {
-            unsigned int at = atomicAdd(&n_items, (unsigned int)__popc(mk));
-            while (mk) {
-                const int i = __ffs((int)mk) - 1;
-                mk &= mk - 1;
-                const int j = seg * S + i;
-                const int nxt = tile_next_start(smask + r * mpad, seg, nseg, S, i, RAGGED ? rlen[r] - e.g.K + 1 : kpr);
-                items[at++] = ((uint32_t)r << 24) | ((uint32_t)j << 12) | (uint32_t)(nxt - j);
-            }
-        }
-    }
-    __syncthreads();
-    const int total = (int)n_items;
+    // (a read longer than BLOCK segments' worth takes several rounds of the loop over t: the items of a round simply follow those of the one before)
+    // Turn 0 takes every segment of the tile.  If its items do not fit, the tile is taken again in turns of ONE segment of `gsz` reads (one lane a read),
+    // whose items always fit: gsz * S <= icap.  A later turn computes what turn 0 computed for its segments, start bits included.
+    const int gsz = icap / S;                                     // (>= 1: launch_tiled)
+    int turn_seg = -1, turn_r = 0;                                // turn 0: the whole tile
     __shared__ unsigned int ocnt[256];
     __shared__ unsigned long long obase[256];
-    if (ROUTE) {
-        ocnt[threadIdx.x] = 0;
-        __syncthreads();
-        for (int it = threadIdx.x; it < total; it += BLOCK) {
-            const uint32_t pk = items[it];
-            const uint32_t pid = pids[(int)(pk >> 24) * kpad + (int)((pk >> 12) & 0xFFF)];
-            ranks[it] = atomicAdd(&ocnt[pid % (uint32_t)ro.n_owners], 1u);
+    for (;;) {
+        const bool whole = turn_seg < 0;
+        const int ntask = whole ? R * nseg : min(gsz, nr - turn_r);
+        for (int t = threadIdx.x; t < ntask; t += BLOCK) {
+            int seg, r;
+            if (whole) { seg = (int)fastdiv1(t, R, sa.inv_R); r = t - seg * R; }
+            else { seg = turn_seg; r = turn_r + t; }
+            if (r >= nr) continue;
+            const int j0 = seg * S;
+            const int kpr_r = RAGGED ? rlen[r] - e.g.K + 1 : kpr, np_r = RAGGED ? rlen[r] - m + 1 : np;
+            const int cnt = min(S, kpr_r - j0);
+            if (RAGGED && cnt <= 0) { smask[r * mpad + seg] = 0; continue; }       // behind the read's last k-mer
+            uint32_t pid[S];
+            const uint32_t mk = tile_segment<S, W>(v0 + r * npad, np_r, j0, cnt, w, e.g.nmax, e.g.part_mul, pid);
+            smask[r * mpad + seg] = mk;
+            if (mk) {
+                const unsigned int n = (unsigned int)__popc(mk), at = atomicAdd(&n_items, n);
+                if (at + n > (unsigned int)icap) overflow = 1;    // (turn 0 only) nothing is stored, the list is forgotten below
+                else tile_put_items<S>(mk, pid, r, j0, at, ikey, ipid);
+            }
         }
         __syncthreads();
-        if ((int)threadIdx.x < ro.n_owners && ocnt[threadIdx.x])
-            obase[threadIdx.x] = atomicAdd(&ro.cursor[threadIdx.x], (unsigned long long)ocnt[threadIdx.x]);
-        __syncthreads();
-    }
-    for (int it = threadIdx.x; it < total; it += BLOCK) {
-        const uint32_t pk = items[it];
-        const int r = (int)(pk >> 24), j0 = (int)((pk >> 12) & 0xFFF), n = (int)(pk & 0xFFF);
-        const uint32_t pid = pids[r * kpad + j0];
-        uint64_t* out;
-        uint32_t q = 0;
-        // the returned atomic on the partition's cursor is asked first and looked at after the record is built
-        if (!ROUTE) q = atomicAdd(&e.cursor[pid], 1u);
-        uint64_t rec[RW];
-        if (RAGGED) tile_make_record<PW>(dw + r * wsd, rlen[r], j0, n, a.ord_base + rkb[r], e.g.K, rec);
-        else tile_make_record<PW>(dw + r * wsd, len, j0, n, a.ord_base + (r0 + (uint64_t)r) * (uint64_t)kpr, e.g.K, rec);
+        const bool over = whole && overflow != 0;
+        const int total = over ? 0 : (int)n_items;
         if (ROUTE) {
-            const uint32_t o = pid % (uint32_t)ro.n_owners;
-            const unsigned long long at = obase[o] + ranks[it];
-            if (at >= ro.cap) { atomicOr(&ctr->e2_flags, F_ROUTE); continue; }
-            ro.pids[(uint64_t)o * ro.cap + at] = pid;
-            out = ro.recs + ((uint64_t)o * ro.cap + at) * RW;
-        } else out = record_slot(e, pid, q, ctr, RW);
-        if (!out) continue;
-        ulonglong2* o2 = (ulonglong2*)out;
+            ocnt[threadIdx.x] = 0;
+            __syncthreads();
+            for (int it = threadIdx.x; it < total; it += BLOCK)
+                ranks[it] = atomicAdd(&ocnt[ipid[it] % (uint32_t)ro.n_owners], 1u);
+            __syncthreads();
+            if ((int)threadIdx.x < ro.n_owners && ocnt[threadIdx.x])
+                obase[threadIdx.x] = atomicAdd(&ro.cursor[threadIdx.x], (unsigned long long)ocnt[threadIdx.x]);
+            __syncthreads();
+        }
+        for (int it = threadIdx.x; it < total; it += BLOCK) {
+            const uint32_t key = ikey[it], pid = ipid[it];
+            int r, j0, n;
+            tile_item_run<S>(key, smask, mpad, nseg, RAGGED ? rlen[(int)(key >> 24)] - e.g.K + 1 : kpr, r, j0, n);
+            uint64_t* out;
+            uint32_t q = 0;
+            // the returned atomic on the partition's cursor is asked first and looked at after the record is built
+            if (!ROUTE) q = atomicAdd(&e.cursor[pid], 1u);
+            uint64_t rec[RW];
+            if (RAGGED) tile_make_record<PW>(dw + r * wsd, rlen[r], j0, n, a.ord_base + rkb[r], e.g.K, rec);
+            else tile_make_record<PW>(dw + r * wsd, len, j0, n, a.ord_base + (r0 + (uint64_t)r) * (uint64_t)kpr, e.g.K, rec);
+            if (ROUTE) {
+                const uint32_t o = pid % (uint32_t)ro.n_owners;
+                const unsigned long long at = obase[o] + ranks[it];
+                if (at >= ro.cap) { atomicOr(&ctr->e2_flags, F_ROUTE); continue; }
+                ro.pids[(uint64_t)o * ro.cap + at] = pid;
+                out = ro.recs + ((uint64_t)o * ro.cap + at) * RW;
+            } else out = record_slot(e, pid, q, ctr, RW);
+            if (!out) continue;
+            ulonglong2* o2 = (ulonglong2*)out;
 #pragma unroll
-        for (int k = 0; k < RW / 2; k++) o2[k] = make_ulonglong2(rec[2 * k], rec[2 * k + 1]);
+            for (int k = 0; k < RW / 2; k++) o2[k] = make_ulonglong2(rec[2 * k], rec[2 * k + 1]);
+        }
+        if (whole) {
+            if (!over) break;
+            turn_seg = 0;
+        } else {
+            turn_r += gsz;
+            if (turn_r >= nr) { turn_r = 0; if (++turn_seg == nseg) break; }
+        }
+        __syncthreads();                                          // everybody is done with the list of this turn
+        if (threadIdx.x == 0) n_items = 0;
+        __syncthreads();
     }
 }
 
@@ -1662,28 +1678,23 @@ static int launch_tiled(pg_ctx* c, const ReadsArg& a, const RouteArg* route, hip
     const SkmGeom& g = c->e2.g;
     const bool ragged = a.uniform_len == 0;                                   // rows for the batch's longest read (a.kpr, a.wpr: its)
     const int kpr = (int)a.kpr, wpr = (int)a.wpr, np = (int)(ragged ? a.max_len : a.uniform_len) - g.m + 1;
-    int S = tile_pick_segment(kpr, g.w);
-    if (const char* v = env_measure("PG_K1_S")) { const int q = atoi(v); if (q >= 7 && q <= 15 && (q & 1) && (q <= g.w || q == 7)) S = q; }
-    const int nseg = (kpr + S - 1) / S, nca = (np + 15) / 16, npad = (16 * nca) | 1, wsd = (2 * wpr + 3) | 1;   // value rows: whole 16-position chunks, odd stride
-    const size_t per_read = (size_t)(wsd + npad + ((nseg * S) | 1) + (nseg | 1) + (route ? kpr : 0)) * 4 + (ragged ? 12 : 0);     // (the kernel's rows: dword string, values, partition ids, start bits, ranks; ragged: first k-mer + length)
-    int R = std::min<int>(128, std::max(1, BLOCK / nseg));                     // one pass of phase B per tile
-    R = (int)std::min<size_t>((size_t)R, (60 * 1024) / per_read);
-    // ... and about 25 KB of LDS a tile, i.e. five workgroups a CU: measured at 150 bp (profiles/r03v_k1_tile_sizes.json), K = 63
-    // (1016 B a read): 12 / 16 / 20 / 24 / 28 / 32 / 56 reads -> 84.7 / 73.6 / 65.9 / 59.5 - 61.1 / 61.6 / 66.8 - 67.3 / 108.9 ms per
-    // 200 M reads; K = 127 (760 B a read): 16 / 24 / 32 / 48 / 80 -> 57.7 / 42.1 / 38.1 / 41.4 / 54.3 ms
-    {
-        const int r_lds = (int)(((25 * 1024) / per_read) & ~(size_t)7);
-        if (r_lds >= 8) R = std::min(R, r_lds);
-    }
+    int force_S = 0;
+    if (const char* v = env_measure("PG_K1_S")) { const int q = atoi(v); if (q >= 7 && q <= 15 && (q & 1) && (q <= g.w || q == 7)) force_S = q; }
+    const TilePlan tp = tile_plan(kpr, g.w, wpr, np, route != nullptr, ragged, BLOCK, force_S);     // (skm_tile.hpp: segment length, rows, item room, reads a tile)
+    const int S = tp.S, nseg = tp.nseg, nca = tp.nca, npad = tp.npad, wsd = tp.wsd, cap = tp.cap;
+    const size_t per_read = tp.row_bytes;
+    int R = tp.R;
     if (const char* v = env_measure("PG_K1_R")) R = std::max(1, std::min(atoi(v), (int)std::min<size_t>(128, (60 * 1024) / per_read)));
     if (R < 1) return 1;
     const uint64_t grid = (a.n_reads + R - 1) / R;
     if (grid > 0x7FFFFFFFULL) { pg_set_error("batch too large for one launch"); return PG_EINVAL; }
     auto inv = [](uint32_t d) { return (uint32_t)(((1ULL << 32) + d - 1) / d); };
-    SegArg sa{R, np, npad, wsd, nseg, nca, inv((uint32_t)R), inv(a.wpr)};
+    // PG_K1_ITEM_CAP (test hook): a smaller list in the same tile, so that tiles of ordinary reads overflow it and take the slow path
+    const int icap = tile_list_items(cap, R, env_int(env_test("PG_K1_ITEM_CAP"), 0));
+    SegArg sa{R, np, npad, wsd, nseg, nca, icap, inv((uint32_t)R), inv(a.wpr)};
     RouteArg ro{nullptr, nullptr, nullptr, 0, 1};
     if (route) ro = *route;
-    const size_t smem = per_read * R + (ragged ? 8 : 0);                      // (+ the alignment of the 8-byte row)
+    const size_t smem = per_read * R + (ragged ? 8 : 0) + (cap * R < 16 ? 16 * 12 : 0);      // (+ the alignment of the 8-byte row, + the shortest list)
     if (c->NW == 2) {
         if (route) launch_seg_rg<2, true>(ragged, S, g.m, g.w, dim3((unsigned)grid), smem, st, a, dev_view(c), c->ctr, sa, ro);
         else launch_seg_rg<2, false>(ragged, S, g.m, g.w, dim3((unsigned)grid), smem, st, a, dev_view(c), c->ctr, sa, ro);

@@ -9,11 +9,15 @@
 //                           all S + 1 windows share the core [first k-mer + S - 1, first k-mer - 1 + w), so
 //                           min(window j) = min(suffix-min up to the core, core, prefix-min behind the core);
 //                           then partition ids and the run-start bits of the S k-mers
-//   D  tile_next_start      where the run that starts at a given bit ends (the next start bit, in this or a later segment)
-//   E  tile_make_record<PW> the record of a run from the dword string
+//      tile_put_items<S>    ... and one item per start bit -- (read, first k-mer) and the partition id -- into the tile's bounded item list
+//   E  tile_item_run<S>     the run an item starts: it ends at the read's next start bit (tile_next_start), in this or a later segment
+//      tile_make_record<PW> the record of a run from the dword string
+// A tile whose runs outnumber its item list drops the list and is taken again in turns of ONE segment of a few reads (one lane a read:
+// tile_segment and tile_put_items again, then E), few enough that a turn's items fit for certain: slower, and exactly the same runs.
+//   tile_plan               the geometry of a tile for a batch's read length: segment length, row strides, item room, reads a tile
 //
-// Everything here is plain inline code shared with the CPU harness (tests/emu_skm.cpp), which runs the same phases serially
-// and compares the records with skm_split_read + skm_make_record.
+// Everything here is plain inline code shared with the CPU harnesses (tests/emu_skm.cpp, tests/emu_k1_items.cpp), which run the same
+// phases serially and compare the records with skm_split_read + skm_make_record.
 #pragma once
 #include "skm.hpp"
 #include "occ32.hpp"
@@ -109,6 +113,28 @@ PG_HD uint32_t tile_segment(const uint32_t* v, int np, int j0, int cnt, int w_rt
     return mask;
 }
 
+// B -> E: the start bits `mk` of the segment at k-mer j0 of read r as items at place `at` of the list: key = r << 24 | j << 12 (r < 256,
+// j < 4096) and the partition id beside it.  Compile-time indices into pid[], so the ids stay in registers.
+template <int S>
+PG_HD void tile_put_items(uint32_t mk, const uint32_t* pid, int r, int j0, uint32_t at, uint32_t* keys, uint32_t* ids) {
+#pragma unroll
+    for (int i = 0; i < S; i++)
+        if ((mk >> i) & 1u) { keys[at] = ((uint32_t)r << 24) | ((uint32_t)(j0 + i) << 12); ids[at] = pid[i]; at++; }
+}
+// items a read of a tile's list: 2.5 times the records a read is expected to make (2 kpr / (w + 1) + 1, as the record pool is sized), at least 8,
+// at most one a k-mer.  The list is pooled over the tile's reads.
+inline int tile_item_cap(int kpr, int w) {
+    const int want = (int)(2.5 * (2.0 * kpr / (w + 1) + 1.0) + 0.999999);
+    const int lo = want < 8 ? 8 : want;
+    return lo < kpr ? lo : kpr;
+}
+// items of a tile's list: `cap` a read (a smaller `forced` one: the test hook PG_K1_ITEM_CAP), and never fewer than 16 -- one segment of one read
+// (S <= 15 start bits) always fits, which is what the turns of an overflowed tile rely on
+inline int tile_list_items(int cap, int R, int forced) {
+    const int n = (forced >= 1 && forced < cap ? forced : cap) * R;
+    return n < 16 ? 16 : n;
+}
+
 // D: end of the run that starts at bit i of segment `seg`: the next start bit of the read (segments seg .. nseg - 1, S
 // k-mers each), or kpr.  masks = the read's segment masks.
 PG_HD int tile_next_start(const uint32_t* masks, int seg, int nseg, int S, int i, int kpr) {
@@ -120,6 +146,14 @@ PG_HD int tile_next_start(const uint32_t* masks, int seg, int nseg, int S, int i
         if (mk) return sg * S + __builtin_ffs((int)mk) - 1;
     }
     return kpr;
+}
+
+// E: the run of an item key: read r, first k-mer j0, n k-mers.  masks = the tile's start bits, mpad words a read; kpr_r = the read's k-mers.
+template <int S>
+PG_HD void tile_item_run(uint32_t key, const uint32_t* masks, int mpad, int nseg, int kpr_r, int& r, int& j0, int& n) {
+    r = (int)(key >> 24); j0 = (int)((key >> 12) & 0xFFF);
+    const int seg = j0 / S;
+    n = tile_next_start(masks + r * mpad, seg, nseg, S, j0 - seg * S, kpr_r) - j0;
 }
 
 // E: the record of the run [j0, j0 + n) of a read of `len` bases given as a dword string (two zero dwords behind it).
@@ -155,6 +189,39 @@ inline int tile_pick_segment(int kpr, int w) {
         if (eff > best_eff) { best_eff = eff; best = s; }
     }
     return best;
+}
+
+// ---- the geometry of a tile (host side: launch_tiled; the harnesses and the GPU tests ask the same function)
+// kpr / wpr / np: k-mers, 64-bit words and m-mers of the batch's (longest) read; w: m-mers a k-mer; block: threads a workgroup.
+// route: the tile ranks its items by owner (a third word an item); ragged: a read's first k-mer and length beside its row.
+// force_S: a segment length to take instead of the chosen one (measure builds), 0 = none.
+struct TilePlan { int S, nseg, nca, npad, wsd, cap, R; size_t row_bytes; };
+inline TilePlan tile_plan(int kpr, int w, int wpr, int np, bool route, bool ragged, int block, int force_S = 0) {
+    TilePlan p;
+    p.nca = (np + 15) / 16; p.npad = (16 * p.nca) | 1; p.wsd = (2 * wpr + 3) | 1;   // value rows: whole 16-position chunks, odd stride
+    p.cap = tile_item_cap(kpr, w);
+    // a read's rows: dword string, values, start bits, its share of the item list -- key, partition id, rank; ragged: first k-mer + length
+    auto row_bytes = [&](int s) { return (size_t)(p.wsd + p.npad + (((kpr + s - 1) / s) | 1) + (route ? 3 : 2) * p.cap) * 4 + (ragged ? 12 : 0); };
+    // About 25 KB of LDS a tile.  K1's time follows the reads a CU holds in LDS (profiles/k1_tile_life.json), which is workgroups a CU x reads a
+    // tile; a CU takes 160 KB of tiles and at most 7 of these workgroups (28 waves: registers), and a tile takes at most the reads of one pass of phase B
+    // (block / nseg: a second, mostly idle pass costs more than its reads bring).  Measured per 200 M reads (profiles/k1_lds_footprint_ab.json):
+    //   150 bp, K = 63 (764 B a read, S = 11): 20 / 24 / 28 / 32 / 36 / 40 / 48 reads -> 56.1 / 50.5 / 47.7 / 46.7 / 54.9 / 52.5 / 54.3 ms
+    //   150 bp, K = 127 (708 B a read, S = 13): 24 / 32 / 40 / 48 / 64 -> 37.0 / 31.5 / 35.1 / 37.0 / 41.4 ms
+    //   100 bp, K = 31 (S = 7: 25 reads a pass; 9: 32; 15: 51): S, reads = 7, 25 / 7, 20 / 9, 28 / 9, 32 / 15, 40 / 15, 51 -> 96.8 / 95.1 / 94.0 / 91.6 / 90.8 / 93.9 ms
+    // (with the per-k-mer partition ids in LDS, 1016 B a read at K = 63, the best was 24 reads and 54.7 ms: profiles/r03v_k1_tile_sizes.json)
+    auto lds_reads = [&](int s) { return (int)(((25 * 1024) / row_bytes(s)) & ~(size_t)7); };
+    p.S = tile_pick_segment(kpr, w);
+    // The segment with the least padding may be so short that one pass of phase B holds fewer reads than the LDS target: the next longer ones then.
+    // INFERRED FROM ONE SHAPE: 100 bp, K = 31, where S = 7 (25 reads a tile, 7 workgroups a CU) measured 96.8 ms against the parent's 93.5 and S = 9
+    // (32 reads) 87.8 - 91.6.  Other geometries the rule moves (250 bp, K = 63: S = 9 -> 13) have not been timed; any S cuts the same records.
+    while (p.S + 2 <= 15 && p.S + 2 <= w && block / ((kpr + p.S - 1) / p.S) < lds_reads(p.S)) p.S += 2;
+    if (force_S) p.S = force_S;
+    p.nseg = (kpr + p.S - 1) / p.S;
+    p.row_bytes = row_bytes(p.S);
+    p.R = block / p.nseg < 1 ? 1 : (block / p.nseg > 128 ? 128 : block / p.nseg);            // one pass of phase B per tile (the item key holds 8 bits of read)
+    if ((size_t)p.R > (60 * 1024) / p.row_bytes) p.R = (int)((60 * 1024) / p.row_bytes);     // (0: the reads are too long for a tile)
+    if (lds_reads(p.S) >= 8 && p.R > lds_reads(p.S)) p.R = lds_reads(p.S);
+    return p;
 }
 
 }  // namespace pg
