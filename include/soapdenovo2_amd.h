@@ -510,7 +510,24 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       `stream` waits for them, ORs their rows together and takes the summary from the merged rows.  The host waits
  *                       only where a buffer has to grow past the largest batch met so far.  On an index in one table it is
  *                       pg_kindex_query.  pg_kindex_query itself returns PG_EINVAL on an index cut over ranks, and pg_kindex_correct
- *                       PG_ESTATE: its trials are chains of dependent lookups, which merged rows cannot answer.
+ *                       PG_ESTATE: its kernel chases one lookup after the other in one table.  The corrector's rule is answered from
+ *                       merged rows by pg_kindex_correct_rows.
+ *   pg_kindex_correct_rows       pg_kindex_correct on any index, by rounds over merged rows (csrc/kcorrect_rows.hpp).  The batch, its
+ *                       tail, n_words and n_kmers are pg_kindex_query_words' and pg_kindex_trim's; packed_out, out_report, in-place
+ *                       use, the report word, the rule and the argument errors are pg_kindex_correct's, and so is the result, bit for
+ *                       bit.  A k-mer that holds no changed base is answered by the rows of the read as given, and a trial's questions
+ *                       are fixed before its answers: three sequences of 2K - 1 bases a trial.  So a round is: every read with a
+ *                       trial due writes its three sequences (at most one trial a read a round, at most a fixed number of trials a
+ *                       round: a read without a slot waits for the next), one pg_kindex_query_words of them, one decision a trial; a
+ *                       read takes at most max_fixes + 2 trials.  PG_EINVAL also where n_kmers or n_words disagree with the batch;
+ *                       nothing is written then.  On an index in one table the call is pg_kindex_correct.
+ *                       Device memory of the lead's device, ordered on `stream` -- but unlike the other operators the call WAITS ON
+ *                       THE HOST, once a round, to learn how many trials the round holds; it returns when the last round is queued
+ *                       and known to be empty.  The index keeps scratch that grows to the largest batch met.  Host memory for a
+ *                       host-twin index, which runs the same rounds.
+ *   pg_kindex_correct_rows_stats the last pg_kindex_correct_rows of the index: out[0] rounds that held a trial, [1] trials, [2] k-mers
+ *                       asked in trials (3 K a trial), [3] host waits (the rounds and the empty one that ends them); zeros after a
+ *                       call on an index in one table.
  *   pg_kindex_ranks     the ranks of an index cut over ranks; 0: one table (pg_kindex_build, pg_kindex_from_ctx).
  *   pg_kindex_rank_info pg_kindex_info's four words of one rank: the keys it owns, its slots, its table's bytes, its device.
  *   pg_kindex_query_times        milliseconds of the last pg_kindex_query_words on a device index cut over ranks, from its events, after
@@ -541,6 +558,10 @@ pg_kindex *pg_kindex_from_ctx_sharded(pg_ctx *ctx, const int *devices, int n_dev
 int pg_kindex_query_words(pg_kindex *ix, const uint64_t *packed, uint64_t n_words, const uint64_t *word_off, const uint64_t *kmer_base,
                           uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, int wave, uint64_t *out_cnt, uint64_t *out_summary,
                           void *stream);
+int pg_kindex_correct_rows(pg_kindex *ix, const uint64_t *packed, uint64_t n_words, const uint64_t *word_off, const uint64_t *kmer_base,
+                           uint64_t n_seqs, uint32_t uniform_len, uint64_t n_kmers, uint32_t min_cov, uint32_t max_fixes, uint32_t min_run,
+                           uint64_t *packed_out, uint64_t *out_report, void *stream);
+int pg_kindex_correct_rows_stats(pg_kindex *ix, uint64_t out[4]);   /* last call: rounds, trials, k-mers asked in trials, host waits */
 int pg_kindex_ranks(const pg_kindex *ix);
 int pg_kindex_rank_info(const pg_kindex *ix, int rank, uint64_t out[4]);
 int pg_kindex_query_times(pg_kindex *ix, double out[4]);

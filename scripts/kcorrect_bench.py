@@ -7,6 +7,12 @@ correct call's copy of the batch included).  Writes profiles/kcorrect.json: seco
 reports add up to.  The query is the yardstick; no rate is asserted anywhere.  Needs a GPU; nothing falls back.
 
     python scripts/kcorrect_bench.py [--reads 10000000] [--min-cov 3] [--out profiles/kcorrect.json]
+
+--ranks N [N ...]: in the same process and on the same reads, the corrector on an index cut over N ranks of the one GPU
+(KmerIndex.correct_rows_uniform: rounds over merged rows) against this run's own correct_uniform, alternating in the same way.  Writes
+profiles/kcorrect_rows.json (--rows-out): seconds, medians, the ratio to the single table, and rounds, trials and host waits of the last
+call.  All ranks share one GPU, every rank rolls every k-mer and a trial asks three times the lookups: the single table's time is the
+yardstick, and no ratio is a target.
 """
 import argparse
 import json
@@ -19,6 +25,38 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def rows_bench(a, torch, api, kc, one, packed, out, n, L, e0, e1):
+    """--ranks: the same counter's records cut over N ranks of GPU 0 (KmerCounter.index(devices=(0,) * N)), correct_rows_uniform on them
+    against this run's own correct_uniform on the single table `one`, alternating, a.runs times after one warm-up each, an event pair
+    around each call -- the rows form's host waits lie between its events.  Writes a.rows_out; the single table's time is the yardstick."""
+    res = {"workload": f"{n} resident reads x {L} bp, genome {a.genome}, err {a.err}, K={a.kmer}, min_cov {a.min_cov}, max_fixes {api.CORRECT_MAX_FIXES}, "
+                       f"min_run {api.CORRECT_MIN_RUN}: corrected into a second buffer; every rank on GPU 0",
+           "device": torch.cuda.get_device_name(0), "ranks": {}}
+    out_rows = torch.empty_like(packed)
+    for ranks in a.ranks:
+        cut = kc.index(devices=(0,) * ranks)
+        runs = {"rows": [], "single_table": []}
+        for i in range(a.runs + 1):
+            for name in ("rows", "single_table"):
+                e0.record()
+                if name == "rows":
+                    _, rep_rows = cut.correct_rows_uniform(packed, n, L, a.min_cov, out=out_rows)
+                else:
+                    _, rep_one = one.correct_uniform(packed, n, L, a.min_cov, out=out)
+                e1.record()
+                torch.cuda.synchronize()
+                if i:
+                    runs[name].append(e0.elapsed_time(e1) * 1e-3)
+        med = {k: float(np.median(t)) for k, t in runs.items()}
+        res["ranks"][str(ranks)] = {"seconds": runs, "median_seconds": med, "rows_over_single_table": med["rows"] / med["single_table"],
+                                    "stats": cut.correct_rows_stats(), "same_words": bool(torch.equal(out_rows, out)),
+                                    "same_reports": bool(torch.equal(rep_rows, rep_one)), "index": cut.info()}
+        cut.close()
+    os.makedirs(os.path.dirname(a.rows_out), exist_ok=True)
+    json.dump(res, open(a.rows_out, "w"), indent=1)
+    print(json.dumps({r: {k: v[k] for k in ("median_seconds", "rows_over_single_table", "stats", "same_words")} for r, v in res["ranks"].items()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=10_000_000)
@@ -29,6 +67,8 @@ def main():
     ap.add_argument("--min-cov", type=int, default=3)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kcorrect.json"))
+    ap.add_argument("--ranks", type=int, nargs="+", default=[], help="also time correct_rows_uniform on an index cut over N ranks of the one GPU")
+    ap.add_argument("--rows-out", default=os.path.join(ROOT, "profiles", "kcorrect_rows.json"))
     a = ap.parse_args()
     import torch
     from soapdenovo2_amd import api, synth
@@ -47,7 +87,8 @@ def main():
     kc.finalize(0)
     distinct_before = kc.distinct()
     ix = kc.index()
-    kc.close()
+    if not a.ranks:
+        kc.close()
     out = torch.empty_like(packed)
     runs = {"correct": [], "query": []}
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -65,6 +106,9 @@ def main():
                 runs[name].append(e0.elapsed_time(e1) * 1e-3)
     f = api.report_fields(report)
     info = ix.info()
+    if a.ranks:
+        rows_bench(a, torch, api, kc, ix, packed, out, n, L, e0, e1)
+        kc.close()
     ix.close()
     kc = api.KmerCounter(K, n_sets=8, log2_slots=max(16, int(np.ceil(np.log2(expected / 0.7)))))
     kc.count_uniform(out, n, L, 0)

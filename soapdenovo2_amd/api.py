@@ -10,6 +10,7 @@ Mirrors the reference's entry points `int call_pregraph(int argc, char **argv)` 
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import subprocess
 import sys
@@ -194,6 +195,9 @@ def lib() -> C.CDLL:
     L.pg_kindex_from_ctx_sharded.restype = C.c_void_p
     L.pg_kindex_from_ctx_sharded.argtypes = [C.c_void_p, u64p, C.c_int, C.c_void_p]
     L.pg_kindex_query_words.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u64p, u64p, C.c_void_p]
+    L.pg_kindex_correct_rows.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, u64p, u64p, C.c_void_p]
+    L.pg_kindex_correct_rows_stats.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_ranks.argtypes = [C.c_void_p]
     L.pg_kindex_rank_info.argtypes = [C.c_void_p, C.c_int, u64p]
     L.pg_kindex_query_times.argtypes = [C.c_void_p, u64p]
@@ -215,7 +219,7 @@ EXPORTED_SYMBOLS = [
     "pg_map_reads_sharded", "pg_map_hits_sharded", "pg_map_long_reads_sharded", "pg_host_map_owner", "pg_host_map_plan",
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
-    "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times",
+    "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times", "pg_kindex_correct_rows", "pg_kindex_correct_rows_stats",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
@@ -915,7 +919,8 @@ class KmerIndex:
     `KmerIndex.from_records(records, K)`.  On a GPU the batches and the answers are torch tensors of that device; with device = -1
     (the host twin, no GPU) they are numpy arrays.  An answer is a record's cnt word, 0 for a k-mer that is not in the set.
     An index cut over ranks (`device` a sequence of ordinals, `from_parts`, `KmerCounter.index(devices)`) answers the same queries with
-    the same words; its batches and answers lie on the lead's device, `device`; it trims reads but does not correct them."""
+    the same words; its batches and answers lie on the lead's device, `device`; it trims reads, and corrects them through correct_rows_uniform / correct_rows_ragged (correct_uniform and
+    correct_ragged refuse it)."""
 
     def __init__(self, handle, K: int, mer127: bool, device: int):
         self.h, self.K, self.mer127, self.device = handle, K, mer127, device
@@ -1063,6 +1068,43 @@ class KmerIndex:
         """correct_uniform for reads of any lengths (pack_seqs_ragged); a read shorter than K comes back as it is, flagged."""
         return self._correct(d_packed, d_word_off, d_kmer_base, n_reads, 0, min_cov, max_fixes, min_run, out)
 
+    def _correct_rows(self, packed, word_off, kmer_base, n_reads, uniform_len, n_kmers, min_cov, max_fixes, min_run, out):
+        n_words = int(packed.size if self.device < 0 else packed.numel())
+        if out is None:
+            out = np.empty_like(packed) if self.device < 0 else self.torch.empty_like(packed)
+        elif int(out.size if self.device < 0 else out.numel()) < n_words:
+            raise PgError("KmerIndex: `out` is shorter than the batch")
+        # (one element at least: an empty array has no address)
+        report = np.zeros(max(n_reads, 1), dtype=np.uint64) if self.device < 0 else \
+            self.torch.zeros(max(n_reads, 1), dtype=self.torch.int64, device=f"cuda:{self.device}")
+        _check(lib().pg_kindex_correct_rows(self.h, self._ptr(packed), n_words, self._ptr(word_off), self._ptr(kmer_base), n_reads, uniform_len,
+                                            n_kmers, min_cov, max_fixes, min_run, self._ptr(out), self._ptr(report), self._stream()),
+               "pg_kindex_correct_rows")
+        return out, report[:n_reads]
+
+    def correct_rows_uniform(self, d_packed, n_reads: int, read_len: int, min_cov: int, max_fixes: int = CORRECT_MAX_FIXES,
+                             min_run: int = CORRECT_MIN_RUN, out=None):
+        """correct_uniform on any index, an index cut over ranks included (pg_kindex_correct_rows): the same arguments, the same
+        (packed_out, report), bit for bit.  The trials are answered by rounds of batch queries over the ranks, and the call waits for
+        the GPU once a round (correct_rows_stats); on an index in one table it is correct_uniform."""
+        nk = max(0, read_len - self.K + 1)
+        return self._correct_rows(d_packed, None, None, n_reads, read_len, n_reads * nk, min_cov, max_fixes, min_run, out)
+
+    def correct_rows_ragged(self, d_packed, d_word_off, d_kmer_base, n_reads: int, min_cov: int, max_fixes: int = CORRECT_MAX_FIXES,
+                            min_run: int = CORRECT_MIN_RUN, out=None, n_kmers=None):
+        """correct_rows_uniform for reads of any lengths (pack_seqs_ragged).  n_kmers = d_kmer_base[n_reads]; where it is not given it
+        is read from there, which on a GPU waits for the stream."""
+        if n_kmers is None:
+            n_kmers = int(d_kmer_base[n_reads]) if n_reads else 0
+        return self._correct_rows(d_packed, d_word_off, d_kmer_base, n_reads, 0, n_kmers, min_cov, max_fixes, min_run, out)
+
+    def correct_rows_stats(self) -> dict:
+        """The last correct_rows_* call of this index (pg_kindex_correct_rows_stats): rounds that held a trial, trials, k-mers asked in
+        trials, and the times the host waited for the GPU; zeros after a call on an index in one table."""
+        out = np.zeros(4, dtype=np.uint64)
+        _check(lib().pg_kindex_correct_rows_stats(self.h, out.ctypes.data), "pg_kindex_correct_rows_stats")
+        return {"rounds": int(out[0]), "trials": int(out[1]), "trial_kmers": int(out[2]), "host_waits": int(out[3])}
+
     def _trim(self, packed, word_off, kmer_base, n_reads, uniform_len, n_kmers, min_cov, min_len, pack):
         n_words = int(packed.size if self.device < 0 else packed.numel())
         min_len = self.K + 1 if min_len is None else min_len
@@ -1174,12 +1216,14 @@ def correct_reads(reads: Sequence[np.ndarray], index: KmerIndex, min_cov: int, m
     """Substitution errors of reads (base-code arrays, any lengths) corrected against the index: (a list of base-code arrays of the
     same lengths, the report words as a numpy uint64 array -- see report_fields)."""
     words, word_off, kmer_base = pack_seqs_ragged(reads, index.K)
+    # (an index cut over ranks: the rows form, which gives the same words)
+    correct = functools.partial(index.correct_rows_ragged, n_kmers=int(kmer_base[-1])) if index.sharded else index.correct_ragged
     if index.device < 0:
-        out, report = index.correct_ragged(words, word_off, kmer_base, len(reads), min_cov, max_fixes, min_run)
+        out, report = correct(words, word_off, kmer_base, len(reads), min_cov, max_fixes, min_run)
     else:
         t, dev = index.torch, f"cuda:{index.device}"
         up = lambda a: t.from_numpy(a.view(np.int64)).to(dev)
-        out, report = index.correct_ragged(up(words), up(word_off), up(kmer_base), len(reads), min_cov, max_fixes, min_run)
+        out, report = correct(up(words), up(word_off), up(kmer_base), len(reads), min_cov, max_fixes, min_run)
         out, report = out.cpu().numpy().view(np.uint64), report.cpu().numpy().view(np.uint64)
     return [unpack_seq(out[int(word_off[i]):], len(r)) for i, r in enumerate(reads)], report
 

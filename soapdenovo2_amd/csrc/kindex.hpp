@@ -210,6 +210,13 @@ struct pg_kindex {
     uint64_t cap_trim = 0;
     hipEvent_t e_trim[4] = {nullptr, nullptr, nullptr, nullptr};
     bool trimmed = false;          // e_trim has been recorded
+    // pg_kindex_correct_rows' scratch on `device` (kcorrect_rows.hpp): the reads' state words and as-given bits, a round's trial batch, its
+    // rows, the read of each trial and the claim counter.  It grows to the largest batch met; the event is the last correction's end
+    uint64_t* d_cor = nullptr;
+    uint64_t cap_cor = 0;
+    hipEvent_t e_cor = nullptr;
+    bool corrected = false;        // e_cor has been recorded
+    uint64_t cor_stats[4] = {0, 0, 0, 0};   // the last pg_kindex_correct_rows: rounds, trials, k-mers asked in trials, host waits
 };
 
 namespace pg {

@@ -41,6 +41,14 @@
 //   ktrim_pack_kernel          a lane per output word, the tail's nw + 1 zero words included: the kept read by binary search in
 //                              word_off_out, the word by ktrim_pack_word.  The launch covers the batch's n_words, which the result never
 //                              passes; how many of those lanes have a word is read from the totals on the device
+// The corrector on an index cut over ranks (kcorrect_rows.hpp; pg_kindex_correct_rows): rounds of plan, query, decide on the
+// caller's stream, every query kidx_query_ranks, and the host reads the round's trial count back once a round
+//   kcor_rows_begin_kernel     a lane per read over its row of the read as given: weak count, anchor, first weak k-mer behind it, the
+//                              state words, and a bit a k-mer in words of the read's own (the row buffer is reused by the trial queries)
+//   kcor_rows_plan_kernel      a lane per read: the moves that need no answer (kcor_rows_settle); a read with a trial due takes a slot
+//                              from a counter (one atomicAdd) and writes its three sequences of 2K - 1 bases from the output batch
+//   kcor_rows_decide_kernel    a lane per trial over its 3 K answers: kcor_sweep's acceptance, one base written into the read's own
+//                              words, the state moved on; a read that ends gets its report word
 // A batch reaches every kernel as one KidxBatch by value (kindex.hpp), and the host side builds a table the same way whether it is
 // pg_kindex_build's or a rank's of a cut (kidx_rank_table, kidx_rank_insert, kidx_build_verdict).
 // Both forms of the query kernel wait for one random slot read per k-mer (32 B a slot in the 63-mer build, 48 B in the 127-mer one) of a table that
@@ -56,6 +64,7 @@
 #include "device_ctx.hpp"
 #include "env.hpp"
 #include "kcorrect.hpp"
+#include "kcorrect_rows.hpp"
 #include "kindex.hpp"
 #include "ktrim.hpp"
 
@@ -338,6 +347,53 @@ __global__ __launch_bounds__(256) void ktrim_pack_kernel(const uint64_t* __restr
     // ktrim_pack_word loads two source words whatever the shift: the second one of a read's last output word may be the next read's
     // first word or, for the batch's last read, the first of the nw + 1 readable tail words -- never past the batch
     packed_out[w] = ktrim_pack_word(rd, ktrim_start(sp), ktrim_len(sp), w - word_off_out[lo]);
+}
+
+// ---- the corrector on an index cut over ranks: rounds over merged rows (kcorrect_rows.hpp) ----
+__global__ __launch_bounds__(256) void kcor_rows_begin_kernel(KidxBatch b, int K, const uint64_t* __restrict__ rows, uint32_t min_cov,
+                                                              uint64_t* __restrict__ state, uint64_t* __restrict__ bits, uint64_t* __restrict__ report) {
+    const uint64_t r = kidx_seq_index<false>();
+    if (r >= b.n_seqs) return;
+    const KidxRow w = kidx_row(b, K, r);
+    const KcorRowsRead s = kcor_rows_begin(rows + w.base, w.nk, min_cov, bits + kcor_rows_bits_at(w.base, r));
+    kcor_rows_store(state + r * KCOR_ROWS_STATE_WORDS, s);
+    if (report && s.phase == KCOR_ROWS_DONE) report[r] = kcor_rows_report(s);
+}
+
+// (b.packed is the output buffer: the trial sequences are cut from the read as it stands)
+__global__ __launch_bounds__(256) void kcor_rows_plan_kernel(KidxBatch b, int K, uint32_t max_fixes, uint64_t* __restrict__ state,
+                                                             const uint64_t* __restrict__ bits, uint64_t cap, unsigned long long* __restrict__ claimed,
+                                                             uint64_t* __restrict__ trial_read, uint64_t* __restrict__ trial, uint64_t* __restrict__ report) {
+    const uint64_t r = kidx_seq_index<false>();
+    if (r >= b.n_seqs) return;
+    uint64_t* st = state + r * KCOR_ROWS_STATE_WORDS;
+    KcorRowsRead s = kcor_rows_load(st);
+    if (s.phase == KCOR_ROWS_DONE) return;
+    const KidxSeq q = kidx_seq(b, K, r);
+    const bool due = kcor_rows_settle(s, q.nk, max_fixes, bits + kcor_rows_bits_at(q.base, r));
+    if (due) {
+        const uint64_t slot = atomicAdd(claimed, 1ull);   // (which reads get the slots is not deterministic; the result is)
+        if (slot < cap) {
+            trial_read[slot] = r;
+            kcor_rows_trial_write(q.rd, q.nk, K, s, trial + slot * 3 * (uint64_t)kcor_rows_trial_words(K));
+        }
+    }
+    kcor_rows_store(st, s);
+    if (!due && report) report[r] = kcor_rows_report(s);
+}
+
+__global__ __launch_bounds__(256) void kcor_rows_decide_kernel(KidxBatch b, int K, KcorParams pr, uint64_t n_trials, const uint64_t* __restrict__ trial_read,
+                                                               const uint64_t* __restrict__ trial_rows, uint64_t* __restrict__ state,
+                                                               const uint64_t* __restrict__ bits, uint64_t* __restrict__ report) {
+    const uint64_t t = kidx_seq_index<false>();
+    if (t >= n_trials) return;
+    const uint64_t r = trial_read[t];
+    uint64_t* st = state + r * KCOR_ROWS_STATE_WORDS;
+    KcorRowsRead s = kcor_rows_load(st);
+    const KidxSeq q = kidx_seq(b, K, r);
+    const bool more = kcor_rows_decide(s, trial_rows + t * 3 * (uint64_t)K, const_cast<uint64_t*>(q.rd), q.nk, K, pr, bits + kcor_rows_bits_at(q.base, r));
+    kcor_rows_store(st, s);
+    if (!more && report) report[r] = kcor_rows_report(s);
 }
 
 namespace {
@@ -838,6 +894,87 @@ int ktrim_device_times(::pg_kindex* ix, double out[4]) {
     return PG_OK;
 }
 
+// ---- the corrector on an index cut over ranks ----
+namespace {
+
+void kcor_rows_free(::pg_kindex* ix) {
+    if (ix->d_cor) (void)arena_free(ix->d_cor);
+    if (ix->e_cor) (void)hipEventDestroy(ix->e_cor);
+    ix->d_cor = nullptr;
+    ix->e_cor = nullptr;
+    ix->cap_cor = 0;
+    ix->corrected = false;
+}
+
+// the rounds on the caller's stream (the lead's device is current); d_packed_out already holds the batch or is about to
+int kcor_rows_rounds(::pg_kindex* ix, const KidxBatch& b, const KcorParams& pr, uint64_t* d_packed_out, uint64_t* d_report, hipStream_t st,
+                     uint64_t* stats) {
+    const int K = ix->K;
+    const uint64_t n_seqs = b.n_seqs, cap = std::min<uint64_t>(kcor_round_trials(), n_seqs);
+    dim3 grid;
+    if (int rc = kidx_batch_blocks(n_seqs, false, &grid)) return rc;
+    // Scratch: the reads' state and bits, the round's trial reads, the claim counter, the trial batch with its readable tail, its rows.
+    // It grows to the largest batch met: the buffer is given back first, and arena_free waits for the device as hipFree does, so no
+    // earlier correction still uses it -- the only wait besides the one a round
+    const uint64_t w_state = n_seqs * KCOR_ROWS_STATE_WORDS, w_bits = kcor_rows_bit_words(b.n_kmers, n_seqs), w_trial = kcor_rows_batch_words(cap, K, ix->nw),
+                   w_rows = cap * 3 * (uint64_t)K;
+    if (int rc = kidx_reserve(&ix->d_cor, &ix->cap_cor, w_state + w_bits + cap + 1 + w_trial + w_rows)) return rc;
+    uint64_t *d_state = ix->d_cor, *d_bits = d_state + w_state, *d_trial_read = d_bits + w_bits, *d_claimed = d_trial_read + cap, *d_trial = d_claimed + 1,
+             *d_trial_rows = d_trial + w_trial;
+    if (!ix->e_cor) KIDX_HIP(hipEventCreate(&ix->e_cor));
+    // the copy first -- pad bits and the readable tail with it -- then every read is worked on in its own words of the output
+    if (d_packed_out != b.packed) KIDX_HIP(hipMemcpyAsync(d_packed_out, b.packed, b.n_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    if (ix->corrected) KIDX_HIP(hipStreamWaitEvent(st, ix->e_cor, 0));            // (another stream than last time's: the scratch is one)
+    KidxBatch o = b;
+    o.packed = d_packed_out;
+    const dim3 block(256);
+    // the read as given: every rank probes the k-mers it owns and the lead's row buffer receives the merged answers
+    if (int rc = kidx_query_ranks(ix, o, 0, nullptr, nullptr, st)) return rc;
+    hipLaunchKernelGGL(kcor_rows_begin_kernel, grid, block, 0, st, o, K, ix->ranks[0].d_rows, pr.min_cov, d_state, d_bits, d_report);
+    KIDX_HIP(hipGetLastError());
+    KIDX_HIP(hipEventRecord(ix->e_end, st));       // the next query's ranks zero the rows: they wait for this read of them too
+    for (;;) {
+        unsigned long long claimed = 0;
+        KIDX_HIP(hipMemsetAsync(d_claimed, 0, sizeof(uint64_t), st));
+        hipLaunchKernelGGL(kcor_rows_plan_kernel, grid, block, 0, st, o, K, pr.max_fixes, d_state, d_bits, cap, (unsigned long long*)d_claimed, d_trial_read,
+                           d_trial, d_report);
+        KIDX_HIP(hipGetLastError());
+        // the round's one wait on the host: how many trials it holds sizes the query and the decide
+        KIDX_HIP(hipMemcpyAsync(&claimed, d_claimed, sizeof claimed, hipMemcpyDeviceToHost, st));
+        KIDX_HIP(hipStreamSynchronize(st));
+        stats[3]++;
+        const uint64_t n_trials = std::min<uint64_t>(claimed, cap);
+        if (!n_trials) break;
+        stats[0]++;
+        stats[1] += n_trials;
+        stats[2] += n_trials * 3 * (uint64_t)K;
+        const KidxBatch trials{d_trial, nullptr, nullptr, n_trials * 3, (uint32_t)(2 * K - 1), kcor_rows_batch_words(n_trials, K, ix->nw), n_trials * 3 * (uint64_t)K};
+        if (int rc = kidx_query_ranks(ix, trials, 0, d_trial_rows, nullptr, st)) return rc;
+        dim3 trial_grid;
+        if (int rc = kidx_batch_blocks(n_trials, false, &trial_grid)) return rc;
+        hipLaunchKernelGGL(kcor_rows_decide_kernel, trial_grid, block, 0, st, o, K, pr, n_trials, d_trial_read, d_trial_rows, d_state, d_bits, d_report);
+        KIDX_HIP(hipGetLastError());
+    }
+    KIDX_HIP(hipEventRecord(ix->e_cor, st));
+    ix->corrected = true;
+    return PG_OK;
+}
+
+}  // namespace
+
+int kcor_device_correct_rows(::pg_kindex* ix, const KidxBatch& b, const KcorParams& pr, uint64_t* d_packed_out, uint64_t* d_report, void* stream,
+                             uint64_t* stats) {
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    if (!b.n_seqs) return PG_OK;
+    const int rc = kcor_rows_rounds(ix, b, pr, d_packed_out, d_report, (hipStream_t)stream, stats);
+    if (rc) {                                      // no stream is left reading the caller's batch, the scratch or writing its results
+        kidx_sync_ranks(ix);
+        (void)hipSetDevice(ix->device);
+        (void)hipStreamSynchronize((hipStream_t)stream);
+    }
+    return rc;
+}
+
 int kidx_device_query_times(::pg_kindex* ix, double out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
     if (!ix->queried) return PG_OK;
@@ -861,6 +998,10 @@ void kidx_device_free(::pg_kindex* ix) {
     if (ix->d_trim || ix->e_trim[0]) {             // (arena_free waits for the device: no trim still uses the scratch)
         (void)hipSetDevice(ix->device);
         ktrim_free(ix);
+    }
+    if (ix->d_cor || ix->e_cor) {                  // (the same for the corrector's rounds)
+        (void)hipSetDevice(ix->device);
+        kcor_rows_free(ix);
     }
     kidx_sync_ranks(ix);                           // every stream first: the lead's copies read the other ranks' rows
     for (KidxRank& r : ix->ranks) {

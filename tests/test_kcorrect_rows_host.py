@@ -1,0 +1,150 @@
+"""The corrector on an index cut over ranks, on the CPU: the host twin of pg_kindex_correct_rows (a device list of -1s: the rounds of
+csrc/kcorrect_rows.hpp with the kernels' own steps, over the rows of the twin's query) against the independent model
+(tests/kcorrect_model.py), the single-table twin (pg_kindex_correct) and itself at other round capacities.
+tests/test_gpu_kcorrect_rows.py runs the same through the kernels.  All comparisons are of integers and exact."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import kcorrect_cases as E
+import kcorrect_model as C
+import kcorrect_rows_cases as R
+from conftest import oracle_records
+from soapdenovo2_amd import api
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("flavour", E.FLAVOURS, ids=E.flavour_id)
+def test_host_twin_matches_model_over_3_ranks(flavour):
+    R.check_flavour(flavour[0], flavour[1], (-1, -1, -1))
+
+
+@pytest.mark.parametrize("flavour", R.RANK_FLAVOURS, ids=E.flavour_id)
+def test_1_2_and_8_ranks(flavour):
+    R.check_ranks(flavour[0], flavour[1], lambda n: (-1,) * n)
+
+
+@pytest.mark.parametrize("flavour", R.RANK_FLAVOURS, ids=E.flavour_id)
+def test_round_capacity_changes_nothing_but_the_rounds(flavour):
+    cor = R.RowsCorrector(flavour[0], flavour[1], (-1, -1, -1))
+    try:
+        R.check_capacities(cor, (1, 2, 5))
+    finally:
+        cor.close()
+
+
+def test_limit_takes_no_trial_and_both_sweeps_report():
+    K = 31
+    cor = R.RowsCorrector(K, False, (-1, -1, -1))
+    try:
+        by_name = {c.name: c for c in E.cases(K)}
+        reads = [c.read for c in E.cases(K) if len(c.read) == E.read_len(K)]
+        got, rep = cor.check(reads, "max_fixes = 0", **dict(E.PARAMS, max_fixes=0))
+        stats = cor.ix.correct_rows_stats()
+        assert stats["trials"] == 0 and stats["rounds"] == 0 and stats["host_waits"] == 1
+        assert ((rep & np.uint64(C.LIMIT)) != 0).sum() > 10 and not (rep & np.uint64(0xFF)).any()
+        # the right sweep runs into the limit and the left one, which has an error of its own to meet, reports it too; then a right
+        # sweep that stops at a rejected trial in front of a left sweep that fixes its error
+        truth = E.genome(K)[E.PLAIN:E.PLAIN + 200].copy()
+        limited = E._with_errors(truth, [2, 80, 100, 120, 140])
+        stopped = by_name["two-errors-1-apart"].read.copy()
+        stopped[2] ^= 1
+        for read, flags, fixes in ((limited, C.LIMIT, E.MAX_FIXES), (stopped, C.STOP_RIGHT, 1)):
+            _, want = E.model_correct(cor.model, read, E.PARAMS)
+            assert want & E.FLAGS == flags and want & 0xFF == fixes
+            cor.check([read], "both sweeps", **E.PARAMS)
+            cor.check([read, read], "both sweeps, uniform", uniform=True, **E.PARAMS)
+        fixed, _ = E.model_correct(cor.model, limited, E.PARAMS)
+        assert (np.flatnonzero(fixed != truth) == [2, 140]).all()
+    finally:
+        cor.close()
+
+
+def test_one_table_is_pg_kindex_correct():
+    K = 31
+    one = E.Corrector(K, False, -1)
+    try:
+        reads = [c.read for c in E.cases(K)]
+        words, off, base, _ = E.pack(reads, K, 2, False)
+        a, a_rep = one.ix.correct_ragged(words, off, base, len(reads), **E.PARAMS)
+        b, b_rep = one.ix.correct_rows_ragged(words, off, base, len(reads), **E.PARAMS)
+        assert (a == b).all() and (a_rep == b_rep).all() and not (a == words).all()
+        assert one.ix.correct_rows_stats() == dict(rounds=0, trials=0, trial_kmers=0, host_waits=0)
+    finally:
+        one.close()
+
+
+def test_argument_errors():
+    K = 31
+    cor = R.RowsCorrector(K, False, (-1, -1, -1))
+    words, off, base, _ = E.pack([c.read for c in E.cases(K)[:6]], K, 2, False)
+    out, rep = np.zeros_like(words), np.zeros(6, dtype=np.uint64)
+    L = api.lib()
+
+    def call(min_cov=3, max_fixes=3, min_run=5, n=6, packed_out=out.ctypes.data, report=rep.ctypes.data, n_words=len(words), ulen=0, n_kmers=int(base[-1])):
+        return L.pg_kindex_correct_rows(cor.ix.h, words.ctypes.data, n_words, off.ctypes.data, base.ctypes.data, n, ulen, n_kmers, min_cov, max_fixes,
+                                        min_run, packed_out, report, None)
+
+    einval = -1                                                 # PG_EINVAL (include/soapdenovo2_amd.h)
+    assert call(min_cov=0) == einval and b"min_cov" in L.pg_last_error()
+    assert call(min_run=0) == einval and call(max_fixes=256) == einval and call(packed_out=None) == einval
+    nk = 101 - K + 1
+    assert call(ulen=101, n_words=6 * 4 + 2, n_kmers=6 * nk) == einval and b"n_words" in L.pg_last_error()   # (the nw + 1 words of tail)
+    assert call(ulen=101, n_words=6 * 4 + 3, n_kmers=6 * nk - 1) == einval and b"n_kmers" in L.pg_last_error()
+    assert call(n_kmers=int(base[-1]) + 1) == einval and b"n_kmers" in L.pg_last_error()
+    assert call(n_words=2) == einval
+    assert not out.any() and not rep.any()
+    assert call(n=0) == 0 and not out.any()                     # no reads: PG_OK, nothing touched
+    assert call(max_fixes=255, report=None) == 0 and out.any() and not rep.any()
+    assert L.pg_kindex_correct_rows(None, words.ctypes.data, len(words), off.ctypes.data, base.ctypes.data, 6, 0, int(base[-1]), 3, 3, 5, out.ctypes.data,
+                                    None, None) == einval
+    for bad in (dict(min_cov=0), dict(min_run=0), dict(max_fixes=256)):
+        with pytest.raises(api.PgError, match=r"failed \(-1\)"):
+            cor.ix.correct_rows_ragged(words, off, base, 6, **dict(E.PARAMS, **bad))
+    cor.close()
+
+
+@pytest.fixture(scope="module")
+def simulated_records(tmp_path_factory):
+    return oracle_records(E.simulated()[0], E.SIM_K, 8, prefix=str(tmp_path_factory.mktemp("kcorrect_rows") / "o"))[0]
+
+
+def test_simulated_set(simulated_records):
+    """The simulated set (900 reads of 100 bases, K = 31, the oracle's records, min_cov = 3): the rows form over 3 ranks == pg_kindex_correct
+    on the single-table twin == the model, reads and reports; api.correct_reads on the cut twin returns the model's reads."""
+    reads = list(E.simulated()[0])
+    params = dict(min_cov=E.SIM_MIN_COV, max_fixes=api.CORRECT_MAX_FIXES, min_run=api.CORRECT_MIN_RUN)
+    one = E.Corrector(E.SIM_K, False, -1, records=simulated_records)
+    cut = R.RowsCorrector(E.SIM_K, False, (-1, -1, -1), records=simulated_records, model=one.model)
+    try:
+        fixed, report = E.simulated_model_output(one.model)
+        for uniform in (True, False):
+            a, a_rep = one.run(reads, uniform=uniform, **params)
+            b, b_rep = cut.check(reads, "simulated, uniform=%s" % uniform, uniform=uniform, **params)
+            assert (a == b).all() and (a_rep == b_rep).all() and (b_rep == report).all()
+        stats = cut.ix.correct_rows_stats()
+        assert stats["trials"] == R.trials_of(report) > 300
+        got, rep = api.correct_reads(reads, cut.ix, E.SIM_MIN_COV)
+        assert all((g == f).all() for g, f in zip(got, fixed)) and (rep == report).all()
+    finally:
+        one.close()
+        cut.close()
+
+
+# ---- the host twin under the sanitizers, in a program of its own ----
+def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
+    """tests/kcorrect_rows_asan.cpp: both flavours, 3 ranks, a ragged and a uniform batch on the heap with exactly nw + 1 words of tail,
+    packed_out at exactly n_words, a round capacity of 2, checked against the single-table twin -- compiled with the host twin's sources
+    and -fsanitize=address,undefined, and run.  Nothing loaded into Python is sanitised."""
+    exe = str(tmp_path / "kcorrect_rows_asan")
+    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
+           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kcorrect_rows_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
+           os.path.join(csrc, "kcorrect_rows_host.cpp"), "-o", exe]
+    built = subprocess.run(cmd, capture_output=True, text=True)
+    assert built.returncode == 0, built.stderr
+    ran = subprocess.run([exe], capture_output=True, text=True)
+    assert ran.returncode == 0 and "kcorrect rows host twin: ok" in ran.stdout, ran.stdout + ran.stderr
