@@ -487,6 +487,31 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       when packed_out is given.
  *   pg_kindex_trim_times         milliseconds of the last pg_kindex_trim on a device index, from its events, after waiting for its
  *                       end: out[0] the spans (a cut index: probes and merge included), [1] the scan, [2] the pack, [3] all of it.
+ *   pg_kindex_walk      unitigs walked from the two ends of every sequence of a batch over the arc counters of the cnt words
+ *                       (csrc/kwalk.hpp): the table is the de Bruijn graph of the read set, arc multiplicities included, and a walk
+ *                       extends an oriented k-mer to the right while the graph is unambiguous.  The batch is laid out as for
+ *                       pg_kindex_correct; n_words = its words, the nw + 1 readable ones behind the last sequence included.  Sequence
+ *                       r yields walk 2r, from its last k-mer as read, and walk 2r + 1, from the reverse complement of its first
+ *                       k-mer: the left extension of the sequence is the reverse complement of walk 2r + 1's text.  A sequence of
+ *                       exactly K bases is a seed k-mer.  Solid is pg_kindex_correct's, with min_cov 1..255.  An arc exists when its
+ *                       6-bit counter is >= min_arc (1..63).  For an oriented k-mer x whose canonical form c has cnt word w:
+ *                       x == c: out(b) = right counter b (word B, bits 6b+5:6b) and in(a) = left counter a (word A); x == rc(c):
+ *                       out(b) = left counter b ^ 2 and in(a) = right counter a ^ 2.  The start k-mer is looked up: the sequence has
+ *                       no k-mer: reason 1 (NO_KMER); the start is not solid: 2 (SEED_WEAK); both with length 0.  Then, from the
+ *                       current x: the bases b with out_x(b) >= min_arc -- none: 3 (DEAD_END), more than one: 4 (BRANCH_OUT);
+ *                       y = x without its first base, with b appended, and canon(y) is looked up -- not solid: 5 (WEAK_NEXT); the
+ *                       bases a with in_y(a) >= min_arc must be exactly the first base of x, else 6 (BRANCH_IN); canon(y) is the
+ *                       start's canonical k-mer: 7 (LOOP), the base is not appended; otherwise b is appended, y's coverage is added
+ *                       to the walk's sum, x = y, and a walk of max_ext bases stops with 8 (MAX_EXT).  max_ext is 1..2^20.
+ *                       out_ext[walk * pg_packed_words(max_ext) + q]: the appended bases as pg_pack_read lays them out, pad bits
+ *                       zero, every word of the row written (zero beyond the last used one).  out_report[2 walk]: length in bits
+ *                       31:0, reason in bits 39:32, all other bits 0; out_report[2 walk + 1]: the sum of coverage (bits 31:24) of
+ *                       the appended k-mers.  The caller provides 2 n_seqs rows and 4 n_seqs report words.  Either may be null.
+ *                       PG_EINVAL: a parameter out of range, both outputs null, n_words that does not hold the batch and its tail.
+ *                       PG_ESTATE on an index cut over ranks: the kernel chases one lookup after the other in one table.  n_seqs == 0:
+ *                       PG_OK, nothing touched.  Device memory of the index's device, asynchronous on `stream`, no host wait, no
+ *                       scratch in the index; host memory for a host-twin index.  Not done: a cut index, indels (a walk follows
+ *                       substitution-free arcs only), and choosing among branches (a walk stops at every one).
  *   pg_kindex_info      out[0] keys (the records the table was made for, deleted ones included), [1] slots, [2] bytes of the table, [3] device (-1 as a 64-bit value: the host twin).
  *                       An index cut over ranks: the totals over its ranks, and the lead's device.
  *
@@ -549,6 +574,9 @@ int pg_kindex_trim(pg_kindex *ix, const uint64_t *packed, uint64_t n_words, cons
                    uint64_t *packed_out, uint64_t *word_off_out, uint64_t *kmer_base_out, uint64_t *src_out, uint64_t *out_totals,
                    void *stream);
 int pg_kindex_trim_times(pg_kindex *ix, double out[4]);
+int pg_kindex_walk(pg_kindex *ix, const uint64_t *packed, uint64_t n_words, const uint64_t *word_off, const uint64_t *kmer_base,
+                   uint64_t n_seqs, uint32_t uniform_len, uint32_t min_cov, uint32_t min_arc, uint32_t max_ext, uint64_t *out_ext,
+                   uint64_t *out_report, void *stream);
 int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
 void pg_kindex_destroy(pg_kindex *ix);
 uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */

@@ -185,6 +185,8 @@ def lib() -> C.CDLL:
     L.pg_kindex_trim.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, u64p, u64p,
                                  u64p, u64p, u64p, u64p, C.c_void_p]
     L.pg_kindex_trim_times.argtypes = [C.c_void_p, u64p]
+    L.pg_kindex_walk.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u64p,
+                                 C.c_void_p]
     L.pg_kindex_info.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_destroy.argtypes = [C.c_void_p]
     L.pg_kindex_destroy.restype = None
@@ -220,6 +222,7 @@ EXPORTED_SYMBOLS = [
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
     "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times", "pg_kindex_correct_rows", "pg_kindex_correct_rows_stats",
+    "pg_kindex_walk",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
@@ -894,6 +897,25 @@ def span_fields(spans) -> dict:
     return {"start": (w & np.uint64(0xffffffff)).astype(np.int64), "len": (w >> np.uint64(32)).astype(np.int64)}
 
 
+# The walk (pg_kindex_walk).  WALK_REASONS[code] names a stop reason; WALK_MAX_EXT is the default of max_ext (32 words a row), WALK_EXT_BOUND
+# the most the entry takes.
+WALK_REASONS = {1: "no_kmer", 2: "seed_weak", 3: "dead_end", 4: "branch_out", 5: "weak_next", 6: "branch_in", 7: "loop", 8: "max_ext"}
+WALK_MAX_EXT = 1024
+WALK_EXT_BOUND = 1 << 20
+
+
+def walk_fields(report) -> dict:
+    """The walk's report words split up, one entry a walk (two walks a sequence: 2r from its last k-mer, 2r + 1 from the reverse complement
+    of its first): `len` (bases appended), `reason` (a list of WALK_REASONS names), `code` (the reasons as numbers) and `coverage_sum` (of
+    the appended k-mers).  Takes a numpy array or a torch tensor of 2 words a walk; returns numpy arrays."""
+    if not isinstance(report, np.ndarray):
+        report = report.cpu().numpy()
+    w = np.ascontiguousarray(report).view(np.uint64).reshape(-1, 2)
+    code = ((w[:, 0] >> np.uint64(32)) & np.uint64(0xff)).astype(np.int64)
+    return {"len": (w[:, 0] & np.uint64(0xffffffff)).astype(np.int64), "code": code, "reason": [WALK_REASONS.get(int(c), "?") for c in code],
+            "coverage_sum": w[:, 1].astype(np.int64)}
+
+
 def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
     """pg_host_kindex_bytes: the table an index of n_records k-mers cuts (no GPU)."""
     return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
@@ -1140,6 +1162,32 @@ class KmerIndex:
         _check(lib().pg_kindex_trim_times(self.h, out.ctypes.data), "pg_kindex_trim_times")
         return {"span": float(out[0]), "scan": float(out[1]), "pack": float(out[2]), "total": float(out[3])}
 
+    def _walk(self, packed, word_off, kmer_base, n_seqs, uniform_len, min_cov, min_arc, max_ext):
+        n_words = int(packed.size if self.device < 0 else packed.numel())
+        row = packed_words(max_ext) if 0 < max_ext <= WALK_EXT_BOUND else 1     # (the entry refuses the rest; nothing is written then)
+        # (one element at least: an empty array has no address)
+        if self.device < 0:
+            new = lambda n: np.zeros(max(n, 1), dtype=np.uint64)
+        else:
+            new = lambda n: self.torch.zeros(max(n, 1), dtype=self.torch.int64, device=f"cuda:{self.device}")
+        ext, report = new(2 * n_seqs * row), new(4 * n_seqs)
+        _check(lib().pg_kindex_walk(self.h, self._ptr(packed), n_words, self._ptr(word_off), self._ptr(kmer_base), n_seqs, uniform_len, min_cov,
+                                    min_arc, max_ext, self._ptr(ext), self._ptr(report), self._stream()), "pg_kindex_walk")
+        return ext[:2 * n_seqs * row].reshape(2 * n_seqs, row), report[:4 * n_seqs]
+
+    def walk_uniform(self, d_packed, n_seqs: int, seq_len: int, min_cov: int, min_arc: int = 1, max_ext: int = WALK_MAX_EXT):
+        """Unitigs walked from both ends of every sequence of a batch of seq_len bases (pack_reads_uniform; the whole of d_packed is the
+        batch, its readable tail included) over the arc counters of the index (pg_kindex_walk).  Sequence r gives walk 2r, to the right
+        of its last k-mer, and walk 2r + 1, to the right of the reverse complement of its first k-mer; a walk goes on while exactly one
+        arc with a counter >= min_arc leaves the current k-mer, its successor is solid (coverage >= min_cov) and has that one arc
+        coming in, for at most max_ext bases.  Returns (ext, report): ext[v] = walk v's bases in packed_words(max_ext) words
+        (unpack_seq), report = two words a walk (walk_fields).  An index cut over ranks is refused."""
+        return self._walk(d_packed, None, None, n_seqs, seq_len, min_cov, min_arc, max_ext)
+
+    def walk_ragged(self, d_packed, d_word_off, d_kmer_base, n_seqs: int, min_cov: int, min_arc: int = 1, max_ext: int = WALK_MAX_EXT):
+        """walk_uniform for sequences of any lengths (pack_seqs_ragged); one shorter than K gives two empty walks, reason no_kmer."""
+        return self._walk(d_packed, d_word_off, d_kmer_base, n_seqs, 0, min_cov, min_arc, max_ext)
+
     def info(self) -> dict:
         out = np.zeros(4, dtype=np.uint64)
         _check(lib().pg_kindex_info(self.h, out.ctypes.data), "pg_kindex_info")
@@ -1244,3 +1292,22 @@ def trim_reads(reads: Sequence[np.ndarray], index: KmerIndex, min_cov: int, min_
     lens = span_fields(spans)["len"]
     kept = [unpack_seq(packed_out[int(word_off_out[i]):], int(lens[int(src[i])])) for i in range(n_kept)]
     return kept, src[:n_kept].astype(np.int64), spans
+
+
+def extend_seqs(seqs: Sequence[np.ndarray], index: KmerIndex, min_cov: int, min_arc: int = 1, max_ext: int = WALK_MAX_EXT):
+    """Sequences (base-code arrays, any lengths; one of K bases is a seed k-mer) extended at both ends while the index's graph is
+    unambiguous: (a list of base-code arrays, sequence i's = rc(walk 2i + 1) + seqs[i] + walk 2i, and the fields of all 2 n walks --
+    see walk_fields)."""
+    words, word_off, kmer_base = pack_seqs_ragged(seqs, index.K)
+    if index.device < 0:
+        ext, report = index.walk_ragged(words, word_off, kmer_base, len(seqs), min_cov, min_arc, max_ext)
+    else:
+        t, dev = index.torch, f"cuda:{index.device}"
+        up = lambda a: t.from_numpy(a.view(np.int64)).to(dev)
+        ext, report = [o.cpu().numpy().view(np.uint64) for o in index.walk_ragged(up(words), up(word_off), up(kmer_base), len(seqs), min_cov, min_arc, max_ext)]
+    f = walk_fields(report)
+    out = []
+    for i, s in enumerate(seqs):
+        right, left = unpack_seq(ext[2 * i], int(f["len"][2 * i])), unpack_seq(ext[2 * i + 1], int(f["len"][2 * i + 1]))
+        out.append(np.concatenate([(left[::-1] ^ 2).astype(np.uint8), np.asarray(s, dtype=np.uint8), right]))
+    return out, f

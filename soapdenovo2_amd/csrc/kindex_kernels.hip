@@ -20,6 +20,10 @@
 //   kcor_kernel             a lane per read of a batch that already lies in the output buffer: kcor_read (kcorrect.hpp) on the lane's own
 //                           words, in global memory -- the first pass over the read as given is the query kernel's lane walk, and a read
 //                           without a weak k-mer ends there; the lanes of a wave diverge in the trials.
+//   kwalk_kernel            a lane per walk, two walks a sequence (kwalk.hpp; pg_kindex_walk): kwalk_one with kidx_find as its
+//                           lookup.  One dependent slot read per appended base, latency-chained within the lane; the word of 32 bases
+//                           being filled stays in a register and is stored when full.  No LDS, no barrier; lanes whose walks ended wait
+//                           for the longest walk of their wave.
 // The index cut over ranks (kindex.hpp; pg_kindex_build_sharded, pg_kindex_query_words):
 //   kidx_count_owners_kernel   a lane per record of a device part, on the device where the part lies: the owners of all n ranks at once
 //                              into an LDS histogram (n <= 256 bins: 1 KB, zeroed and flushed per workgroup), one global atomicAdd per
@@ -67,6 +71,7 @@
 #include "kcorrect_rows.hpp"
 #include "kindex.hpp"
 #include "ktrim.hpp"
+#include "kwalk.hpp"
 
 namespace pg {
 
@@ -180,6 +185,17 @@ __global__ __launch_bounds__(256) void kcor_kernel(KidxBatch b, int K, const uin
     const KidxSeq q = kidx_seq(b, K, r);           // (b.packed is the output buffer, which already holds the batch)
     const uint64_t rep = kcor_read<NW>(const_cast<uint64_t*>(q.rd), q.nk, K, tab, mask, pr);
     if (report) report[r] = rep;
+}
+
+// walk v = 2 r + s of sequence r: s = 0 from its last k-mer, s = 1 from the reverse complement of its first (the two lie in neighbouring lanes)
+template <int NW>
+__global__ __launch_bounds__(256) void kwalk_kernel(KidxBatch b, int K, const uint64_t* __restrict__ tab, uint64_t mask, KwalkParams pr,
+                                                    uint64_t* __restrict__ ext, uint64_t* __restrict__ report) {
+    const uint64_t v = kidx_seq_index<false>();
+    if (v >= 2 * b.n_seqs) return;
+    const KidxSeq q = kidx_seq(b, K, v >> 1);
+    kwalk_one<NW>(q.rd, q.nk, K, (v & 1) != 0, pr, [tab, mask](const Kmer<NW>& ck) { return kidx_find<NW>(tab, mask, ck); },
+                  ext ? ext + v * kwalk_row_words(pr.max_ext) : nullptr, report ? report + 2 * v : nullptr);
 }
 
 // ---- the index cut over ranks ----
@@ -508,6 +524,18 @@ int kcor_device_correct(::pg_kindex* ix, const KidxBatch& b, const KcorParams& p
     o.packed = d_packed_out;
     return kidx_launch(ix, [&](auto nw) {
         hipLaunchKernelGGL((kcor_kernel<decltype(nw)::value>), grid, dim3(256), 0, st, o, ix->K, t.d_tab, t.slots - 1, pr, d_report);
+    });
+}
+
+int kwalk_device_walk(::pg_kindex* ix, const KidxBatch& b, const KwalkParams& pr, uint64_t* d_ext, uint64_t* d_report, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const KidxRank& t = ix->ranks[0];
+    dim3 grid;
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    if (!b.n_seqs) return PG_OK;
+    if (int rc = kidx_batch_blocks(2 * b.n_seqs, false, &grid)) return rc;   // a lane a walk
+    return kidx_launch(ix, [&](auto nw) {
+        hipLaunchKernelGGL((kwalk_kernel<decltype(nw)::value>), grid, dim3(256), 0, st, b, ix->K, t.d_tab, t.slots - 1, pr, d_ext, d_report);
     });
 }
 
