@@ -117,6 +117,59 @@ extern "C" int64_t emu_skm_count(const uint64_t* packed, int64_t n_reads, int le
                   : run<2>(packed, n_reads, len, K, log2_parts, out, cap, n_records, max_part_distinct);
 }
 
+// ---- what each partition holds (tests/k2_partition_cases.py): the records the cutter sends to it, how many of them differ in what
+// the counting kernel's search for copies compares (the payload and the header's low 18 bits: n and the flank bits), and its distinct
+// canonical k-mers.  word_off / lens = null: n_reads reads of `len` bases back to back; otherwise a ragged batch (word_off[r] = first
+// word of read r, lens[r] its bases).  The three arrays have 1 << log2_parts entries.  Returns the records of the batch, < 0 on an error.
+#include <algorithm>
+template <int NW>
+static int64_t part_stats(const uint64_t* packed, const uint64_t* word_off, const int32_t* lens, int64_t n_reads, int len, int K, int log2_parts,
+                          int64_t* n_rec, int64_t* n_distinct_rec, int64_t* n_distinct_kmers) {
+    constexpr int PW = NW == 2 ? 5 : 7, RW = PW + 1;
+    const SkmGeom g = skm_geometry(K, log2_parts, NW);
+    if (g.rw != RW) return -1;
+    const int wpr = (len + 31) / 32;
+    typedef std::array<uint64_t, RW> Rec;
+    std::vector<std::vector<Rec>> parts((size_t)1 << log2_parts);
+    int64_t nrec = 0, kb = 0;
+    for (int64_t r = 0; r < n_reads; r++) {
+        const int rl = lens ? lens[r] : len;
+        if (rl < K + 1) return -2;
+        const uint64_t* rd = packed + (word_off ? word_off[r] : (uint64_t)r * wpr);
+        skm_split_read(rd, rl, g, [&](int j0, int n, uint32_t pid) {
+            Rec rec;
+            skm_make_record<PW>(rd, rl, j0, n, (uint64_t)kb, g, rec.data());
+            parts[pid].push_back(rec);
+            nrec++;
+        });
+        kb += rl - K + 1;
+    }
+    const Kmer<NW> filter = kmer_filter<NW>(K);
+    for (size_t p = 0; p < parts.size(); p++) {
+        std::vector<Rec>& v = parts[p];
+        n_rec[p] = (int64_t)v.size();
+        std::vector<std::array<uint64_t, NW>> keys;
+        for (const Rec& rec : v)
+            skm_expand_record<NW>(rec.data(), K, filter, [&](const Kmer<NW>& key, int, int, uint64_t) {
+                std::array<uint64_t, NW> kk;
+                for (int q = 0; q < NW; q++) kk[q] = key.w[q];
+                keys.push_back(kk);
+            });
+        std::sort(keys.begin(), keys.end());
+        n_distinct_kmers[p] = (int64_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
+        for (Rec& rec : v) rec[0] &= ((uint64_t)1 << SKM_ORD_SHIFT) - 1;
+        std::sort(v.begin(), v.end());
+        n_distinct_rec[p] = (int64_t)(std::unique(v.begin(), v.end()) - v.begin());
+    }
+    return nrec;
+}
+
+extern "C" int64_t emu_skm_part_stats(const uint64_t* packed, const uint64_t* word_off, const int32_t* lens, int64_t n_reads, int len, int K, int mer127,
+                                      int log2_parts, int64_t* n_rec, int64_t* n_distinct_rec, int64_t* n_distinct_kmers) {
+    return mer127 ? part_stats<4>(packed, word_off, lens, n_reads, len, K, log2_parts, n_rec, n_distinct_rec, n_distinct_kmers)
+                  : part_stats<2>(packed, word_off, lens, n_reads, len, K, log2_parts, n_rec, n_distinct_rec, n_distinct_kmers);
+}
+
 // ---- the tiled cutter (csrc/skm_tile.hpp) run serially: phases A, B, D, E over tiles of R reads, compared run for run
 // and word for word with skm_split_read + skm_make_record.  Returns 0 or a negative code.
 #include "../soapdenovo2_amd/csrc/skm_tile.hpp"

@@ -26,7 +26,7 @@ def _nmax(K):
 
 def _tandem(rng, period, length, offset=0):
     unit = rng.integers(0, 4, size=period).astype(np.uint8)
-    while len(set(unit.tolist())) < 3:                             # (no homopolymer units: the oracle's and the cutter's rules are the same, but keep it a real repeat)
+    while len(set(unit.tolist())) < 3:                             # (a real repeat here; homopolymer and two-base units, in windows of 512 copies: tests/k2_partition_cases.py)
         unit = rng.integers(0, 4, size=period).astype(np.uint8)
     return np.tile(unit, (length + offset) // period + 2)[offset:offset + length].copy()
 
