@@ -537,6 +537,37 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       pg_kindex_query.  pg_kindex_query itself returns PG_EINVAL on an index cut over ranks, and pg_kindex_correct
  *                       PG_ESTATE: its kernel chases one lookup after the other in one table.  The corrector's rule is answered from
  *                       merged rows by pg_kindex_correct_rows.
+ *   pg_kindex_unitigs   the whole graph of the index compacted into unitigs (csrc/kunitig.hpp): every maximal unambiguous path exactly
+ *                       once, as a ragged batch that pg_kindex_query, pg_kindex_walk and pg_count_reads take where it lies.  Solid, the
+ *                       arc sets, min_cov (1..255) and min_arc (1..63) are pg_kindex_walk's.  The right side of a solid oriented k-mer x
+ *                       is open when exactly one arc b leaves it, y = next(x, b) is solid, the one arc into y comes from x's first base
+ *                       and canon(y) != canon(x); otherwise it is an end, with reason 3 dead end, 4 branch out, 5 weak next, 6 branch
+ *                       in (pg_kindex_walk's codes) or 9 hairpin (x -> rc(x), or the self-loop x -> x).  The left side of x is the
+ *                       right side of rc(x).  A linear unitig is a maximal chain x0 -> .. -> x(n-1) through open sides between two
+ *                       ends; its text is x0 and the appended bases, n + K - 1 of them; of its two orientations the one whose first
+ *                       k-mer is not greater (most significant word first) is emitted.  A cyclic unitig is a ring of k-mers without an
+ *                       end side, emitted from its least canonical k-mer as it is, walking right: n + K - 1 bases, both reasons 10
+ *                       cycle.  A walk stops after max_kmers (1 .. 2^26) k-mers: a longer chain comes out from both ends, each with
+ *                       reason 11 cut on the cut side, and a longer ring not at all.  When nothing was cut (out_totals[6] == 0 and
+ *                       out_totals[3] == out_totals[4]) every solid k-mer lies in exactly one unitig, in one orientation.  The order
+ *                       of the unitigs is unspecified and differs between runs on a device.
+ *                       out_totals (8 words, always written): [0] unitigs, [1] packed words needed -- rows word-aligned, the nw + 1
+ *                       readable tail words included --, [2] bases, [3] k-mers covered (the sum of the unitigs' k-mers =
+ *                       kmer_base_out[unitigs]), [4] solid k-mers of the index, [5] cyclic unitigs, [6] cut unitigs, [7] overflow.
+ *                       packed_out null: count mode, only the totals are written.  Else unitig u starts at word word_off_out[u],
+ *                       pg_pack_read's layout, pad bits zero, nw + 1 zero words behind the last one; word_off_out[0 .. unitigs] and
+ *                       kmer_base_out[0 .. unitigs] are the exclusive prefix sums of the rows' words and of the k-mers;
+ *                       out_report[2u] = bases | left reason << 32 | right reason << 40, out_report[2u + 1] = the sum of coverage
+ *                       of the unitig's k-mers.  word_off_out, kmer_base_out and out_report may each be null.  The caller provides
+ *                       packed_out: cap_words words, word_off_out and kmer_base_out: cap_unitigs + 1, out_report: 2 cap_unitigs.  If
+ *                       the unitigs exceed cap_unitigs or the words cap_words, nothing but the totals is written and out_totals[7]
+ *                       is 1: the device decides, the host does not wait.  Instead of a count call the caller may use the bound
+ *                       `keys` unitigs and keys * pg_packed_words(K) + nw + 1 words (keys: pg_kindex_info), which holds when
+ *                       max_kmers >= keys, so that nothing can be cut; twice that holds always.
+ *                       PG_EINVAL: a threshold or max_kmers out of range, out_totals null; PG_ESTATE: an index cut over ranks (a
+ *                       walk chases its lookups in one table); nothing is written then.  Device memory of the index's device,
+ *                       asynchronous on `stream`; the index keeps scratch of 3 words a stored k-mer and a bit a slot, which grows
+ *                       to the size needed, and only that growth waits.  Host memory for a host-twin index.
  *   pg_kindex_correct_rows       pg_kindex_correct on any index, by rounds over merged rows (csrc/kcorrect_rows.hpp).  The batch, its
  *                       tail, n_words and n_kmers are pg_kindex_query_words' and pg_kindex_trim's; packed_out, out_report, in-place
  *                       use, the report word, the rule and the argument errors are pg_kindex_correct's, and so is the result, bit for
@@ -577,6 +608,9 @@ int pg_kindex_trim_times(pg_kindex *ix, double out[4]);
 int pg_kindex_walk(pg_kindex *ix, const uint64_t *packed, uint64_t n_words, const uint64_t *word_off, const uint64_t *kmer_base,
                    uint64_t n_seqs, uint32_t uniform_len, uint32_t min_cov, uint32_t min_arc, uint32_t max_ext, uint64_t *out_ext,
                    uint64_t *out_report, void *stream);
+int pg_kindex_unitigs(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_kmers, uint64_t cap_unitigs, uint64_t cap_words,
+                      uint64_t *packed_out, uint64_t *word_off_out, uint64_t *kmer_base_out, uint64_t *out_report, uint64_t *out_totals,
+                      void *stream);
 int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
 void pg_kindex_destroy(pg_kindex *ix);
 uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */

@@ -9,6 +9,7 @@ Mirrors the reference's entry points `int call_pregraph(int argc, char **argv)` 
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import functools
 import os
@@ -187,6 +188,7 @@ def lib() -> C.CDLL:
     L.pg_kindex_trim_times.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_walk.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u64p,
                                  C.c_void_p]
+    L.pg_kindex_unitigs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p, u64p, C.c_void_p]
     L.pg_kindex_info.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_destroy.argtypes = [C.c_void_p]
     L.pg_kindex_destroy.restype = None
@@ -222,7 +224,7 @@ EXPORTED_SYMBOLS = [
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
     "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times", "pg_kindex_correct_rows", "pg_kindex_correct_rows_stats",
-    "pg_kindex_walk",
+    "pg_kindex_walk", "pg_kindex_unitigs",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
@@ -916,6 +918,28 @@ def walk_fields(report) -> dict:
             "coverage_sum": w[:, 1].astype(np.int64)}
 
 
+# The unitigs (pg_kindex_unitigs).  UNITIG_REASONS[code] names the reason of a unitig's side: the walk's end reasons, and hairpin, cycle, cut.
+UNITIG_REASONS = {3: "dead_end", 4: "branch_out", 5: "weak_next", 6: "branch_in", 9: "hairpin", 10: "cycle", 11: "cut"}
+UNITIG_MAX_KMERS = 1 << 24
+UNITIG_KMERS_BOUND = 1 << 26
+UNITIG_TOTALS_FIELDS = ["unitigs", "words", "bases", "covered", "solid", "cyclic", "cut", "overflow"]
+Unitigs = collections.namedtuple("Unitigs", "packed word_off kmer_base report totals")
+
+
+def unitig_fields(report) -> dict:
+    """The unitigs' report words split up, one entry a unitig: `len` (bases), `left` and `right` (lists of UNITIG_REASONS names),
+    `left_code` and `right_code` (the reasons as numbers) and `coverage_sum` (of the unitig's k-mers).  Takes a numpy array or a torch
+    tensor of 2 words a unitig; returns numpy arrays."""
+    if not isinstance(report, np.ndarray):
+        report = report.cpu().numpy()
+    w = np.ascontiguousarray(report).view(np.uint64).reshape(-1, 2)
+    left = ((w[:, 0] >> np.uint64(32)) & np.uint64(0xff)).astype(np.int64)
+    right = ((w[:, 0] >> np.uint64(40)) & np.uint64(0xff)).astype(np.int64)
+    return {"len": (w[:, 0] & np.uint64(0xffffffff)).astype(np.int64), "left_code": left, "right_code": right,
+            "left": [UNITIG_REASONS.get(int(c), "?") for c in left], "right": [UNITIG_REASONS.get(int(c), "?") for c in right],
+            "coverage_sum": w[:, 1].astype(np.int64)}
+
+
 def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
     """pg_host_kindex_bytes: the table an index of n_records k-mers cuts (no GPU)."""
     return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
@@ -1188,6 +1212,32 @@ class KmerIndex:
         """walk_uniform for sequences of any lengths (pack_seqs_ragged); one shorter than K gives two empty walks, reason no_kmer."""
         return self._walk(d_packed, d_word_off, d_kmer_base, n_seqs, 0, min_cov, min_arc, max_ext)
 
+    def unitigs(self, min_cov: int, min_arc: int = 1, max_kmers: int = UNITIG_MAX_KMERS) -> "Unitigs":
+        """The whole graph of the index compacted into unitigs (pg_kindex_unitigs): every maximal unambiguous path -- exactly one arc
+        with a counter >= min_arc out, a solid successor (coverage >= min_cov) with exactly that arc in -- once, in the orientation
+        whose first k-mer is not greater, rings from their least k-mer; a walk stops after max_kmers k-mers (reason cut).  Returns
+        Unitigs(packed, word_off, kmer_base, report, totals): a ragged batch of totals[0] sequences that query_ragged, walk_ragged and
+        KmerCounter.count_ragged take as it lies (word_off and kmer_base have one entry more than there are unitigs, packed the
+        readable tail), report = two words a unitig (unitig_fields) and totals = UNITIG_TOTALS_FIELDS as a numpy array.  Two calls:
+        a count call, whose totals are read -- the one wait for the GPU here -- to allocate exactly, and the full call.  The order of
+        the unitigs is unspecified.  An index cut over ranks is refused."""
+        if self.device < 0:
+            new = lambda n: np.zeros(max(n, 1), dtype=np.uint64)
+        else:
+            new = lambda n: self.torch.zeros(max(n, 1), dtype=self.torch.int64, device=f"cuda:{self.device}")
+        totals = new(8)
+        _check(lib().pg_kindex_unitigs(self.h, min_cov, min_arc, max_kmers, 0, 0, None, None, None, None, self._ptr(totals), self._stream()),
+               "pg_kindex_unitigs")
+        t = totals if self.device < 0 else totals.cpu().numpy().view(np.uint64)
+        n, words = int(t[0]), int(t[1])
+        packed, word_off, kmer_base, report = new(words), new(n + 1), new(n + 1), new(2 * n)
+        _check(lib().pg_kindex_unitigs(self.h, min_cov, min_arc, max_kmers, n, words, self._ptr(packed), self._ptr(word_off), self._ptr(kmer_base),
+                                       self._ptr(report), self._ptr(totals), self._stream()), "pg_kindex_unitigs")
+        t = totals.copy() if self.device < 0 else totals.cpu().numpy().view(np.uint64)
+        if int(t[7]):
+            raise PgError("KmerIndex.unitigs: the full call needs more than the count call said")
+        return Unitigs(packed[:words], word_off[:n + 1], kmer_base[:n + 1], report[:2 * n], t)
+
     def info(self) -> dict:
         out = np.zeros(4, dtype=np.uint64)
         _check(lib().pg_kindex_info(self.h, out.ctypes.data), "pg_kindex_info")
@@ -1311,3 +1361,14 @@ def extend_seqs(seqs: Sequence[np.ndarray], index: KmerIndex, min_cov: int, min_
         right, left = unpack_seq(ext[2 * i], int(f["len"][2 * i])), unpack_seq(ext[2 * i + 1], int(f["len"][2 * i + 1]))
         out.append(np.concatenate([(left[::-1] ^ 2).astype(np.uint8), np.asarray(s, dtype=np.uint8), right]))
     return out, f
+
+
+def unitig_seqs(index: KmerIndex, min_cov: int, min_arc: int = 1, max_kmers: int = UNITIG_MAX_KMERS):
+    """The unitigs of the index's graph as base codes, for tests and small uses: (a list of base-code arrays, the fields of all of them
+    -- see unitig_fields --, the totals as a dict of UNITIG_TOTALS_FIELDS).  The order of the unitigs is unspecified."""
+    u = index.unitigs(min_cov, min_arc, max_kmers)
+    down = (lambda a: a) if index.device < 0 else (lambda a: a.cpu().numpy().view(np.uint64))
+    packed, word_off, report = down(u.packed), down(u.word_off), down(u.report)
+    f = unitig_fields(report)
+    seqs = [unpack_seq(packed[int(word_off[i]):], int(f["len"][i])) for i in range(int(u.totals[0]))]
+    return seqs, f, {k: int(v) for k, v in zip(UNITIG_TOTALS_FIELDS, u.totals)}

@@ -217,6 +217,12 @@ struct pg_kindex {
     hipEvent_t e_cor = nullptr;
     bool corrected = false;        // e_cor has been recorded
     uint64_t cor_stats[4] = {0, 0, 0, 0};   // the last pg_kindex_correct_rows: rounds, trials, k-mers asked in trials, host waits
+    // pg_kindex_unitigs' scratch on `device` (kunitig.hpp): the counters, the start list, the lengths, the scan's block sums and a covered
+    // bit a slot.  It grows to the size needed; the event is the last compaction's end
+    uint64_t* d_uni = nullptr;
+    uint64_t cap_uni = 0;
+    hipEvent_t e_uni = nullptr;
+    bool unitigged = false;        // e_uni has been recorded
 };
 
 namespace pg {

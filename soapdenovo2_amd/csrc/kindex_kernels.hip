@@ -45,6 +45,17 @@
 //   ktrim_pack_kernel          a lane per output word, the tail's nw + 1 zero words included: the kept read by binary search in
 //                              word_off_out, the word by ktrim_pack_word.  The launch covers the batch's n_words, which the result never
 //                              passes; how many of those lanes have a word is read from the totals on the device
+// The unitigs (kunitig.hpp; pg_kindex_unitigs): the whole graph compacted, six launches on the caller's stream
+//   kunitig_ends_kernel        a lane per table slot: both sides of a published solid key tested (kunitig_ends, two lookups at most), every
+//                              end side appended to the start list through an atomic counter; the solid k-mers counted a wave at a time
+//   kunitig_measure_kernel     a lane per start: kunitig_chain to the far end with a covered bit a k-mer on the way (atomicOr on 32-bit
+//                              words), the length, or 0 for the copy the orientation rule does not emit
+//   kunitig_rings_kernel       a lane per slot, solid and not covered: the cyclic form of kunitig_chain, which ends at the first smaller
+//                              key; a ring's least member appends its start behind the chains' -- one scan and one write serve both
+//   the scan                   the trim's ktrim_block_scan over (kept, words, k-mers) of the starts: kunitig_block_sums_kernel and
+//                              kunitig_scan_sums_kernel (one workgroup: the totals, the overflow decision the write kernel obeys, the
+//                              last offsets and the tail's zero words)
+//   kunitig_write_kernel       a lane per start: the scan inside the workgroup again, and a kept start walks once more into its row
 // The corrector on an index cut over ranks (kcorrect_rows.hpp; pg_kindex_correct_rows): rounds of plan, query, decide on the
 // caller's stream, every query kidx_query_ranks, and the host reads the round's trial count back once a round
 //   kcor_rows_begin_kernel     a lane per read over its row of the read as given: weak count, anchor, first weak k-mer behind it, the
@@ -71,6 +82,7 @@
 #include "kcorrect_rows.hpp"
 #include "kindex.hpp"
 #include "ktrim.hpp"
+#include "kunitig.hpp"
 #include "kwalk.hpp"
 
 namespace pg {
@@ -363,6 +375,175 @@ __global__ __launch_bounds__(256) void ktrim_pack_kernel(const uint64_t* __restr
     // ktrim_pack_word loads two source words whatever the shift: the second one of a read's last output word may be the next read's
     // first word or, for the batch's last read, the first of the nw + 1 readable tail words -- never past the batch
     packed_out[w] = ktrim_pack_word(rd, ktrim_start(sp), ktrim_len(sp), w - word_off_out[lo]);
+}
+
+// ---- the unitigs: ends, measure, rings, the scan of the kept starts' counts, write (kunitig.hpp) ----
+// The scratch of one compaction.  ctr: KUNITIG_C_*; starts / lens: `cap` entries, the chains' starts first and the rings' behind them;
+// sums: the scan's, KTRIM_COUNTS a block of 256 starts; bits: a covered bit a slot
+enum : int { KUNITIG_C_STARTS = 0, KUNITIG_C_CYCLIC = 1, KUNITIG_C_SOLID = 2, KUNITIG_C_CUT = 3, KUNITIG_C_GO = 4, KUNITIG_CTRS = 8 };
+struct KunitigScratch {
+    unsigned long long* ctr;
+    uint64_t* starts;
+    uint32_t* lens;
+    uint64_t* sums;
+    uint32_t* bits;
+    uint64_t cap;
+};
+
+__device__ __forceinline__ uint64_t kunitig_n_starts(const KunitigScratch& s) {
+    const uint64_t n = s.ctr[KUNITIG_C_STARTS];
+    return n < s.cap ? n : s.cap;
+}
+__device__ __forceinline__ bool kunitig_covered(const uint32_t* bits, uint64_t slot) { return (bits[slot >> 5] >> (slot & 31) & 1u) != 0; }
+// a start takes the next entry of the list (the order is the atomics': it differs from run to run, the set does not)
+__device__ __forceinline__ void kunitig_append(const KunitigScratch& s, uint64_t start, uint32_t len) {
+    const uint64_t i = atomicAdd(s.ctr + KUNITIG_C_STARTS, 1ull);
+    if (i >= s.cap) return;                        // (2 * keys entries hold every start: the bound of kunitig_device_unitigs)
+    s.starts[i] = start;
+    s.lens[i] = len;
+}
+template <int NW>
+__device__ __forceinline__ KunitigNode<NW> kunitig_start_node(const uint64_t* tab, uint64_t start, int K) {
+    const uint64_t slot = kunitig_start_slot(start);
+    const uint64_t* sl = tab + slot * map_slot_words<NW>();
+    return kunitig_node<NW>(kunitig_slot_key<NW>(sl), sl[NW], slot, kunitig_start_fwd(start), K);
+}
+
+// a lane per table slot: a published solid key has both sides tested, two lookups at most, and every end side becomes a start
+template <int NW>
+__global__ __launch_bounds__(256) void kunitig_ends_kernel(const uint64_t* __restrict__ tab, uint64_t slots, int K, KunitigParams pr, KunitigScratch s) {
+    constexpr int SW = map_slot_words<NW>();
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, mask = slots - 1;
+    const uint64_t* sl = tab + e * SW;
+    const uint64_t w = e < slots && sl[NW + 1] != KIDX_EMPTY ? sl[NW] : 0;
+    const bool solid = kcor_solid_word(w, pr.min_cov);
+    const uint64_t wave_solid = __ballot(solid);   // (every lane of the wave is here)
+    if ((threadIdx.x & 63) == 0 && wave_solid) atomicAdd(s.ctr + KUNITIG_C_SOLID, (unsigned long long)__popcll(wave_solid));
+    if (!solid) return;
+    uint32_t reasons[2];
+    const uint32_t ends = kunitig_ends<NW>(kunitig_slot_key<NW>(sl), w, e, K, pr,
+                                           [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); }, reasons);
+    if (ends & 1u) kunitig_append(s, kunitig_start(e, true, reasons[0]), 0);
+    if (ends & 2u) kunitig_append(s, kunitig_start(e, false, reasons[1]), 0);
+}
+
+// a lane per start: to the far end, a covered bit a k-mer on the way; the length, or 0 for the copy that is not emitted
+template <int NW>
+__global__ __launch_bounds__(256) void kunitig_measure_kernel(const uint64_t* __restrict__ tab, uint64_t mask, int K, KunitigParams pr, KunitigScratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= kunitig_n_starts(s)) return;
+    uint32_t* bits = s.bits;
+    const KunitigWalk w = kunitig_chain<NW>(kunitig_start_node<NW>(tab, s.starts[i], K), false, K, pr,
+                                            [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); },
+                                            [bits](uint64_t slot) { atomicOr(bits + (slot >> 5), 1u << (slot & 31)); }, [](uint64_t) { return false; },
+                                            nullptr);
+    s.lens[i] = w.n;
+    if (w.n && w.reason == KUNITIG_CUT) atomicAdd(s.ctr + KUNITIG_C_CUT, 1ull);
+}
+
+// a lane per table slot: a solid key no chain covered walks right until it knows whether it is the least member of a ring
+template <int NW>
+__global__ __launch_bounds__(256) void kunitig_rings_kernel(const uint64_t* __restrict__ tab, uint64_t slots, int K, KunitigParams pr, KunitigScratch s) {
+    constexpr int SW = map_slot_words<NW>();
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, mask = slots - 1;
+    if (e >= slots) return;
+    const uint64_t* sl = tab + e * SW;
+    if (sl[NW + 1] == KIDX_EMPTY || !kcor_solid_word(sl[NW], pr.min_cov) || kunitig_covered(s.bits, e)) return;
+    const uint32_t* bits = s.bits;                 // (read only here: a ring's k-mers are not marked)
+    const uint64_t start = kunitig_start(e, true, KUNITIG_CYCLE);
+    const KunitigWalk w = kunitig_chain<NW>(kunitig_start_node<NW>(tab, start, K), true, K, pr,
+                                            [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); },
+                                            [](uint64_t) {}, [bits](uint64_t slot) { return kunitig_covered(bits, slot); }, nullptr);
+    if (!w.n) return;
+    kunitig_append(s, start, w.n);
+    atomicAdd(s.ctr + KUNITIG_C_CYCLIC, 1ull);
+}
+
+// start i's counts for the scan: kept, words, k-mers; a lane past the list has none
+__device__ __forceinline__ KtrimCounts kunitig_lane_counts(const KunitigScratch& s, uint64_t n_starts, int K, uint64_t i) {
+    const uint32_t n = i < n_starts ? s.lens[i] : 0;
+    return KtrimCounts{{n ? 1ull : 0ull, n ? kunitig_row_words(n, K) : 0ull, n, 0}};
+}
+
+// the trim's scan over the starts: a workgroup's sums (a workgroup past the list has nothing to say: the next kernel does not read it)
+__global__ __launch_bounds__(256) void kunitig_block_sums_kernel(KunitigScratch s, int K) {
+    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
+    const uint64_t n_starts = kunitig_n_starts(s);
+    if ((uint64_t)blockIdx.x * 256 >= n_starts) return;                          // (uniform over the workgroup)
+    KtrimCounts c = kunitig_lane_counts(s, n_starts, K, (uint64_t)blockIdx.x * 256 + threadIdx.x);
+    const KtrimCounts all = ktrim_block_scan(c, wave_sums);
+    if (threadIdx.x < KTRIM_COUNTS) s.sums[(uint64_t)blockIdx.x * KTRIM_COUNTS + threadIdx.x] = all.c[threadIdx.x];
+}
+
+// One workgroup: the exclusive scan of the workgroups' sums in place (ktrim_scan_sums_kernel's rounds), the totals, and the decision the
+// write kernel obeys: full mode, and the unitigs and their words with the tail fit the capacities.  Then the batch's last offsets and
+// the tail's zero words are written here
+__global__ __launch_bounds__(256) void kunitig_scan_sums_kernel(KunitigScratch s, int K, int tail, uint64_t cap_unitigs, uint64_t cap_words,
+                                                                uint64_t* __restrict__ packed_out, uint64_t* __restrict__ word_off_out,
+                                                                uint64_t* __restrict__ kmer_base_out, uint64_t* __restrict__ totals) {
+    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
+    const uint64_t n_blocks = (kunitig_n_starts(s) + 255) / 256;
+    KtrimCounts carry{{0, 0, 0, 0}};
+    for (uint64_t at = 0; at < n_blocks; at += 256) {                           // (uniform over the workgroup: every lane meets the barriers)
+        const uint64_t b = at + threadIdx.x;
+        KtrimCounts own{{0, 0, 0, 0}};
+        if (b < n_blocks)
+#pragma unroll
+            for (int i = 0; i < KTRIM_COUNTS; i++) own.c[i] = s.sums[b * KTRIM_COUNTS + i];
+        KtrimCounts c = own;
+        const KtrimCounts all = ktrim_block_scan(c, wave_sums);
+#pragma unroll
+        for (int i = 0; i < KTRIM_COUNTS; i++) {
+            if (b < n_blocks) s.sums[b * KTRIM_COUNTS + i] = carry.c[i] + c.c[i] - own.c[i];
+            carry.c[i] += all.c[i];
+        }
+    }
+    if (threadIdx.x != 0) return;
+    const uint64_t unitigs = carry.c[0], words = carry.c[1], kmers = carry.c[2];
+    const bool overflow = packed_out && (unitigs > cap_unitigs || words + (uint64_t)tail > cap_words), go = packed_out && !overflow;
+    totals[KUNITIG_T_UNITIGS] = unitigs;
+    totals[KUNITIG_T_WORDS] = words + (uint64_t)tail;
+    totals[KUNITIG_T_BASES] = kmers + unitigs * (uint64_t)(K - 1);
+    totals[KUNITIG_T_COVERED] = kmers;
+    totals[KUNITIG_T_SOLID] = s.ctr[KUNITIG_C_SOLID];
+    totals[KUNITIG_T_CYCLIC] = s.ctr[KUNITIG_C_CYCLIC];
+    totals[KUNITIG_T_CUT] = s.ctr[KUNITIG_C_CUT];
+    totals[KUNITIG_T_OVERFLOW] = overflow ? 1 : 0;
+    s.ctr[KUNITIG_C_GO] = go ? 1 : 0;
+    if (!go) return;
+    if (word_off_out) word_off_out[unitigs] = words;
+    if (kmer_base_out) kmer_base_out[unitigs] = kmers;
+    for (int q = 0; q < tail; q++) packed_out[words + q] = 0;
+}
+
+// a lane per start: the scan inside the workgroup again, and a kept start writes its offsets, walks once more into its row, and reports
+template <int NW>
+__global__ __launch_bounds__(256) void kunitig_write_kernel(const uint64_t* __restrict__ tab, uint64_t mask, int K, KunitigParams pr, KunitigScratch s,
+                                                            uint64_t* __restrict__ packed_out, uint64_t* __restrict__ word_off_out,
+                                                            uint64_t* __restrict__ kmer_base_out, uint64_t* __restrict__ report) {
+    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
+    const uint64_t n_starts = kunitig_n_starts(s);
+    if (!s.ctr[KUNITIG_C_GO] || (uint64_t)blockIdx.x * 256 >= n_starts) return;  // (uniform over the workgroup)
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const KtrimCounts own = kunitig_lane_counts(s, n_starts, K, i);
+    KtrimCounts c = own;
+    (void)ktrim_block_scan(c, wave_sums);
+    if (!own.c[0]) return;                         // (no barrier follows)
+    const uint64_t* before = s.sums + (uint64_t)blockIdx.x * KTRIM_COUNTS;
+    const uint64_t u = before[0] + c.c[0] - 1, at = before[1] + c.c[1] - own.c[1];
+    if (word_off_out) word_off_out[u] = at;
+    if (kmer_base_out) kmer_base_out[u] = before[2] + c.c[2] - own.c[2];
+    const uint64_t start = s.starts[i];
+    const uint32_t left = kunitig_start_reason(start);
+    const uint32_t* bits = s.bits;
+    // the walk of the measure pass (or of the rings kernel) again, step for step: own.c[1] words, which the scan has counted
+    const KunitigWalk w = kunitig_chain<NW>(kunitig_start_node<NW>(tab, start, K), left == KUNITIG_CYCLE, K, pr,
+                                            [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); },
+                                            [](uint64_t) {}, [bits](uint64_t slot) { return kunitig_covered(bits, slot); }, packed_out + at);
+    if (report) {
+        report[2 * u] = kunitig_report_word(own.c[2] + (uint64_t)K - 1, left, w.reason);
+        report[2 * u + 1] = w.cov;
+    }
 }
 
 // ---- the corrector on an index cut over ranks: rounds over merged rows (kcorrect_rows.hpp) ----
@@ -922,6 +1103,72 @@ int ktrim_device_times(::pg_kindex* ix, double out[4]) {
     return PG_OK;
 }
 
+// ---- the unitigs ----
+namespace {
+
+void kunitig_free(::pg_kindex* ix) {
+    if (ix->d_uni) (void)arena_free(ix->d_uni);
+    if (ix->e_uni) (void)hipEventDestroy(ix->e_uni);
+    ix->d_uni = nullptr;
+    ix->e_uni = nullptr;
+    ix->cap_uni = 0;
+    ix->unitigged = false;
+}
+
+}  // namespace
+
+// Six launches on the caller's stream and no host wait: ends, measure, rings, the scan's two, write (count mode: without the last).  The
+// start list holds 2 * keys entries: a stored k-mer has two sides, a chain's start is an end side, and a ring's least member has none
+int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out,
+                           uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_report, uint64_t* d_totals, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const KidxRank& t = ix->ranks[0];
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    const uint64_t cap = std::max<uint64_t>(2 * t.keys, 1);
+    dim3 slot_grid, start_grid;
+    if (int rc = kidx_launch_blocks(t.slots, 256, "table too large", &slot_grid)) return rc;
+    if (int rc = kidx_launch_blocks(cap, 256, "too many starts", &start_grid)) return rc;
+    // Scratch, in words: the counters, the starts, the lengths (two a word), the block sums, the covered bits (64 a word).  It grows to
+    // the size needed: the buffer is given back first, and arena_free waits for the device as hipFree does, so no earlier compaction
+    // still uses it -- the only place the host waits
+    const uint64_t w_lens = (cap + 1) / 2, w_sums = (uint64_t)start_grid.x * KTRIM_COUNTS, w_bits = (t.slots + 63) / 64;
+    if (int rc = kidx_reserve(&ix->d_uni, &ix->cap_uni, KUNITIG_CTRS + cap + w_lens + w_sums + w_bits)) return rc;
+    KunitigScratch s;
+    s.ctr = (unsigned long long*)ix->d_uni;
+    s.starts = ix->d_uni + KUNITIG_CTRS;
+    s.lens = (uint32_t*)(s.starts + cap);
+    s.sums = s.starts + cap + w_lens;
+    s.bits = (uint32_t*)(s.sums + w_sums);
+    s.cap = cap;
+    if (!ix->e_uni) KIDX_HIP(hipEventCreate(&ix->e_uni));
+    if (ix->unitigged) KIDX_HIP(hipStreamWaitEvent(st, ix->e_uni, 0));           // (another stream than last time's: the scratch is one)
+    KIDX_HIP(hipMemsetAsync(s.ctr, 0, KUNITIG_CTRS * sizeof(uint64_t), st));
+    KIDX_HIP(hipMemsetAsync(s.bits, 0, w_bits * sizeof(uint64_t), st));
+    const dim3 block(256);
+    const int K = ix->K, tail = ix->nw + 1;
+    const uint64_t mask = t.slots - 1;
+    if (int rc = kidx_launch(ix, [&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            hipLaunchKernelGGL((kunitig_ends_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, pr, s);
+            hipLaunchKernelGGL((kunitig_measure_kernel<NW>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
+            hipLaunchKernelGGL((kunitig_rings_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, pr, s);
+        }))
+        return rc;
+    hipLaunchKernelGGL(kunitig_block_sums_kernel, start_grid, block, 0, st, s, K);
+    hipLaunchKernelGGL(kunitig_scan_sums_kernel, dim3(1), block, 0, st, s, K, tail, cap_unitigs, cap_words, d_packed_out, d_word_off_out, d_kmer_base_out,
+                       d_totals);
+    KIDX_HIP(hipGetLastError());
+    if (d_packed_out)
+        if (int rc = kidx_launch(ix, [&](auto nw) {
+                hipLaunchKernelGGL((kunitig_write_kernel<decltype(nw)::value>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s, d_packed_out,
+                                   d_word_off_out, d_kmer_base_out, d_report);
+            }))
+            return rc;
+    KIDX_HIP(hipEventRecord(ix->e_uni, st));
+    ix->unitigged = true;
+    return PG_OK;
+}
+
 // ---- the corrector on an index cut over ranks ----
 namespace {
 
@@ -1030,6 +1277,10 @@ void kidx_device_free(::pg_kindex* ix) {
     if (ix->d_cor || ix->e_cor) {                  // (the same for the corrector's rounds)
         (void)hipSetDevice(ix->device);
         kcor_rows_free(ix);
+    }
+    if (ix->d_uni || ix->e_uni) {                  // (and for the unitigs)
+        (void)hipSetDevice(ix->device);
+        kunitig_free(ix);
     }
     kidx_sync_ranks(ix);                           // every stream first: the lead's copies read the other ranks' rows
     for (KidxRank& r : ix->ranks) {

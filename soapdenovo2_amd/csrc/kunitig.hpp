@@ -1,0 +1,219 @@
+// kunitig.hpp -- the whole graph of the k-mer index compacted into unitigs (pg_kindex_unitigs, include/soapdenovo2_amd.h section 3; DESIGN.md
+// §14).  kwalk.hpp extends sequences the caller already has; this is the operator that asks nothing of the caller but two thresholds and
+// returns every maximal unambiguous path of the graph exactly once, as a ragged batch the other operators take where it lies.  The
+// reference does the same once for the whole graph, from the same counters (node2edge.c).
+//
+// Solid, the arc sets out_x and in_x of an oriented k-mer x, min_cov (1..255) and min_arc (1..63) are kwalk.hpp's: kcor_solid_word,
+// kwalk_out_set, kwalk_in_set.
+//
+// The right side of a solid oriented k-mer x is OPEN when all of
+//     out_x holds exactly one base b                      else KWALK_DEAD_END (none) or KWALK_BRANCH_OUT (several)
+//     y = next(x, b) is solid                             else KWALK_WEAK_NEXT
+//     in_y is exactly { first base of x }                 else KWALK_BRANCH_IN
+//     canon(y) != canon(x)                                else KUNITIG_HAIRPIN
+// hold, and otherwise it is an END with the first reason of that list that applies.  HAIRPIN covers x -> rc(x) (K odd: K - 1 is even,
+// so the (K-1)-mer the two share can be its own reverse complement) and the self-loop x -> x; without it a path could run back over its
+// own reverse complement and every node would come out twice.  The left side of x is the right side of rc(x).
+// Open is symmetric: the right side of x is open towards y exactly when the left side of y is open towards x.  The test reads x's record
+// for out_x and y's for in_y, and the left side of y -- the right side of rc(y) -- reads y's record for out_rc(y) = the complement of in_y and
+// x's for in_rc(x) = the complement of out_x: the same two sets, whatever the counters hold.
+//
+// A LINEAR unitig is a maximal chain x0 -> x1 -> ... -> x(n-1), n >= 1, every step through an open right side, the left side of x0 and
+// the right side of x(n-1) ends.  Its text is x0 followed by the appended bases, n + K - 1 of them.  It is found from both ends, from
+// s = x0 and from e = rc(x(n-1)) as its reverse complement, and emitted once: from s iff !kmer_less(e, s).
+// With K odd a chain from an end never meets a canonical k-mer twice (DESIGN.md §14 has the argument), so s != e and n is at most the
+// number of solid k-mers.
+// A CYCLIC unitig is a set of solid k-mers none of which has an end side: a ring.  It is emitted once, from the member with the least
+// canonical key in that key's canonical orientation, walking right; n + K - 1 bases, both reasons KUNITIG_CYCLE.  A member that meets a
+// smaller canonical key, a covered k-mer or an end knows that it is not that member and stops there.
+// The guard: a walk stops after max_kmers (1 .. 2^26) k-mers.  A linear chain that is longer comes out from both of its ends, each with
+// KUNITIG_CUT on the cut side, and the k-mers between the two cuts (or, where the two overlap, under both) are not in exactly one
+// unitig; a ring that is longer is not emitted at all -- its least member cannot tell it from the inside of a cut chain.  The totals
+// count the cut unitigs.  When nothing was cut, every solid k-mer lies in exactly one emitted unitig in exactly one orientation.
+//
+// One piece of PG_HD code for the kernels (kindex_kernels.hip: kunitig_*_kernel) and the host twin (kunitig_host.cpp): kunitig_side is
+// the side test, kunitig_chain the one walk that measures (row == null) or writes; both take the lookup as a function of the canonical
+// k-mer that also returns the slot, for the covered bit a slot.  The 32 bases being filled stay in one word and are stored when it is
+// full; reason and length are kept with selects (DESIGN.md §11 on what stores under branches inside such a loop became).
+#pragma once
+#include "kwalk.hpp"
+
+namespace pg {
+
+constexpr uint32_t KUNITIG_MAX_KMERS = 1u << 26;
+constexpr int KUNITIG_TOTALS = 8;
+// end reasons: KWALK_DEAD_END (3), KWALK_BRANCH_OUT (4), KWALK_WEAK_NEXT (5), KWALK_BRANCH_IN (6) and
+enum : uint32_t { KUNITIG_HAIRPIN = 9, KUNITIG_CYCLE = 10, KUNITIG_CUT = 11 };
+// out_totals
+enum : int {
+    KUNITIG_T_UNITIGS = 0, KUNITIG_T_WORDS = 1, KUNITIG_T_BASES = 2, KUNITIG_T_COVERED = 3, KUNITIG_T_SOLID = 4, KUNITIG_T_CYCLIC = 5,
+    KUNITIG_T_CUT = 6, KUNITIG_T_OVERFLOW = 7,
+};
+
+struct KunitigParams {
+    uint32_t min_cov, min_arc, max_kmers;
+};
+
+// A start: the slot of x0's canonical key, whether x0 is that key (else its reverse complement), and the reason of x0's left side (an
+// end reason, or KUNITIG_CYCLE for the least member of a ring)
+constexpr int KUNITIG_START_FWD = 62, KUNITIG_START_REASON = 56;
+PG_HD uint64_t kunitig_start(uint64_t slot, bool fwd, uint32_t reason) {
+    return slot | (uint64_t)(fwd ? 1 : 0) << KUNITIG_START_FWD | (uint64_t)reason << KUNITIG_START_REASON;
+}
+PG_HD uint64_t kunitig_start_slot(uint64_t s) { return s & ((1ull << KUNITIG_START_REASON) - 1); }
+PG_HD bool kunitig_start_fwd(uint64_t s) { return (s >> KUNITIG_START_FWD & 1) != 0; }
+PG_HD uint32_t kunitig_start_reason(uint64_t s) { return (uint32_t)(s >> KUNITIG_START_REASON) & 15u; }
+
+// words of a unitig of n k-mers, and its first report word
+PG_HD uint64_t kunitig_row_words(uint32_t n, int K) { return ((uint64_t)n + (uint64_t)K - 1 + 31) / 32; }
+PG_HD uint64_t kunitig_report_word(uint64_t bases, uint32_t left, uint32_t right) { return bases | (uint64_t)left << 32 | (uint64_t)right << 40; }
+
+// kidx_find that also says where: the word of canonical key ck and its slot; 0 (and the slot untouched) when the table has no such key
+template <int NW>
+PG_HD uint64_t kunitig_probe(const uint64_t* tab, uint64_t mask, const Kmer<NW>& ck, uint64_t& slot) {
+    const uint64_t* sl = map_probe<NW>(tab, mask, ck);
+    if (!sl) return 0;
+    slot = (uint64_t)(sl - tab) / map_slot_words<NW>();
+    return sl[NW];
+}
+
+// the k-mer's first base in the top bits of word 0: the first words of its packed text
+template <int NW>
+PG_HD Kmer<NW> kunitig_left_aligned(Kmer<NW> a, int K) {
+    int d = 64 * NW - 2 * K;
+#pragma unroll
+    for (int step = 0; step < NW - 1; step++) {
+        if (d >= 64) {
+#pragma unroll
+            for (int i = 0; i < NW - 1; i++) a.w[i] = a.w[i + 1];
+            a.w[NW - 1] = 0;
+            d -= 64;
+        }
+    }
+    if (d > 0) {
+#pragma unroll
+        for (int i = 0; i < NW - 1; i++) a.w[i] = (a.w[i] << d) | (a.w[i + 1] >> (64 - d));
+        a.w[NW - 1] <<= d;
+    }
+    return a;
+}
+
+// An oriented k-mer with its word in hand: a = the k-mer, b = its reverse complement, fwd: a is the canonical one
+template <int NW>
+struct KunitigNode {
+    Kmer<NW> a, b;
+    uint64_t w, slot;
+    bool fwd;
+};
+template <int NW>
+PG_HD Kmer<NW> kunitig_canon(const KunitigNode<NW>& x) { return x.fwd ? x.a : x.b; }
+
+// the node of the canonical key c stored at `slot` with word w, as itself (fwd) or as its reverse complement
+template <int NW>
+PG_HD KunitigNode<NW> kunitig_node(const Kmer<NW>& c, uint64_t w, uint64_t slot, bool fwd, int K) {
+    const Kmer<NW> r = kmer_rc<NW>(c, K);
+    return KunitigNode<NW>{fwd ? c : r, fwd ? r : c, w, slot, fwd};
+}
+
+// The side test: 0 when the right side of the solid node x is open, and then y is the node behind it and base the base that leads
+// there; else the end's reason.  find(ck, slot) = kunitig_probe.  One lookup, none for DEAD_END and BRANCH_OUT
+template <int NW, typename Find>
+PG_HD uint32_t kunitig_side(const KunitigNode<NW>& x, int K, const Kmer<NW>& filter, const KunitigParams& pr, Find find, KunitigNode<NW>& y, int& base) {
+    const uint32_t out = kwalk_out_set(x.w, x.fwd, pr.min_arc);
+    if (!kwalk_single(out)) return !out ? KWALK_DEAD_END : KWALK_BRANCH_OUT;
+    base = kwalk_lowest(out);
+    const int first = (int)(x.b.w[NW - 1] & 3) ^ 2;                              // (x's first base: the complement of its reverse complement's last)
+    y.a = x.a;
+    y.b = x.b;
+    kmer_roll<NW>(y.a, y.b, base, K, filter);
+    y.fwd = !kmer_less<NW>(y.b, y.a);
+    y.slot = 0;
+    y.w = find(kunitig_canon<NW>(y), y.slot);
+    const bool solid = kcor_solid_word(y.w, pr.min_cov), joined = kwalk_in_set(y.w, y.fwd, pr.min_arc) == 1u << first;
+    const bool same = kmer_eq<NW>(kunitig_canon<NW>(y), kunitig_canon<NW>(x));
+    return !solid ? KWALK_WEAK_NEXT : !joined ? KWALK_BRANCH_IN : same ? KUNITIG_HAIRPIN : 0;
+}
+
+// What a walk found.  n == 0: the start is not the one its unitig is emitted from (the losing end of a chain; not the least member of a
+// ring, or no ring at all) and nothing of the rest counts
+struct KunitigWalk {
+    uint32_t n, reason;            // k-mers, and the reason on the right
+    uint64_t cov;                  // the sum of their coverage
+};
+
+// One walk to the right of the solid node x0.  cyclic: x0 is a canonical k-mer that asks whether it is the least member of a ring.
+// mark(slot) is called for every k-mer of a chain (not of a ring), covered(slot) asked of every k-mer a ring's walk meets.
+// row (may be null): the unitig's kunitig_row_words(n, K) words
+template <int NW, typename Find, typename Mark, typename Covered>
+PG_HD KunitigWalk kunitig_chain(const KunitigNode<NW>& x0, bool cyclic, int K, const KunitigParams& pr, Find find, Mark mark, Covered covered,
+                                uint64_t* row) {
+    const Kmer<NW> filter = kmer_filter<NW>(K);
+    const Kmer<NW> text = kunitig_left_aligned<NW>(x0.a, K), c0 = kunitig_canon<NW>(x0);
+    KunitigNode<NW> x = x0;
+    uint32_t n = 1, reason = 0, pos = (uint32_t)K;             // pos: bases of the text so far
+    uint64_t cov = kidx_coverage(x0.w), acc = 0;               // acc: the bases of word pos / 32 so far
+    bool lost = false;
+#pragma unroll
+    for (int q = 0; q < NW; q++) {
+        if (row && q < K / 32) row[q] = text.w[q];
+        acc = q == K / 32 ? text.w[q] : acc;
+    }
+    if (!cyclic) mark(x0.slot);
+    for (;;) {
+        KunitigNode<NW> y = x;                     // (an end before the lookup leaves y as it is)
+        int base = 0;
+        reason = kunitig_side<NW>(x, K, filter, pr, find, y, base);
+        if (cyclic) {
+            const Kmer<NW> cy = kunitig_canon<NW>(y);
+            const bool closes = !reason && kmer_eq<NW>(cy, c0);
+            // an end: a chain, not a ring; a smaller key: not the least member; a covered k-mer: a chain that was cut; the guard: too long to tell
+            lost = !closes && (reason || kmer_less<NW>(cy, c0) || covered(y.slot) || n == pr.max_kmers);
+            reason = closes ? KUNITIG_CYCLE : reason;
+            if (lost) break;
+        }
+        reason = !reason && n == pr.max_kmers ? KUNITIG_CUT : reason;
+        if (reason) break;
+        acc |= (uint64_t)base << (62 - 2 * (int)(pos & 31));
+        pos++;
+        if (!(pos & 31)) {
+            if (row) row[pos / 32 - 1] = acc;
+            acc = 0;
+        }
+        cov += kidx_coverage(y.w);
+        n++;
+        x = y;
+        if (!cyclic) mark(x.slot);
+    }
+    if (row && (pos & 31)) row[pos / 32] = acc;
+    // a chain is emitted from the end that is not greater; a cut one from both
+    lost = lost || (!cyclic && reason != KUNITIG_CUT && kmer_less<NW>(x.b, x0.a));
+    return KunitigWalk{lost ? 0u : n, reason, cov};
+}
+
+// The ends of the solid canonical k-mer c at `slot`: bit 0 of the result says its left side is an end (c starts a walk), bit 1 that
+// its right side is (rc(c) starts one); reasons[0], reasons[1] are the two sides' reasons, left first.  At most two lookups
+template <int NW, typename Find>
+PG_HD uint32_t kunitig_ends(const Kmer<NW>& c, uint64_t w, uint64_t slot, int K, const KunitigParams& pr, Find find, uint32_t reasons[2]) {
+    const Kmer<NW> filter = kmer_filter<NW>(K);
+    const KunitigNode<NW> f = kunitig_node<NW>(c, w, slot, true, K), r = kunitig_node<NW>(c, w, slot, false, K);
+    KunitigNode<NW> y = f;
+    int base = 0;
+    reasons[1] = kunitig_side<NW>(f, K, filter, pr, find, y, base);
+    reasons[0] = kunitig_side<NW>(r, K, filter, pr, find, y, base);
+    return (reasons[0] ? 1u : 0u) | (reasons[1] ? 2u : 0u);
+}
+
+// the canonical key stored in a slot
+template <int NW>
+PG_HD Kmer<NW> kunitig_slot_key(const uint64_t* sl) {
+    Kmer<NW> k;
+#pragma unroll
+    for (int q = 0; q < NW; q++) k.w[q] = sl[q];
+    return k;
+}
+
+// The caller's side of the device engine (kindex_kernels.hip), asynchronous on `stream`: count mode when d_packed_out is null
+int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out,
+                           uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_report, uint64_t* d_totals, void* stream);
+
+}  // namespace pg
