@@ -93,7 +93,7 @@ PG_HD void kidx_stretch(const uint64_t* rd, int j0, int j1, int K, const uint64_
     });
 }
 
-// the key of a record in export format: its first NW words
+// the key of a record in export format, or of a table slot: its first NW words
 template <int NW>
 PG_HD Kmer<NW> kidx_record_key(const uint64_t* rec) {
     Kmer<NW> k;
@@ -178,6 +178,24 @@ enum : unsigned {
 };
 int kidx_batch_args(const char* who, const ::pg_kindex* ix, const KidxBatch& b, const char* noun, unsigned checks);
 
+// What the scans of the operators sum over their items, 256 items a workgroup (kindex_kernels.hip: kidx_block_scan and the kernels round
+// it): up to four counts an item.  The trim's are ktrim_counts (ktrim.hpp), the unitigs' kunitig_counts (kunitig.hpp)
+constexpr int KIDX_COUNTS = 4;
+struct KidxCounts {
+    uint64_t c[KIDX_COUNTS];
+};
+
+// An operator's scratch on the lead's device: a buffer that grows to the largest call met, the end event of the last call that used it
+// -- a call on another stream than that one's waits for it on the device: the scratch is one -- and whether that event was recorded.
+// A buffer that has to grow is given back first, and arena_free waits for the device as hipFree does, so no earlier call still uses it:
+// the only place the host waits.  (kindex_kernels.hip: kidx_scratch_begin, kidx_scratch_end, kidx_scratch_free)
+struct KidxScratch {
+    uint64_t* d = nullptr;
+    uint64_t cap = 0;              // words
+    hipEvent_t e_end = nullptr;
+    bool recorded = false;         // e_end has been recorded
+};
+
 // the device engine (kindex_kernels.hip); a table is cut from the arena of its rank's device.  PG_OK or a PG_E* code with pg_set_error done
 int kidx_device_build(::pg_kindex* ix, const uint64_t* d_records, uint64_t n_records, void* stream);
 int kidx_device_query(::pg_kindex* ix, const KidxBatch& b, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream);
@@ -204,25 +222,14 @@ struct pg_kindex {
     uint64_t cap_staging = 0;
     hipEvent_t e_begin = nullptr, e_probed = nullptr, e_merged = nullptr, e_end = nullptr;
     bool queried = false;          // e_end has been recorded
-    // pg_kindex_trim's scratch on `device` (ktrim.hpp): the spans and source indices the caller did not ask for and the scan's block sums.
-    // It grows to the largest batch met; the events are a trim's begin, spans done, scan done, end
-    uint64_t* d_trim = nullptr;
-    uint64_t cap_trim = 0;
-    hipEvent_t e_trim[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool trimmed = false;          // e_trim has been recorded
-    // pg_kindex_correct_rows' scratch on `device` (kcorrect_rows.hpp): the reads' state words and as-given bits, a round's trial batch, its
-    // rows, the read of each trial and the claim counter.  It grows to the largest batch met; the event is the last correction's end
-    uint64_t* d_cor = nullptr;
-    uint64_t cap_cor = 0;
-    hipEvent_t e_cor = nullptr;
-    bool corrected = false;        // e_cor has been recorded
+    // The operators' scratch on `device`, one each: merged into one buffer they would order calls on different streams that are independent.
+    // trim (ktrim.hpp): the spans and source indices the caller did not ask for and the scan's block sums; e_trim are a trim's begin,
+    // spans done and scan done, and its end is the scratch's.  cor (kcorrect_rows.hpp): the reads' state words and as-given bits, a
+    // round's trial batch, its rows, the read of each trial and the claim counter.  uni (kunitig.hpp): the counters, the start list, the
+    // lengths, the scan's block sums and a covered bit a slot
+    pg::KidxScratch trim, cor, uni;
+    hipEvent_t e_trim[3] = {nullptr, nullptr, nullptr};
     uint64_t cor_stats[4] = {0, 0, 0, 0};   // the last pg_kindex_correct_rows: rounds, trials, k-mers asked in trials, host waits
-    // pg_kindex_unitigs' scratch on `device` (kunitig.hpp): the counters, the start list, the lengths, the scan's block sums and a covered
-    // bit a slot.  It grows to the size needed; the event is the last compaction's end
-    uint64_t* d_uni = nullptr;
-    uint64_t cap_uni = 0;
-    hipEvent_t e_uni = nullptr;
-    bool unitigged = false;        // e_uni has been recorded
 };
 
 namespace pg {

@@ -24,6 +24,18 @@
 //                           lookup.  One dependent slot read per appended base, latency-chained within the lane; the word of 32 bases
 //                           being filled stays in a register and is stored when full.  No LDS, no barrier; lanes whose walks ended wait
 //                           for the longest walk of their wave.
+// What the operators below share:
+//   the graph step and the base writer   kwalk.hpp: kwalk_step over a KwalkNode and KwalkText, PG_HD code for the walk and the unitigs,
+//                              the kernels and the host twins; the lookup is a lambda find(ck, slot&) -- kidx_find for the walk, which
+//                              leaves the slot alone, kunitig_probe for the unitigs
+//   the scan                   here, for the trim and the unitigs: KidxCounts (kindex.hpp) an item, blocks of 256 items.  kidx_block_scan
+//                              (a workgroup's inclusive scan: __shfl_up inside a wave, the four waves' sums through LDS) and the bodies of
+//                              the three kernels a scan takes: kidx_block_sums (a workgroup's sums), kidx_scan_block_sums (one workgroup:
+//                              the blocks' sums scanned in place, 256 a round with the carry in registers; the totals) and
+//                              kidx_scan_before (the scan inside a workgroup again: what the items before a lane add up to).  Each
+//                              operator's kernels add where a lane's counts come from and what is done with the offsets
+//   the scratch                KidxScratch (kindex.hpp), one each for the trim, the corrector on a cut index and the unitigs:
+//                              kidx_scratch_begin / _end / _free.  kidx_settled is the one way out of an entry point over the ranks
 // The index cut over ranks (kindex.hpp; pg_kindex_build_sharded, pg_kindex_query_words):
 //   kidx_count_owners_kernel   a lane per record of a device part, on the device where the part lies: the owners of all n ranks at once
 //                              into an LDS histogram (n <= 256 bins: 1 KB, zeroed and flushed per workgroup), one global atomicAdd per
@@ -38,10 +50,9 @@
 //                              registers (ktrim_span_probe), one span word stored.  The span word is all the scan wants of a read: kept,
 //                              output words and output k-mers are ktrim_counts of it
 //   ktrim_span_rows_kernel     the same tracker over a read's row of merged answers (an index cut over ranks), no probe
-//   the scan                   three kernels over blocks of 256 reads: ktrim_block_sums_kernel (a workgroup's sums of the four counts
-//                              through wave butterflies and LDS), ktrim_scan_sums_kernel (one workgroup: the exclusive scan of the
-//                              workgroups' sums in place, the totals, kmer_base_out's last entry), ktrim_scatter_kernel (the scan
-//                              inside a workgroup again, and every kept read's word_off_out, kmer_base_out and src_out)
+//   the scan                   over ktrim_counts of the span words: ktrim_block_sums_kernel, ktrim_scan_sums_kernel (the totals,
+//                              kmer_base_out's last entry), ktrim_scatter_kernel (every kept read's word_off_out, kmer_base_out and
+//                              src_out)
 //   ktrim_pack_kernel          a lane per output word, the tail's nw + 1 zero words included: the kept read by binary search in
 //                              word_off_out, the word by ktrim_pack_word.  The launch covers the batch's n_words, which the result never
 //                              passes; how many of those lanes have a word is read from the totals on the device
@@ -52,10 +63,10 @@
 //                              words), the length, or 0 for the copy the orientation rule does not emit
 //   kunitig_rings_kernel       a lane per slot, solid and not covered: the cyclic form of kunitig_chain, which ends at the first smaller
 //                              key; a ring's least member appends its start behind the chains' -- one scan and one write serve both
-//   the scan                   the trim's ktrim_block_scan over (kept, words, k-mers) of the starts: kunitig_block_sums_kernel and
-//                              kunitig_scan_sums_kernel (one workgroup: the totals, the overflow decision the write kernel obeys, the
-//                              last offsets and the tail's zero words)
-//   kunitig_write_kernel       a lane per start: the scan inside the workgroup again, and a kept start walks once more into its row
+//   the scan                   over kunitig_counts (kept, words, k-mers) of the starts: kunitig_block_sums_kernel and
+//                              kunitig_scan_sums_kernel (the totals, the overflow decision the write kernel obeys, the last offsets and
+//                              the tail's zero words)
+//   kunitig_write_kernel       a lane per start: its offsets from the scan, and a kept start walks once more into its row
 // The corrector on an index cut over ranks (kcorrect_rows.hpp; pg_kindex_correct_rows): rounds of plan, query, decide on the
 // caller's stream, every query kidx_query_ranks, and the host reads the round's trial count back once a round
 //   kcor_rows_begin_kernel     a lane per read over its row of the read as given: weak count, anchor, first weak k-mer behind it, the
@@ -206,7 +217,7 @@ __global__ __launch_bounds__(256) void kwalk_kernel(KidxBatch b, int K, const ui
     const uint64_t v = kidx_seq_index<false>();
     if (v >= 2 * b.n_seqs) return;
     const KidxSeq q = kidx_seq(b, K, v >> 1);
-    kwalk_one<NW>(q.rd, q.nk, K, (v & 1) != 0, pr, [tab, mask](const Kmer<NW>& ck) { return kidx_find<NW>(tab, mask, ck); },
+    kwalk_one<NW>(q.rd, q.nk, K, (v & 1) != 0, pr, [tab, mask](const Kmer<NW>& ck, uint64_t&) { return kidx_find<NW>(tab, mask, ck); },
                   ext ? ext + v * kwalk_row_words(pr.max_ext) : nullptr, report ? report + 2 * v : nullptr);
 }
 
@@ -268,18 +279,13 @@ __global__ __launch_bounds__(256) void ktrim_span_rows_kernel(KidxBatch b, int K
     span[r] = ktrim_span_row(rows + w.base, w.nk, K, min_cov);
 }
 
-// read r's counts; a lane past the batch has none
-__device__ __forceinline__ KtrimCounts ktrim_lane_counts(const uint64_t* span, const KidxBatch& b, int K, uint32_t min_len, uint64_t r) {
-    if (r >= b.n_seqs) return KtrimCounts{{0, 0, 0, 0}};
-    return ktrim_counts(span[r], kidx_row(b, K, r).nk, K, min_len);
-}
-
+// ---- the scan the trim and the unitigs share: an item's counts summed over blocks of 256 items, three kernels a scan ----
 // The inclusive scan of the lanes' counts over a 256-thread workgroup: inside a wave by __shfl_up, the four waves' sums through LDS.
 // Every lane of the workgroup calls it.  c becomes the lane's inclusive sums, and the workgroup's sums are returned
-__device__ __forceinline__ KtrimCounts ktrim_block_scan(KtrimCounts& c, uint64_t (*wave_sums)[KTRIM_COUNTS]) {
+__device__ __forceinline__ KidxCounts kidx_block_scan(KidxCounts& c, uint64_t (*wave_sums)[KIDX_COUNTS]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int i = 0; i < KTRIM_COUNTS; i++) {
+    for (int i = 0; i < KIDX_COUNTS; i++) {
         uint64_t v = c.c[i];
         for (int d = 1; d < 64; d <<= 1) {
             const uint64_t o = __shfl_up(v, d);
@@ -289,9 +295,9 @@ __device__ __forceinline__ KtrimCounts ktrim_block_scan(KtrimCounts& c, uint64_t
         if (lane == 63) wave_sums[wave][i] = v;
     }
     __syncthreads();
-    KtrimCounts all{{0, 0, 0, 0}};
+    KidxCounts all{{0, 0, 0, 0}};
 #pragma unroll
-    for (int i = 0; i < KTRIM_COUNTS; i++)
+    for (int i = 0; i < KIDX_COUNTS; i++)
 #pragma unroll
         for (int w = 0; w < 4; w++) {
             const uint64_t s = wave_sums[w][i];
@@ -302,37 +308,65 @@ __device__ __forceinline__ KtrimCounts ktrim_block_scan(KtrimCounts& c, uint64_t
     return all;
 }
 
-__global__ __launch_bounds__(256) void ktrim_block_sums_kernel(const uint64_t* __restrict__ span, KidxBatch b, int K, uint32_t min_len,
-                                                               uint64_t* __restrict__ sums) {
-    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
-    KtrimCounts c = ktrim_lane_counts(span, b, K, min_len, (uint64_t)blockIdx.x * 256 + threadIdx.x);
-    const KtrimCounts all = ktrim_block_scan(c, wave_sums);
-    if (threadIdx.x < KTRIM_COUNTS) sums[(uint64_t)blockIdx.x * KTRIM_COUNTS + threadIdx.x] = all.c[threadIdx.x];
+// the first kernel: the sums of this workgroup's lanes' counts become block blockIdx.x of `sums`.  Every lane of the workgroup calls it
+__device__ __forceinline__ void kidx_block_sums(KidxCounts c, uint64_t* __restrict__ sums) {
+    __shared__ uint64_t wave_sums[4][KIDX_COUNTS];
+    const KidxCounts all = kidx_block_scan(c, wave_sums);
+    if (threadIdx.x < KIDX_COUNTS) sums[(uint64_t)blockIdx.x * KIDX_COUNTS + threadIdx.x] = all.c[threadIdx.x];
 }
 
-// one workgroup: sums[b] becomes the sums of the workgroups before b, 256 of them a round with the carry in registers
-__global__ __launch_bounds__(256) void ktrim_scan_sums_kernel(uint64_t* __restrict__ sums, uint64_t n_blocks, uint64_t* __restrict__ kmer_base_out,
-                                                              uint64_t* __restrict__ totals) {
-    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
-    KtrimCounts carry{{0, 0, 0, 0}};
+// the second kernel, one workgroup: sums[b] becomes the sums of the blocks before b, in place, 256 blocks a round with the carry in
+// registers.  Every lane calls it, and every lane gets the totals
+__device__ __forceinline__ KidxCounts kidx_scan_block_sums(uint64_t* __restrict__ sums, uint64_t n_blocks) {
+    __shared__ uint64_t wave_sums[4][KIDX_COUNTS];
+    KidxCounts carry{{0, 0, 0, 0}};
     for (uint64_t at = 0; at < n_blocks; at += 256) {                           // (uniform over the workgroup: every lane meets the barriers)
         const uint64_t b = at + threadIdx.x;
-        KtrimCounts own{{0, 0, 0, 0}};
+        KidxCounts own{{0, 0, 0, 0}};
         if (b < n_blocks)
 #pragma unroll
-            for (int i = 0; i < KTRIM_COUNTS; i++) own.c[i] = sums[b * KTRIM_COUNTS + i];
-        KtrimCounts c = own;
-        const KtrimCounts all = ktrim_block_scan(c, wave_sums);
+            for (int i = 0; i < KIDX_COUNTS; i++) own.c[i] = sums[b * KIDX_COUNTS + i];
+        KidxCounts c = own;
+        const KidxCounts all = kidx_block_scan(c, wave_sums);
 #pragma unroll
-        for (int i = 0; i < KTRIM_COUNTS; i++) {
-            if (b < n_blocks) sums[b * KTRIM_COUNTS + i] = carry.c[i] + c.c[i] - own.c[i];
+        for (int i = 0; i < KIDX_COUNTS; i++) {
+            if (b < n_blocks) sums[b * KIDX_COUNTS + i] = carry.c[i] + c.c[i] - own.c[i];
             carry.c[i] += all.c[i];
         }
     }
+    return carry;
+}
+
+// the third kernel: the scan inside the workgroup again, and what the items before this lane's add up to over the whole launch -- its
+// block's entry of the scanned sums, the lanes before it, itself not.  Every lane of the workgroup calls it
+__device__ __forceinline__ KidxCounts kidx_scan_before(const KidxCounts& own, const uint64_t* __restrict__ sums) {
+    __shared__ uint64_t wave_sums[4][KIDX_COUNTS];
+    KidxCounts c = own;
+    (void)kidx_block_scan(c, wave_sums);
+#pragma unroll
+    for (int i = 0; i < KIDX_COUNTS; i++) c.c[i] += sums[(uint64_t)blockIdx.x * KIDX_COUNTS + i] - own.c[i];
+    return c;
+}
+
+// read r's counts; a lane past the batch has none
+__device__ __forceinline__ KidxCounts ktrim_lane_counts(const uint64_t* span, const KidxBatch& b, int K, uint32_t min_len, uint64_t r) {
+    if (r >= b.n_seqs) return KidxCounts{{0, 0, 0, 0}};
+    return ktrim_counts(span[r], kidx_row(b, K, r).nk, K, min_len);
+}
+
+__global__ __launch_bounds__(256) void ktrim_block_sums_kernel(const uint64_t* __restrict__ span, KidxBatch b, int K, uint32_t min_len,
+                                                               uint64_t* __restrict__ sums) {
+    kidx_block_sums(ktrim_lane_counts(span, b, K, min_len, (uint64_t)blockIdx.x * 256 + threadIdx.x), sums);
+}
+
+// one workgroup: the scan of the workgroups' sums, the totals, kmer_base_out's last entry
+__global__ __launch_bounds__(256) void ktrim_scan_sums_kernel(uint64_t* __restrict__ sums, uint64_t n_blocks, uint64_t* __restrict__ kmer_base_out,
+                                                              uint64_t* __restrict__ totals) {
+    const KidxCounts all = kidx_scan_block_sums(sums, n_blocks);
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int i = 0; i < KTRIM_COUNTS; i++) totals[i] = carry.c[i];
-        kmer_base_out[carry.c[0]] = carry.c[2];
+        for (int i = 0; i < KIDX_COUNTS; i++) totals[i] = all.c[i];
+        kmer_base_out[all.c[0]] = all.c[2];
     }
 }
 
@@ -340,16 +374,13 @@ __global__ __launch_bounds__(256) void ktrim_scatter_kernel(const uint64_t* __re
                                                             const uint64_t* __restrict__ sums,
                                                             uint64_t* __restrict__ word_off_out, uint64_t* __restrict__ kmer_base_out,
                                                             uint64_t* __restrict__ src_out) {
-    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
     const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const KtrimCounts own = ktrim_lane_counts(span, b, K, min_len, r);
-    KtrimCounts c = own;
-    (void)ktrim_block_scan(c, wave_sums);
+    const KidxCounts own = ktrim_lane_counts(span, b, K, min_len, r);
+    const KidxCounts before = kidx_scan_before(own, sums);
     if (!own.c[0]) return;                         // (no barrier follows)
-    const uint64_t* before = sums + (uint64_t)blockIdx.x * KTRIM_COUNTS;
-    const uint64_t i = before[0] + c.c[0] - 1;     // the kept reads before this one
-    word_off_out[i] = before[1] + c.c[1] - own.c[1];
-    kmer_base_out[i] = before[2] + c.c[2] - own.c[2];
+    const uint64_t i = before.c[0];                // the kept reads before this one
+    word_off_out[i] = before.c[1];
+    kmer_base_out[i] = before.c[2];
     src_out[i] = r;
 }
 
@@ -379,7 +410,7 @@ __global__ __launch_bounds__(256) void ktrim_pack_kernel(const uint64_t* __restr
 
 // ---- the unitigs: ends, measure, rings, the scan of the kept starts' counts, write (kunitig.hpp) ----
 // The scratch of one compaction.  ctr: KUNITIG_C_*; starts / lens: `cap` entries, the chains' starts first and the rings' behind them;
-// sums: the scan's, KTRIM_COUNTS a block of 256 starts; bits: a covered bit a slot
+// sums: the scan's, KIDX_COUNTS a block of 256 starts; bits: a covered bit a slot
 enum : int { KUNITIG_C_STARTS = 0, KUNITIG_C_CYCLIC = 1, KUNITIG_C_SOLID = 2, KUNITIG_C_CUT = 3, KUNITIG_C_GO = 4, KUNITIG_CTRS = 8 };
 struct KunitigScratch {
     unsigned long long* ctr;
@@ -403,10 +434,10 @@ __device__ __forceinline__ void kunitig_append(const KunitigScratch& s, uint64_t
     s.lens[i] = len;
 }
 template <int NW>
-__device__ __forceinline__ KunitigNode<NW> kunitig_start_node(const uint64_t* tab, uint64_t start, int K) {
+__device__ __forceinline__ KwalkNode<NW> kunitig_start_node(const uint64_t* tab, uint64_t start, int K) {
     const uint64_t slot = kunitig_start_slot(start);
     const uint64_t* sl = tab + slot * map_slot_words<NW>();
-    return kunitig_node<NW>(kunitig_slot_key<NW>(sl), sl[NW], slot, kunitig_start_fwd(start), K);
+    return kunitig_node<NW>(kidx_record_key<NW>(sl), sl[NW], slot, kunitig_start_fwd(start), K);
 }
 
 // a lane per table slot: a published solid key has both sides tested, two lookups at most, and every end side becomes a start
@@ -421,7 +452,7 @@ __global__ __launch_bounds__(256) void kunitig_ends_kernel(const uint64_t* __res
     if ((threadIdx.x & 63) == 0 && wave_solid) atomicAdd(s.ctr + KUNITIG_C_SOLID, (unsigned long long)__popcll(wave_solid));
     if (!solid) return;
     uint32_t reasons[2];
-    const uint32_t ends = kunitig_ends<NW>(kunitig_slot_key<NW>(sl), w, e, K, pr,
+    const uint32_t ends = kunitig_ends<NW>(kidx_record_key<NW>(sl), w, e, K, pr,
                                            [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); }, reasons);
     if (ends & 1u) kunitig_append(s, kunitig_start(e, true, reasons[0]), 0);
     if (ends & 2u) kunitig_append(s, kunitig_start(e, false, reasons[1]), 0);
@@ -459,47 +490,26 @@ __global__ __launch_bounds__(256) void kunitig_rings_kernel(const uint64_t* __re
     atomicAdd(s.ctr + KUNITIG_C_CYCLIC, 1ull);
 }
 
-// start i's counts for the scan: kept, words, k-mers; a lane past the list has none
-__device__ __forceinline__ KtrimCounts kunitig_lane_counts(const KunitigScratch& s, uint64_t n_starts, int K, uint64_t i) {
-    const uint32_t n = i < n_starts ? s.lens[i] : 0;
-    return KtrimCounts{{n ? 1ull : 0ull, n ? kunitig_row_words(n, K) : 0ull, n, 0}};
+// start i's counts for the scan; a lane past the list has none
+__device__ __forceinline__ KidxCounts kunitig_lane_counts(const KunitigScratch& s, uint64_t n_starts, int K, uint64_t i) {
+    return kunitig_counts(i < n_starts ? s.lens[i] : 0, K);
 }
 
-// the trim's scan over the starts: a workgroup's sums (a workgroup past the list has nothing to say: the next kernel does not read it)
+// the scan over the starts: a workgroup's sums (a workgroup past the list has nothing to say: the next kernel does not read it)
 __global__ __launch_bounds__(256) void kunitig_block_sums_kernel(KunitigScratch s, int K) {
-    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
     const uint64_t n_starts = kunitig_n_starts(s);
     if ((uint64_t)blockIdx.x * 256 >= n_starts) return;                          // (uniform over the workgroup)
-    KtrimCounts c = kunitig_lane_counts(s, n_starts, K, (uint64_t)blockIdx.x * 256 + threadIdx.x);
-    const KtrimCounts all = ktrim_block_scan(c, wave_sums);
-    if (threadIdx.x < KTRIM_COUNTS) s.sums[(uint64_t)blockIdx.x * KTRIM_COUNTS + threadIdx.x] = all.c[threadIdx.x];
+    kidx_block_sums(kunitig_lane_counts(s, n_starts, K, (uint64_t)blockIdx.x * 256 + threadIdx.x), s.sums);
 }
 
-// One workgroup: the exclusive scan of the workgroups' sums in place (ktrim_scan_sums_kernel's rounds), the totals, and the decision the
-// write kernel obeys: full mode, and the unitigs and their words with the tail fit the capacities.  Then the batch's last offsets and
-// the tail's zero words are written here
+// One workgroup: the scan of the workgroups' sums, the totals, and the decision the write kernel obeys: full mode, and the unitigs and
+// their words with the tail fit the capacities.  Then the batch's last offsets and the tail's zero words are written here
 __global__ __launch_bounds__(256) void kunitig_scan_sums_kernel(KunitigScratch s, int K, int tail, uint64_t cap_unitigs, uint64_t cap_words,
                                                                 uint64_t* __restrict__ packed_out, uint64_t* __restrict__ word_off_out,
                                                                 uint64_t* __restrict__ kmer_base_out, uint64_t* __restrict__ totals) {
-    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
-    const uint64_t n_blocks = (kunitig_n_starts(s) + 255) / 256;
-    KtrimCounts carry{{0, 0, 0, 0}};
-    for (uint64_t at = 0; at < n_blocks; at += 256) {                           // (uniform over the workgroup: every lane meets the barriers)
-        const uint64_t b = at + threadIdx.x;
-        KtrimCounts own{{0, 0, 0, 0}};
-        if (b < n_blocks)
-#pragma unroll
-            for (int i = 0; i < KTRIM_COUNTS; i++) own.c[i] = s.sums[b * KTRIM_COUNTS + i];
-        KtrimCounts c = own;
-        const KtrimCounts all = ktrim_block_scan(c, wave_sums);
-#pragma unroll
-        for (int i = 0; i < KTRIM_COUNTS; i++) {
-            if (b < n_blocks) s.sums[b * KTRIM_COUNTS + i] = carry.c[i] + c.c[i] - own.c[i];
-            carry.c[i] += all.c[i];
-        }
-    }
+    const KidxCounts all = kidx_scan_block_sums(s.sums, (kunitig_n_starts(s) + 255) / 256);
     if (threadIdx.x != 0) return;
-    const uint64_t unitigs = carry.c[0], words = carry.c[1], kmers = carry.c[2];
+    const uint64_t unitigs = all.c[0], words = all.c[1], kmers = all.c[2];
     const bool overflow = packed_out && (unitigs > cap_unitigs || words + (uint64_t)tail > cap_words), go = packed_out && !overflow;
     totals[KUNITIG_T_UNITIGS] = unitigs;
     totals[KUNITIG_T_WORDS] = words + (uint64_t)tail;
@@ -521,18 +531,14 @@ template <int NW>
 __global__ __launch_bounds__(256) void kunitig_write_kernel(const uint64_t* __restrict__ tab, uint64_t mask, int K, KunitigParams pr, KunitigScratch s,
                                                             uint64_t* __restrict__ packed_out, uint64_t* __restrict__ word_off_out,
                                                             uint64_t* __restrict__ kmer_base_out, uint64_t* __restrict__ report) {
-    __shared__ uint64_t wave_sums[4][KTRIM_COUNTS];
     const uint64_t n_starts = kunitig_n_starts(s);
     if (!s.ctr[KUNITIG_C_GO] || (uint64_t)blockIdx.x * 256 >= n_starts) return;  // (uniform over the workgroup)
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const KtrimCounts own = kunitig_lane_counts(s, n_starts, K, i);
-    KtrimCounts c = own;
-    (void)ktrim_block_scan(c, wave_sums);
+    const KidxCounts own = kunitig_lane_counts(s, n_starts, K, i), before = kidx_scan_before(own, s.sums);
     if (!own.c[0]) return;                         // (no barrier follows)
-    const uint64_t* before = s.sums + (uint64_t)blockIdx.x * KTRIM_COUNTS;
-    const uint64_t u = before[0] + c.c[0] - 1, at = before[1] + c.c[1] - own.c[1];
+    const uint64_t u = before.c[0], at = before.c[1];
     if (word_off_out) word_off_out[u] = at;
-    if (kmer_base_out) kmer_base_out[u] = before[2] + c.c[2] - own.c[2];
+    if (kmer_base_out) kmer_base_out[u] = before.c[2];
     const uint64_t start = s.starts[i];
     const uint32_t left = kunitig_start_reason(start);
     const uint32_t* bits = s.bits;
@@ -752,6 +758,36 @@ int kidx_reserve(uint64_t** p, uint64_t* cap, uint64_t want) {
     }
     *cap = want;
     return PG_OK;
+}
+
+// An operator's scratch (KidxScratch, kindex.hpp; the lead's device is current).  A call begins with at least `want` words behind s.d
+// and `st` behind the end of the last call that used them, and ends by recording its own end on `st`
+int kidx_scratch_begin(KidxScratch& s, uint64_t want, hipStream_t st) {
+    if (int rc = kidx_reserve(&s.d, &s.cap, want)) return rc;
+    if (!s.e_end) KIDX_HIP(hipEventCreate(&s.e_end));
+    if (s.recorded) KIDX_HIP(hipStreamWaitEvent(st, s.e_end, 0));
+    return PG_OK;
+}
+int kidx_scratch_end(KidxScratch& s, hipStream_t st) {
+    KIDX_HIP(hipEventRecord(s.e_end, st));
+    s.recorded = true;
+    return PG_OK;
+}
+void kidx_scratch_free(KidxScratch& s) {
+    if (s.d) (void)arena_free(s.d);                // (waits for the device: no call still uses the scratch)
+    if (s.e_end) (void)hipEventDestroy(s.e_end);
+    s = KidxScratch();
+}
+
+// What an entry point over the ranks returns: after a failure no stream is left reading the caller's batch or the scratch, or writing
+// its results
+int kidx_settled(::pg_kindex* ix, int rc, void* stream) {
+    if (rc) {
+        kidx_sync_ranks(ix);
+        (void)hipSetDevice(ix->device);
+        (void)hipStreamSynchronize((hipStream_t)stream);
+    }
+    return rc;
 }
 
 // the fewest ranks pg_host_kindex_plan says hold n_records on a device with device_bytes free, a rank's table at most table_cap; 0: none
@@ -1005,55 +1041,31 @@ int kidx_device_build_sharded(::pg_kindex* ix, const uint64_t* const* parts, con
 int kidx_device_query_sharded(::pg_kindex* ix, const KidxBatch& b, int wave, uint64_t* d_out, uint64_t* d_summary, void* stream) {
     if (int rc = kidx_set_device(ix->device)) return rc;
     if (!b.n_seqs) return PG_OK;
-    const int rc = kidx_query_ranks(ix, b, wave, d_out, d_summary, (hipStream_t)stream);
-    if (rc) {                                      // no stream is left reading the caller's batch or writing its results
-        kidx_sync_ranks(ix);
-        (void)hipSetDevice(ix->device);
-        (void)hipStreamSynchronize((hipStream_t)stream);
-    }
-    return rc;
+    return kidx_settled(ix, kidx_query_ranks(ix, b, wave, d_out, d_summary, (hipStream_t)stream), stream);
 }
 
 // ---- the trim ----
-namespace {
-
-void ktrim_free(::pg_kindex* ix) {
-    if (ix->d_trim) (void)arena_free(ix->d_trim);
-    for (hipEvent_t& e : ix->e_trim) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    ix->d_trim = nullptr;
-    ix->cap_trim = 0;
-    ix->trimmed = false;
-}
-
-}  // namespace
-
 int ktrim_device_trim(::pg_kindex* ix, const KidxBatch& b, uint32_t min_cov, uint32_t min_len, uint64_t* d_span, uint64_t* d_packed_out,
                       uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_src_out, uint64_t* d_totals, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const uint64_t n_seqs = b.n_seqs;
     if (int rc = kidx_set_device(ix->device)) return rc;
     if (!n_seqs) {
-        if (d_packed_out) KIDX_HIP(hipMemsetAsync(d_totals, 0, KTRIM_COUNTS * sizeof(uint64_t), st));
+        if (d_packed_out) KIDX_HIP(hipMemsetAsync(d_totals, 0, KIDX_COUNTS * sizeof(uint64_t), st));
         return PG_OK;
     }
     dim3 grid, pack_grid;
     if (int rc = kidx_batch_blocks(n_seqs, false, &grid)) return rc;
     if (int rc = kidx_launch_blocks(b.n_words, 256, "batch too large", &pack_grid)) return rc;
     const uint64_t n_blocks = grid.x;
-    // Scratch: the spans and the source indices where the caller takes none, and the workgroups' sums.  It grows to the largest batch
-    // met: the buffer is given back first, and arena_free waits for the device as hipFree does, so no earlier trim still uses it --
-    // the only place the host waits
-    const uint64_t want = (d_span ? 0 : n_seqs) + (d_packed_out ? (d_src_out ? 0 : n_seqs) + n_blocks * KTRIM_COUNTS : 0);
-    if (int rc = kidx_reserve(&ix->d_trim, &ix->cap_trim, std::max<uint64_t>(want, 1))) return rc;
-    uint64_t* next = ix->d_trim;
+    // Scratch: the spans and the source indices where the caller takes none, and the workgroups' sums
+    const uint64_t want = (d_span ? 0 : n_seqs) + (d_packed_out ? (d_src_out ? 0 : n_seqs) + n_blocks * KIDX_COUNTS : 0);
+    if (int rc = kidx_scratch_begin(ix->trim, std::max<uint64_t>(want, 1), st)) return rc;
+    uint64_t* next = ix->trim.d;
     if (!d_span) { d_span = next; next += n_seqs; }
     if (d_packed_out && !d_src_out) { d_src_out = next; next += n_seqs; }
     uint64_t* d_sums = next;
-    for (hipEvent_t& e : ix->e_trim) if (!e) KIDX_HIP(hipEventCreate(&e));
-    if (ix->trimmed) KIDX_HIP(hipStreamWaitEvent(st, ix->e_trim[3], 0));         // (another stream than last time's: the scratch is one)
+    for (hipEvent_t& e : ix->e_trim) if (!e) KIDX_HIP(hipEventCreate(&e));       // the timing marks: begin, spans done, scan done
     KIDX_HIP(hipEventRecord(ix->e_trim[0], st));
     const dim3 block(256);
     const KidxRank& lead = ix->ranks[0];
@@ -1083,40 +1095,26 @@ int ktrim_device_trim(::pg_kindex* ix, const KidxBatch& b, uint32_t min_cov, uin
                            d_totals, ix->nw + 1, b.n_words, d_packed_out);
         KIDX_HIP(hipGetLastError());
     }
-    KIDX_HIP(hipEventRecord(ix->e_trim[3], st));
-    ix->trimmed = true;
-    return PG_OK;
+    return kidx_scratch_end(ix->trim, st);
 }
 
 int ktrim_device_times(::pg_kindex* ix, double out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (!ix->trimmed) return PG_OK;
+    if (!ix->trim.recorded) return PG_OK;
     if (int rc = kidx_set_device(ix->device)) return rc;
-    KIDX_HIP(hipEventSynchronize(ix->e_trim[3]));
+    const hipEvent_t mark[4] = {ix->e_trim[0], ix->e_trim[1], ix->e_trim[2], ix->trim.e_end};
+    KIDX_HIP(hipEventSynchronize(mark[3]));
     float ms = 0;
     for (int i = 0; i < 3; i++) {
-        KIDX_HIP(hipEventElapsedTime(&ms, ix->e_trim[i], ix->e_trim[i + 1]));
+        KIDX_HIP(hipEventElapsedTime(&ms, mark[i], mark[i + 1]));
         out[i] = ms;
     }
-    KIDX_HIP(hipEventElapsedTime(&ms, ix->e_trim[0], ix->e_trim[3]));
+    KIDX_HIP(hipEventElapsedTime(&ms, mark[0], mark[3]));
     out[3] = ms;
     return PG_OK;
 }
 
 // ---- the unitigs ----
-namespace {
-
-void kunitig_free(::pg_kindex* ix) {
-    if (ix->d_uni) (void)arena_free(ix->d_uni);
-    if (ix->e_uni) (void)hipEventDestroy(ix->e_uni);
-    ix->d_uni = nullptr;
-    ix->e_uni = nullptr;
-    ix->cap_uni = 0;
-    ix->unitigged = false;
-}
-
-}  // namespace
-
 // Six launches on the caller's stream and no host wait: ends, measure, rings, the scan's two, write (count mode: without the last).  The
 // start list holds 2 * keys entries: a stored k-mer has two sides, a chain's start is an end side, and a ring's least member has none
 int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out,
@@ -1128,20 +1126,16 @@ int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t ca
     dim3 slot_grid, start_grid;
     if (int rc = kidx_launch_blocks(t.slots, 256, "table too large", &slot_grid)) return rc;
     if (int rc = kidx_launch_blocks(cap, 256, "too many starts", &start_grid)) return rc;
-    // Scratch, in words: the counters, the starts, the lengths (two a word), the block sums, the covered bits (64 a word).  It grows to
-    // the size needed: the buffer is given back first, and arena_free waits for the device as hipFree does, so no earlier compaction
-    // still uses it -- the only place the host waits
-    const uint64_t w_lens = (cap + 1) / 2, w_sums = (uint64_t)start_grid.x * KTRIM_COUNTS, w_bits = (t.slots + 63) / 64;
-    if (int rc = kidx_reserve(&ix->d_uni, &ix->cap_uni, KUNITIG_CTRS + cap + w_lens + w_sums + w_bits)) return rc;
+    // Scratch, in words: the counters, the starts, the lengths (two a word), the block sums, the covered bits (64 a word)
+    const uint64_t w_lens = (cap + 1) / 2, w_sums = (uint64_t)start_grid.x * KIDX_COUNTS, w_bits = (t.slots + 63) / 64;
+    if (int rc = kidx_scratch_begin(ix->uni, KUNITIG_CTRS + cap + w_lens + w_sums + w_bits, st)) return rc;
     KunitigScratch s;
-    s.ctr = (unsigned long long*)ix->d_uni;
-    s.starts = ix->d_uni + KUNITIG_CTRS;
+    s.ctr = (unsigned long long*)ix->uni.d;
+    s.starts = ix->uni.d + KUNITIG_CTRS;
     s.lens = (uint32_t*)(s.starts + cap);
     s.sums = s.starts + cap + w_lens;
     s.bits = (uint32_t*)(s.sums + w_sums);
     s.cap = cap;
-    if (!ix->e_uni) KIDX_HIP(hipEventCreate(&ix->e_uni));
-    if (ix->unitigged) KIDX_HIP(hipStreamWaitEvent(st, ix->e_uni, 0));           // (another stream than last time's: the scratch is one)
     KIDX_HIP(hipMemsetAsync(s.ctr, 0, KUNITIG_CTRS * sizeof(uint64_t), st));
     KIDX_HIP(hipMemsetAsync(s.bits, 0, w_bits * sizeof(uint64_t), st));
     const dim3 block(256);
@@ -1164,22 +1158,11 @@ int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t ca
                                    d_word_off_out, d_kmer_base_out, d_report);
             }))
             return rc;
-    KIDX_HIP(hipEventRecord(ix->e_uni, st));
-    ix->unitigged = true;
-    return PG_OK;
+    return kidx_scratch_end(ix->uni, st);
 }
 
 // ---- the corrector on an index cut over ranks ----
 namespace {
-
-void kcor_rows_free(::pg_kindex* ix) {
-    if (ix->d_cor) (void)arena_free(ix->d_cor);
-    if (ix->e_cor) (void)hipEventDestroy(ix->e_cor);
-    ix->d_cor = nullptr;
-    ix->e_cor = nullptr;
-    ix->cap_cor = 0;
-    ix->corrected = false;
-}
 
 // the rounds on the caller's stream (the lead's device is current); d_packed_out already holds the batch or is about to
 int kcor_rows_rounds(::pg_kindex* ix, const KidxBatch& b, const KcorParams& pr, uint64_t* d_packed_out, uint64_t* d_report, hipStream_t st,
@@ -1188,18 +1171,15 @@ int kcor_rows_rounds(::pg_kindex* ix, const KidxBatch& b, const KcorParams& pr, 
     const uint64_t n_seqs = b.n_seqs, cap = std::min<uint64_t>(kcor_round_trials(), n_seqs);
     dim3 grid;
     if (int rc = kidx_batch_blocks(n_seqs, false, &grid)) return rc;
-    // Scratch: the reads' state and bits, the round's trial reads, the claim counter, the trial batch with its readable tail, its rows.
-    // It grows to the largest batch met: the buffer is given back first, and arena_free waits for the device as hipFree does, so no
-    // earlier correction still uses it -- the only wait besides the one a round
+    // Scratch: the reads' state and bits, the round's trial reads, the claim counter, the trial batch with its readable tail, its rows
+    // (where it grows the host waits: the only wait besides the one a round)
     const uint64_t w_state = n_seqs * KCOR_ROWS_STATE_WORDS, w_bits = kcor_rows_bit_words(b.n_kmers, n_seqs), w_trial = kcor_rows_batch_words(cap, K, ix->nw),
                    w_rows = cap * 3 * (uint64_t)K;
-    if (int rc = kidx_reserve(&ix->d_cor, &ix->cap_cor, w_state + w_bits + cap + 1 + w_trial + w_rows)) return rc;
-    uint64_t *d_state = ix->d_cor, *d_bits = d_state + w_state, *d_trial_read = d_bits + w_bits, *d_claimed = d_trial_read + cap, *d_trial = d_claimed + 1,
+    if (int rc = kidx_scratch_begin(ix->cor, w_state + w_bits + cap + 1 + w_trial + w_rows, st)) return rc;
+    uint64_t *d_state = ix->cor.d, *d_bits = d_state + w_state, *d_trial_read = d_bits + w_bits, *d_claimed = d_trial_read + cap, *d_trial = d_claimed + 1,
              *d_trial_rows = d_trial + w_trial;
-    if (!ix->e_cor) KIDX_HIP(hipEventCreate(&ix->e_cor));
     // the copy first -- pad bits and the readable tail with it -- then every read is worked on in its own words of the output
     if (d_packed_out != b.packed) KIDX_HIP(hipMemcpyAsync(d_packed_out, b.packed, b.n_words * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    if (ix->corrected) KIDX_HIP(hipStreamWaitEvent(st, ix->e_cor, 0));            // (another stream than last time's: the scratch is one)
     KidxBatch o = b;
     o.packed = d_packed_out;
     const dim3 block(256);
@@ -1230,9 +1210,7 @@ int kcor_rows_rounds(::pg_kindex* ix, const KidxBatch& b, const KcorParams& pr, 
         hipLaunchKernelGGL(kcor_rows_decide_kernel, trial_grid, block, 0, st, o, K, pr, n_trials, d_trial_read, d_trial_rows, d_state, d_bits, d_report);
         KIDX_HIP(hipGetLastError());
     }
-    KIDX_HIP(hipEventRecord(ix->e_cor, st));
-    ix->corrected = true;
-    return PG_OK;
+    return kidx_scratch_end(ix->cor, st);
 }
 
 }  // namespace
@@ -1241,13 +1219,7 @@ int kcor_device_correct_rows(::pg_kindex* ix, const KidxBatch& b, const KcorPara
                              uint64_t* stats) {
     if (int rc = kidx_set_device(ix->device)) return rc;
     if (!b.n_seqs) return PG_OK;
-    const int rc = kcor_rows_rounds(ix, b, pr, d_packed_out, d_report, (hipStream_t)stream, stats);
-    if (rc) {                                      // no stream is left reading the caller's batch, the scratch or writing its results
-        kidx_sync_ranks(ix);
-        (void)hipSetDevice(ix->device);
-        (void)hipStreamSynchronize((hipStream_t)stream);
-    }
-    return rc;
+    return kidx_settled(ix, kcor_rows_rounds(ix, b, pr, d_packed_out, d_report, (hipStream_t)stream, stats), stream);
 }
 
 int kidx_device_query_times(::pg_kindex* ix, double out[4]) {
@@ -1270,17 +1242,14 @@ int kidx_device_query_times(::pg_kindex* ix, double out[4]) {
 }
 
 void kidx_device_free(::pg_kindex* ix) {
-    if (ix->d_trim || ix->e_trim[0]) {             // (arena_free waits for the device: no trim still uses the scratch)
+    for (KidxScratch* s : {&ix->trim, &ix->cor, &ix->uni}) {
+        if (!s->d && !s->e_end) continue;
         (void)hipSetDevice(ix->device);
-        ktrim_free(ix);
+        kidx_scratch_free(*s);
     }
-    if (ix->d_cor || ix->e_cor) {                  // (the same for the corrector's rounds)
-        (void)hipSetDevice(ix->device);
-        kcor_rows_free(ix);
-    }
-    if (ix->d_uni || ix->e_uni) {                  // (and for the unitigs)
-        (void)hipSetDevice(ix->device);
-        kunitig_free(ix);
+    for (hipEvent_t& e : ix->e_trim) {             // (created behind the trim's scratch: there are none without it)
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
     }
     kidx_sync_ranks(ix);                           // every stream first: the lead's copies read the other ranks' rows
     for (KidxRank& r : ix->ranks) {

@@ -58,17 +58,12 @@ PG_HD uint64_t ktrim_span_row(const uint64_t* row, int nk, int K, uint32_t min_c
 
 // What the scan sums over the reads, all from the span word: kept reads, their output words, their k-mers, and the bases that go --
 // those cut off a kept read and all of a dropped one.  A read's own length is nk + K - 1; a read without k-mers (shorter than K) has
-// no length in a ragged batch's layout and counts as 0 bases, in a uniform batch too
-constexpr int KTRIM_COUNTS = 4;
-struct KtrimCounts {
-    uint64_t c[KTRIM_COUNTS];      // kept, words, k-mers, bases removed
-};
-
-PG_HD KtrimCounts ktrim_counts(uint64_t span, int nk, int K, uint32_t min_len) {
+// no length in a ragged batch's layout and counts as 0 bases, in a uniform batch too.  (KidxCounts: kindex.hpp, the scan's type)
+PG_HD KidxCounts ktrim_counts(uint64_t span, int nk, int K, uint32_t min_len) {
     const uint32_t len = ktrim_len(span);
     const bool kept = len >= min_len;
     const uint64_t given = nk > 0 ? (uint64_t)nk + (uint64_t)K - 1 : 0;
-    return KtrimCounts{{kept ? 1u : 0u, kept ? (uint64_t)((len + 31) / 32) : 0, kept ? (uint64_t)(len - (uint32_t)K + 1) : 0, given - (kept ? len : 0)}};
+    return KidxCounts{{kept ? 1u : 0u, kept ? (uint64_t)((len + 31) / 32) : 0, kept ? (uint64_t)(len - (uint32_t)K + 1) : 0, given - (kept ? len : 0)}};
 }
 
 // Output word q of a kept read: bases start + 32 q .. of the source read rd, a 128-bit funnel of two source words.  The second word is

@@ -19,7 +19,7 @@ template <int NW>
 void ktrim_host_trim(const pg_kindex* ix, const KidxBatch& b, uint32_t min_cov, uint32_t min_len, uint64_t* out_span, uint64_t* packed_out,
                      uint64_t* word_off_out, uint64_t* kmer_base_out, uint64_t* src_out, uint64_t* out_totals) {
     const int K = ix->K;
-    KtrimCounts total{{0, 0, 0, 0}};
+    KidxCounts total{{0, 0, 0, 0}};
     for (uint64_t r = 0; r < b.n_seqs; r++) {
         const KidxSeq q = kidx_seq(b, K, r);
         KtrimRun t = ktrim_run_none();
@@ -27,19 +27,19 @@ void ktrim_host_trim(const pg_kindex* ix, const KidxBatch& b, uint32_t min_cov, 
         const uint64_t span = ktrim_span_word(t, K);
         if (out_span) out_span[r] = span;
         if (!packed_out) continue;
-        const KtrimCounts c = ktrim_counts(span, q.nk, K, min_len);
+        const KidxCounts c = ktrim_counts(span, q.nk, K, min_len);
         if (c.c[0]) {
             word_off_out[total.c[0]] = total.c[1];
             kmer_base_out[total.c[0]] = total.c[2];
             if (src_out) src_out[total.c[0]] = r;
             for (uint64_t w = 0; w < c.c[1]; w++) packed_out[total.c[1] + w] = ktrim_pack_word(q.rd, ktrim_start(span), ktrim_len(span), w);
         }
-        for (int i = 0; i < KTRIM_COUNTS; i++) total.c[i] += c.c[i];
+        for (int i = 0; i < KIDX_COUNTS; i++) total.c[i] += c.c[i];
     }
     if (!packed_out) return;
     kmer_base_out[total.c[0]] = total.c[2];
     for (int i = 0; i < NW + 1; i++) packed_out[total.c[1] + i] = 0;
-    for (int i = 0; i < KTRIM_COUNTS; i++) out_totals[i] = total.c[i];
+    for (int i = 0; i < KIDX_COUNTS; i++) out_totals[i] = total.c[i];
 }
 
 }  // namespace
@@ -63,7 +63,7 @@ extern "C" int pg_kindex_trim(pg_kindex* ix, const uint64_t* packed, uint64_t n_
     if (ix->device >= 0)
         return pg::ktrim_device_trim(ix, b, min_cov, min_len, out_span, packed_out, word_off_out, kmer_base_out, src_out, out_totals, stream);
     if (!n_seqs) {
-        if (packed_out) for (int i = 0; i < pg::KTRIM_COUNTS; i++) out_totals[i] = 0;
+        if (packed_out) for (int i = 0; i < pg::KIDX_COUNTS; i++) out_totals[i] = 0;
         return PG_OK;
     }
     pg::kidx_with_nw(ix->nw, [&](auto nw) {

@@ -32,9 +32,10 @@
 // count the cut unitigs.  When nothing was cut, every solid k-mer lies in exactly one emitted unitig in exactly one orientation.
 //
 // One piece of PG_HD code for the kernels (kindex_kernels.hip: kunitig_*_kernel) and the host twin (kunitig_host.cpp): kunitig_side is
-// the side test, kunitig_chain the one walk that measures (row == null) or writes; both take the lookup as a function of the canonical
-// k-mer that also returns the slot, for the covered bit a slot.  The 32 bases being filled stay in one word and are stored when it is
-// full; reason and length are kept with selects (DESIGN.md §11 on what stores under branches inside such a loop became).
+// the side test -- the walk's step (kwalk.hpp: kwalk_step over a KwalkNode) and the HAIRPIN comparison --, kunitig_chain the one walk
+// that measures (row == null) or writes through the walk's base writer (KwalkText); both take the lookup as a function of the canonical
+// k-mer that also returns the slot, for the covered bit a slot.  Reason and length are kept with selects (DESIGN.md §11 on what stores
+// under branches inside such a loop became).
 #pragma once
 #include "kwalk.hpp"
 
@@ -98,40 +99,21 @@ PG_HD Kmer<NW> kunitig_left_aligned(Kmer<NW> a, int K) {
     return a;
 }
 
-// An oriented k-mer with its word in hand: a = the k-mer, b = its reverse complement, fwd: a is the canonical one
+// the node (kwalk.hpp) of the canonical key c stored at `slot` with word w, as itself (fwd) or as its reverse complement
 template <int NW>
-struct KunitigNode {
-    Kmer<NW> a, b;
-    uint64_t w, slot;
-    bool fwd;
-};
-template <int NW>
-PG_HD Kmer<NW> kunitig_canon(const KunitigNode<NW>& x) { return x.fwd ? x.a : x.b; }
-
-// the node of the canonical key c stored at `slot` with word w, as itself (fwd) or as its reverse complement
-template <int NW>
-PG_HD KunitigNode<NW> kunitig_node(const Kmer<NW>& c, uint64_t w, uint64_t slot, bool fwd, int K) {
+PG_HD KwalkNode<NW> kunitig_node(const Kmer<NW>& c, uint64_t w, uint64_t slot, bool fwd, int K) {
     const Kmer<NW> r = kmer_rc<NW>(c, K);
-    return KunitigNode<NW>{fwd ? c : r, fwd ? r : c, w, slot, fwd};
+    return KwalkNode<NW>{fwd ? c : r, fwd ? r : c, w, slot, fwd};
 }
 
 // The side test: 0 when the right side of the solid node x is open, and then y is the node behind it and base the base that leads
-// there; else the end's reason.  find(ck, slot) = kunitig_probe.  One lookup, none for DEAD_END and BRANCH_OUT
+// there; else the end's reason: the step's, or HAIRPIN behind a good step.  find(ck, slot) = kunitig_probe
 template <int NW, typename Find>
-PG_HD uint32_t kunitig_side(const KunitigNode<NW>& x, int K, const Kmer<NW>& filter, const KunitigParams& pr, Find find, KunitigNode<NW>& y, int& base) {
-    const uint32_t out = kwalk_out_set(x.w, x.fwd, pr.min_arc);
-    if (!kwalk_single(out)) return !out ? KWALK_DEAD_END : KWALK_BRANCH_OUT;
-    base = kwalk_lowest(out);
-    const int first = (int)(x.b.w[NW - 1] & 3) ^ 2;                              // (x's first base: the complement of its reverse complement's last)
-    y.a = x.a;
-    y.b = x.b;
-    kmer_roll<NW>(y.a, y.b, base, K, filter);
-    y.fwd = !kmer_less<NW>(y.b, y.a);
-    y.slot = 0;
-    y.w = find(kunitig_canon<NW>(y), y.slot);
-    const bool solid = kcor_solid_word(y.w, pr.min_cov), joined = kwalk_in_set(y.w, y.fwd, pr.min_arc) == 1u << first;
-    const bool same = kmer_eq<NW>(kunitig_canon<NW>(y), kunitig_canon<NW>(x));
-    return !solid ? KWALK_WEAK_NEXT : !joined ? KWALK_BRANCH_IN : same ? KUNITIG_HAIRPIN : 0;
+PG_HD uint32_t kunitig_side(const KwalkNode<NW>& x, int K, const Kmer<NW>& filter, const KunitigParams& pr, Find find, KwalkNode<NW>& y, int& base) {
+    y = x;
+    const uint32_t reason = kwalk_step<NW>(y, K, filter, pr.min_cov, pr.min_arc, find, base);
+    const bool same = kmer_eq<NW>(kwalk_canon<NW>(y), kwalk_canon<NW>(x));      // (an end before the lookup: y is x, and the reason stands)
+    return reason ? reason : same ? KUNITIG_HAIRPIN : 0;
 }
 
 // What a walk found.  n == 0: the start is not the one its unitig is emitted from (the losing end of a chain; not the least member of a
@@ -145,26 +127,27 @@ struct KunitigWalk {
 // mark(slot) is called for every k-mer of a chain (not of a ring), covered(slot) asked of every k-mer a ring's walk meets.
 // row (may be null): the unitig's kunitig_row_words(n, K) words
 template <int NW, typename Find, typename Mark, typename Covered>
-PG_HD KunitigWalk kunitig_chain(const KunitigNode<NW>& x0, bool cyclic, int K, const KunitigParams& pr, Find find, Mark mark, Covered covered,
+PG_HD KunitigWalk kunitig_chain(const KwalkNode<NW>& x0, bool cyclic, int K, const KunitigParams& pr, Find find, Mark mark, Covered covered,
                                 uint64_t* row) {
     const Kmer<NW> filter = kmer_filter<NW>(K);
-    const Kmer<NW> text = kunitig_left_aligned<NW>(x0.a, K), c0 = kunitig_canon<NW>(x0);
-    KunitigNode<NW> x = x0;
-    uint32_t n = 1, reason = 0, pos = (uint32_t)K;             // pos: bases of the text so far
-    uint64_t cov = kidx_coverage(x0.w), acc = 0;               // acc: the bases of word pos / 32 so far
+    const Kmer<NW> first = kunitig_left_aligned<NW>(x0.a, K), c0 = kwalk_canon<NW>(x0);
+    KwalkNode<NW> x = x0;
+    uint32_t n = 1, reason = 0;
+    uint64_t cov = kidx_coverage(x0.w);
     bool lost = false;
+    KwalkText text{row, 0, (uint32_t)K};          // x0's bases: its full words stored, the partial one in hand
 #pragma unroll
     for (int q = 0; q < NW; q++) {
-        if (row && q < K / 32) row[q] = text.w[q];
-        acc = q == K / 32 ? text.w[q] : acc;
+        if (row && q < K / 32) row[q] = first.w[q];
+        text.acc = q == K / 32 ? first.w[q] : text.acc;
     }
     if (!cyclic) mark(x0.slot);
     for (;;) {
-        KunitigNode<NW> y = x;                     // (an end before the lookup leaves y as it is)
+        KwalkNode<NW> y;                           // (an end before the lookup leaves it x)
         int base = 0;
         reason = kunitig_side<NW>(x, K, filter, pr, find, y, base);
         if (cyclic) {
-            const Kmer<NW> cy = kunitig_canon<NW>(y);
+            const Kmer<NW> cy = kwalk_canon<NW>(y);
             const bool closes = !reason && kmer_eq<NW>(cy, c0);
             // an end: a chain, not a ring; a smaller key: not the least member; a covered k-mer: a chain that was cut; the guard: too long to tell
             lost = !closes && (reason || kmer_less<NW>(cy, c0) || covered(y.slot) || n == pr.max_kmers);
@@ -173,18 +156,13 @@ PG_HD KunitigWalk kunitig_chain(const KunitigNode<NW>& x0, bool cyclic, int K, c
         }
         reason = !reason && n == pr.max_kmers ? KUNITIG_CUT : reason;
         if (reason) break;
-        acc |= (uint64_t)base << (62 - 2 * (int)(pos & 31));
-        pos++;
-        if (!(pos & 31)) {
-            if (row) row[pos / 32 - 1] = acc;
-            acc = 0;
-        }
+        text.append(base);
         cov += kidx_coverage(y.w);
         n++;
         x = y;
         if (!cyclic) mark(x.slot);
     }
-    if (row && (pos & 31)) row[pos / 32] = acc;
+    (void)text.finish();
     // a chain is emitted from the end that is not greater; a cut one from both
     lost = lost || (!cyclic && reason != KUNITIG_CUT && kmer_less<NW>(x.b, x0.a));
     return KunitigWalk{lost ? 0u : n, reason, cov};
@@ -195,22 +173,16 @@ PG_HD KunitigWalk kunitig_chain(const KunitigNode<NW>& x0, bool cyclic, int K, c
 template <int NW, typename Find>
 PG_HD uint32_t kunitig_ends(const Kmer<NW>& c, uint64_t w, uint64_t slot, int K, const KunitigParams& pr, Find find, uint32_t reasons[2]) {
     const Kmer<NW> filter = kmer_filter<NW>(K);
-    const KunitigNode<NW> f = kunitig_node<NW>(c, w, slot, true, K), r = kunitig_node<NW>(c, w, slot, false, K);
-    KunitigNode<NW> y = f;
+    const KwalkNode<NW> f = kunitig_node<NW>(c, w, slot, true, K), r = kunitig_node<NW>(c, w, slot, false, K);
+    KwalkNode<NW> y;
     int base = 0;
     reasons[1] = kunitig_side<NW>(f, K, filter, pr, find, y, base);
     reasons[0] = kunitig_side<NW>(r, K, filter, pr, find, y, base);
     return (reasons[0] ? 1u : 0u) | (reasons[1] ? 2u : 0u);
 }
 
-// the canonical key stored in a slot
-template <int NW>
-PG_HD Kmer<NW> kunitig_slot_key(const uint64_t* sl) {
-    Kmer<NW> k;
-#pragma unroll
-    for (int q = 0; q < NW; q++) k.w[q] = sl[q];
-    return k;
-}
+// what a start of n k-mers (0: the copy that is not emitted) adds to the scan: kept, words, k-mers
+PG_HD KidxCounts kunitig_counts(uint32_t n, int K) { return KidxCounts{{n ? 1ull : 0ull, n ? kunitig_row_words(n, K) : 0ull, n, 0}}; }
 
 // The caller's side of the device engine (kindex_kernels.hip), asynchronous on `stream`: count mode when d_packed_out is null
 int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out,

@@ -32,7 +32,7 @@ void kunitig_host_unitigs(const pg_kindex* ix, const KunitigParams& pr, uint64_t
     auto solid_at = [&](uint64_t e) { return tab[e * SW + NW + 1] != KIDX_EMPTY && kcor_solid_word(tab[e * SW + NW], pr.min_cov); };
     auto node_of = [&](uint64_t start) {
         const uint64_t* sl = tab + kunitig_start_slot(start) * SW;
-        return kunitig_node<NW>(kunitig_slot_key<NW>(sl), sl[NW], kunitig_start_slot(start), kunitig_start_fwd(start), K);
+        return kunitig_node<NW>(kidx_record_key<NW>(sl), sl[NW], kunitig_start_slot(start), kunitig_start_fwd(start), K);
     };
     uint64_t solid = 0, cyclic = 0, cut = 0;
     // 1. the ends: every end side of a solid k-mer starts a walk
@@ -40,7 +40,7 @@ void kunitig_host_unitigs(const pg_kindex* ix, const KunitigParams& pr, uint64_t
         if (!solid_at(e)) continue;
         solid++;
         uint32_t reasons[2];
-        const uint32_t ends = kunitig_ends<NW>(kunitig_slot_key<NW>(tab + e * SW), tab[e * SW + NW], e, K, pr, find, reasons);
+        const uint32_t ends = kunitig_ends<NW>(kidx_record_key<NW>(tab + e * SW), tab[e * SW + NW], e, K, pr, find, reasons);
         for (int side = 0; side < 2; side++)
             if (ends >> side & 1) starts.push_back(kunitig_start(e, side == 0, reasons[side]));
     }
@@ -61,12 +61,10 @@ void kunitig_host_unitigs(const pg_kindex* ix, const KunitigParams& pr, uint64_t
         cyclic++;
     }
     // 4. the scan and the decision
-    uint64_t unitigs = 0, words = 0, kmers = 0;
-    for (uint32_t n : lens) {
-        unitigs += n ? 1 : 0;
-        words += n ? kunitig_row_words(n, K) : 0;
-        kmers += n;
-    }
+    KidxCounts total{{0, 0, 0, 0}};
+    for (uint32_t n : lens)
+        for (int i = 0; i < KIDX_COUNTS; i++) total.c[i] += kunitig_counts(n, K).c[i];
+    const uint64_t unitigs = total.c[0], words = total.c[1], kmers = total.c[2];
     const uint64_t tail = (uint64_t)ix->nw + 1;
     const bool overflow = packed_out && (unitigs > cap_unitigs || words + tail > cap_words);
     totals[KUNITIG_T_UNITIGS] = unitigs;

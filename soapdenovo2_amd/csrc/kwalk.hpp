@@ -34,8 +34,11 @@
 //   report[2 v]      length in bits 31:0, stop reason (1..8) in bits 39:32
 //   report[2 v + 1]  the sum of coverage of the appended k-mers
 //
-// One piece of PG_HD code for the kernel (kindex_kernels.hip: kwalk_kernel) and the host twin (kwalk_host.cpp): kwalk_one takes the lookup
-// as a function of the canonical k-mer.  The 32 bases being filled stay in one word and are stored when it is full; stop reason and
+// One piece of PG_HD code for the kernel (kindex_kernels.hip: kwalk_kernel) and the host twin (kwalk_host.cpp), and the two pieces the
+// unitigs (kunitig.hpp) share with the walk: kwalk_step, step 2 above up to BRANCH_IN -- what follows a good step is the caller's: the
+// walk compares with its start (LOOP), the unitigs with x (HAIRPIN) and, for rings, with their first k-mer -- and KwalkText, the base
+// writer.  The lookup is a function find(ck, slot&) of the canonical k-mer that may also say where the key lies; the walk's callers
+// pass one that leaves the slot alone.  The 32 bases being filled stay in one word and are stored when it is full; stop reason and
 // length are kept with selects (DESIGN.md §11 on what stores under branches inside such a loop became).
 #pragma once
 #include "kcorrect.hpp"
@@ -79,52 +82,85 @@ PG_HD uint32_t kwalk_in_set(uint64_t w, bool fwd, uint32_t min_arc) {
 PG_HD int kwalk_lowest(uint32_t m) { return m & 1u ? 0 : m & 2u ? 1 : m & 4u ? 2 : 3; }
 PG_HD bool kwalk_single(uint32_t m) { return m != 0 && (m & (m - 1)) == 0; }
 
+// An oriented k-mer with its word in hand: a = the k-mer, b = its reverse complement (KcorCursor's pair: both roll with kmer_roll, the
+// canonical key is the smaller), fwd: a is the canonical one, slot: what the lookup said of where the key lies
+template <int NW>
+struct KwalkNode {
+    Kmer<NW> a, b;
+    uint64_t w, slot;
+    bool fwd;
+};
+template <int NW>
+PG_HD Kmer<NW> kwalk_canon(const KwalkNode<NW>& x) { return x.fwd ? x.a : x.b; }
+
+// The graph step, in place: 0 when the solid node x has one arc out, to a solid y, and that arc is the only one into y; else the first
+// of KWALK_DEAD_END, KWALK_BRANCH_OUT, KWALK_WEAK_NEXT, KWALK_BRANCH_IN that applies.  DEAD_END and BRANCH_OUT leave x as it is and
+// look nothing up; behind the one lookup x is y whatever is returned, and base the base that led there.  A caller that needs x
+// afterwards steps a copy (kunitig.hpp: kunitig_side)
+template <int NW, typename Find>
+PG_HD uint32_t kwalk_step(KwalkNode<NW>& x, int K, const Kmer<NW>& filter, uint32_t min_cov, uint32_t min_arc, Find find, int& base) {
+    const uint32_t out = kwalk_out_set(x.w, x.fwd, min_arc);
+    if (!kwalk_single(out)) return !out ? KWALK_DEAD_END : KWALK_BRANCH_OUT;
+    base = kwalk_lowest(out);
+    const int first = (int)(x.b.w[NW - 1] & 3) ^ 2;                              // (x's first base: the complement of its reverse complement's last)
+    kmer_roll<NW>(x.a, x.b, base, K, filter);
+    x.fwd = !kmer_less<NW>(x.b, x.a);
+    x.slot = 0;
+    x.w = find(kwalk_canon<NW>(x), x.slot);
+    const bool solid = kcor_solid_word(x.w, min_cov), joined = kwalk_in_set(x.w, x.fwd, min_arc) == 1u << first;
+    return !solid ? KWALK_WEAK_NEXT : !joined ? KWALK_BRANCH_IN : 0;
+}
+
+// The base writer: a text of `pos` bases so far in the words of row (may be null: nothing is stored), the bases of word pos / 32 in acc
+struct KwalkText {
+    uint64_t* row;
+    uint64_t acc;
+    uint32_t pos;
+    PG_HD void append(int base) {
+        acc |= (uint64_t)base << (62 - 2 * (int)(pos & 31));
+        pos++;
+        if (!(pos & 31)) {
+            if (row) row[pos / 32 - 1] = acc;
+            acc = 0;
+        }
+    }
+    // the last word where it is a partial one; the words of the text
+    PG_HD uint64_t finish() {
+        if (row && (pos & 31)) row[pos / 32] = acc;
+        return ((uint64_t)pos + 31) / 32;
+    }
+};
+
 // One walk.  rd / nk: the sequence's words and k-mers; second: walk 2r + 1 (from the reverse complement of the first k-mer) and not walk 2r
-// (from the last one).  find(ck) = the index's word of canonical k-mer ck, 0 when it has none.  row (may be null): the walk's
+// (from the last one).  find(ck, slot) = the index's word of canonical k-mer ck, 0 when it has none.  row (may be null): the walk's
 // kwalk_row_words(max_ext) words; rep (may be null): its two report words
 template <int NW, typename Find>
 PG_HD void kwalk_one(const uint64_t* rd, int nk, int K, bool second, const KwalkParams& pr, Find find, uint64_t* row, uint64_t* rep) {
-    const uint64_t row_words = kwalk_row_words(pr.max_ext);
-    uint32_t len = 0, reason = KWALK_NO_KMER;
-    uint64_t cov = 0, acc = 0;                     // acc: the bases of word len / 32 so far
+    uint32_t reason = KWALK_NO_KMER;
+    uint64_t cov = 0;
+    KwalkText text{row, 0, 0};
     if (nk > 0) {
         const Kmer<NW> filter = kmer_filter<NW>(K);
-        // (a, b) = the oriented k-mer and its reverse complement (KcorCursor's pair): both roll with kmer_roll, the canonical key is the smaller
         const Kmer<NW> seed = read_kmer<NW>(rd, second ? 0 : nk - 1, K, filter), seed_rc = kmer_rc<NW>(seed, K);
-        Kmer<NW> a = second ? seed_rc : seed, b = second ? seed : seed_rc;
-        bool fwd = !kmer_less<NW>(b, a);
-        const Kmer<NW> start = fwd ? a : b;
-        uint64_t w = find(start);
-        reason = kcor_solid_word(w, pr.min_cov) ? 0 : KWALK_SEED_WEAK;
+        KwalkNode<NW> x{second ? seed_rc : seed, second ? seed : seed_rc, 0, 0, false};
+        x.fwd = !kmer_less<NW>(x.b, x.a);
+        const Kmer<NW> start = kwalk_canon<NW>(x);
+        x.w = find(start, x.slot);
+        reason = kcor_solid_word(x.w, pr.min_cov) ? 0 : KWALK_SEED_WEAK;
         while (!reason) {
-            const uint32_t out = kwalk_out_set(w, fwd, pr.min_arc);
-            reason = !out ? KWALK_DEAD_END : !kwalk_single(out) ? KWALK_BRANCH_OUT : 0;
+            int base = 0;
+            reason = kwalk_step<NW>(x, K, filter, pr.min_cov, pr.min_arc, find, base);
+            reason = reason ? reason : kmer_eq<NW>(kwalk_canon<NW>(x), start) ? KWALK_LOOP : 0;
             if (reason) break;
-            const int base = kwalk_lowest(out), first = (int)(b.w[NW - 1] & 3) ^ 2;   // (x's first base: the complement of its reverse complement's last)
-            kmer_roll<NW>(a, b, base, K, filter);
-            fwd = !kmer_less<NW>(b, a);
-            const Kmer<NW> cy = fwd ? a : b;
-            w = find(cy);
-            const bool solid = kcor_solid_word(w, pr.min_cov), joined = kwalk_in_set(w, fwd, pr.min_arc) == 1u << first, loop = kmer_eq<NW>(cy, start);
-            reason = !solid ? KWALK_WEAK_NEXT : !joined ? KWALK_BRANCH_IN : loop ? KWALK_LOOP : 0;
-            if (reason) break;
-            acc |= (uint64_t)base << (62 - 2 * (int)(len & 31));
-            cov += kidx_coverage(w);
-            len++;
-            if (!(len & 31)) {
-                if (row) row[len / 32 - 1] = acc;
-                acc = 0;
-            }
-            reason = len == pr.max_ext ? KWALK_MAX_EXT_REACHED : 0;
+            text.append(base);
+            cov += kidx_coverage(x.w);
+            reason = text.pos == pr.max_ext ? KWALK_MAX_EXT_REACHED : 0;
         }
     }
-    if (row) {
-        uint64_t q = len / 32;                     // the words before it are full and stored
-        if (len & 31) row[q++] = acc;
-        for (; q < row_words; q++) row[q] = 0;
-    }
+    if (row)
+        for (uint64_t q = text.finish(), row_words = kwalk_row_words(pr.max_ext); q < row_words; q++) row[q] = 0;
     if (rep) {
-        rep[0] = kwalk_report_word(len, reason);
+        rep[0] = kwalk_report_word(text.pos, reason);
         rep[1] = cov;
     }
 }

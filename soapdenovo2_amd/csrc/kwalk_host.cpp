@@ -17,7 +17,7 @@ template <int NW>
 void kwalk_host_walk(const pg_kindex* ix, const KidxBatch& b, const KwalkParams& pr, uint64_t* out_ext, uint64_t* out_report) {
     const int K = ix->K;
     const uint64_t row_words = kwalk_row_words(pr.max_ext);
-    auto find = [ix](const Kmer<NW>& ck) { return kidx_host_find<NW>(ix, ck); };
+    auto find = [ix](const Kmer<NW>& ck, uint64_t&) { return kidx_host_find<NW>(ix, ck); };
     for (uint64_t r = 0; r < b.n_seqs; r++) {
         const KidxSeq q = kidx_seq(b, K, r);
         for (uint64_t v = 2 * r; v < 2 * r + 2; v++)

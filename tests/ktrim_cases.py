@@ -232,6 +232,47 @@ def check_flavour(K, mer127, device, batches=BATCHES):
         t.close()
 
 
+# ---- batches of 65 536 and 65 537 reads: 256 blocks of 256 are exactly one round of the scan over the blocks' sums, the 257th block is
+# the first of its second round ----
+ROUND = 256 * 256
+
+
+def check_rounds(device, twin=None):
+    """K = 13, uniform reads of K + 3 bases, each one of two templates by a seeded random bit: a stretch of the genome that is solid
+    throughout (kept whole) or the one whose four k-mers all hold the base at P_BELOW_MIN (coverage MIN_COV - 1: dropped).  Every
+    output is then a cumulative sum of the bit vector, and the output words are the kept template's word repeated."""
+    K, L, nw, nk = 13, 16, 2, 4
+    g = C.genome(K)
+    t = Trimmer(K, False, device)
+    h = Trimmer(K, False, twin, model=t.model) if twin is not None else None
+    try:
+        keep, drop = g[C.PLAIN:C.PLAIN + L], g[C.P_BELOW_MIN - 3:C.P_BELOW_MIN - 3 + L]
+        assert model_span(t.model, keep) == (0, L) and T.solid_flags(t.model, drop, MIN_COV) == [False] * nk
+        w_keep, w_drop = pack([keep], K, nw, True)[0][0], pack([drop], K, nw, True)[0][0]
+        w_out = w_keep & ~np.uint64(0xFFFFFFFF)                                # (16 bases: the low half of the word is pad)
+        for n in (ROUND, ROUND + 1):
+            bits = np.random.default_rng(600 + n).integers(0, 2, size=n).astype(bool)
+            words = np.concatenate([np.where(bits, w_keep, w_drop), np.full(nw + 1, ONES)]).astype(np.uint64)
+            before = (np.cumsum(bits) - bits).astype(np.uint64)               # the kept reads in front of each read
+            kept = int(bits.sum())
+            assert 0 < kept < n
+            want = [np.where(bits, np.uint64(L << 32), np.uint64(0)), np.concatenate([np.full(kept, w_out), np.zeros(nw + 1, dtype=np.uint64)]),
+                    before[bits], np.concatenate([before[bits] * np.uint64(nk), [np.uint64(kept * nk)]]), np.flatnonzero(bits).astype(np.uint64),
+                    np.array([kept, kept, kept * nk, (n - kept) * L], dtype=np.uint64)]
+            sizes = [n, kept + nw + 1, kept, kept + 1, kept, 4]
+            for who in (t, h):
+                if who is None:
+                    continue
+                got = [who.down(o) for o in who.ix.trim_uniform(who.up(words.copy()), n, L, MIN_COV, K + 1)]
+                for name, a, b, m in zip(("spans", "packed_out", "word_off_out", "kmer_base_out", "src_out", "totals"), got, want, sizes):
+                    assert (a[:m] == b).all(), "%d reads: %s differs from the cumulative sums of the bit vector" % (n, name)
+                assert not got[1][kept + nw + 1:].any(), "%d reads: words behind the tail were written" % n
+    finally:
+        t.close()
+        if h is not None:
+            h.close()
+
+
 def check_ranks(K, mer127, devices_of):
     """The index cut over 1, 2, 3 and 8 ranks gives the single table's words (and the model's)."""
     reads = [c.read for c in cases(K)] + batch_of(K, 257, 7)

@@ -325,6 +325,66 @@ def check_noisy(K, mer127, device, twin=None):
             h.close()
 
 
+# ---- 32 769 isolated k-mers: 65 538 starts, the start list's capacity 2 * keys exactly, in 257 blocks of 256 -- the 257th is the first
+# block of the second round of the scan over the blocks' sums ----
+ISOLATED, ISOLATED_K, ISOLATED_MIN_COV = 128 * 256 + 1, 31, 2
+
+
+@functools.lru_cache(maxsize=None)
+def isolated():
+    """(records, the model, the model's unitigs as a sorted list of (key, left, right, coverage sum)): distinct random canonical 31-mers
+    with a coverage of ISOLATED_MIN_COV .. 255 and every arc counter zero.  Built once and shared, and never written to."""
+    K, n = ISOLATED_K, ISOLATED
+    rng = np.random.default_rng(4900)
+    two, three = np.uint64(2), np.uint64(3)
+    x = rng.integers(0, 1 << 62, size=n + 64, dtype=np.uint64)
+    back = np.zeros_like(x)
+    for i in range(K):                                                         # (a step a base, over all keys at once)
+        back = (back << two) | (((x >> np.uint64(2 * i)) & three) ^ two)
+    keys = np.unique(np.minimum(x, back))
+    assert keys.size >= n
+    keys = rng.permutation(keys)[:n]
+    records = np.zeros((n, 4), dtype=np.uint64)
+    records[:, 1] = keys
+    records[:, 2] = rng.integers(ISOLATED_MIN_COV, 256, size=n).astype(np.uint64) << np.uint64(24)
+    records[:, 3] = np.arange(n, dtype=np.uint64)
+    model = M.Model.from_records(records, K, 2)
+    want, n_cut = U.unitigs(model, ISOLATED_MIN_COV, 1)
+    assert n_cut == 0 and all(len(t) == K for t, _, _, _ in want)
+    return records, model, sorted((W.value(t), l, r, c) for t, l, r, c in want)
+
+
+def check_isolated(device, twin=None):
+    """The count call and the full call over the isolated k-mers: the totals, the layout, and -- as sorted lists -- the unitigs the
+    construction dictates (every key as it is, K bases, both reasons DEAD_END, its own coverage), the model's and the host twin's."""
+    K, n, tail = ISOLATED_K, ISOLATED, 3
+    records, model, want = isolated()
+    D = U.DEAD_END
+    assert want == sorted((int(k), D, D, int(c) >> 24) for k, c in zip(records[:, 1], records[:, 2]))
+    totals = [n, n + tail, n * K, n, n, 0, 0, 0]
+
+    def run(dev):
+        w = Compactor(records, K, False, dev, model=model)
+        try:
+            assert w.count(ISOLATED_MIN_COV, 1, MAXK) == totals
+            outs = w.outputs(n, n + tail)
+            assert w.call(ISOLATED_MIN_COV, 1, MAXK, n, n + tail, *outs) == 0, api.lib().pg_last_error()
+            packed, word_off, kmer_base, report, tot = (w.down(a) for a in outs)
+        finally:
+            w.close()
+        assert [int(v) for v in tot] == totals
+        assert (word_off == np.arange(n + 1, dtype=np.uint64)).all() and (kmer_base == np.arange(n + 1, dtype=np.uint64)).all()
+        assert packed.size == n + tail and not packed[n:].any() and not (packed[:n] & np.uint64(3)).any()
+        f = api.unitig_fields(report)
+        assert (f["len"] == K).all()
+        return sorted(zip((packed[:n] >> np.uint64(2)).tolist(), f["left_code"].tolist(), f["right_code"].tolist(), f["coverage_sum"].tolist()))
+
+    got = run(device)
+    assert got == want, "the unitigs differ from the model's"
+    if twin is not None:
+        assert run(twin) == got, "the device differs from the host twin"
+
+
 def check_capacities(K, mer127, device):
     """Capacities one short in unitigs and one short in words: the overflow flag, and nothing but the totals written; exact ones: the
     result; each nullable output null in turn: the others as before."""

@@ -32,6 +32,13 @@ def test_cut_over_ranks_gives_the_single_tables_words(flavour):
     E.check_ranks(flavour[0], flavour[1], lambda n: (0,) * n)
 
 
+def test_batches_of_one_scan_round_and_one_block_more():
+    """65 536 reads are exactly one round of ktrim_scan_sums_kernel (256 blocks of 256), 65 537 put one block into its second round,
+    which takes the first round's carry: the kernels against the cumulative sums of the keep / drop bit vector and against the host
+    twin (tests/ktrim_cases.py: check_rounds)."""
+    E.check_rounds(0, twin=-1)
+
+
 @pytest.fixture(scope="module")
 def simulated_records(tmp_path_factory):
     return oracle_records(C.simulated()[0], C.SIM_K, 8, prefix=str(tmp_path_factory.mktemp("ktrim") / "o"))[0]

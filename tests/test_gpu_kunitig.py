@@ -53,6 +53,13 @@ def test_api_and_round_trip(flavour):
     G.check_api(flavour[0], flavour[1], 0)
 
 
+def test_isolated_kmers_fill_the_start_list():
+    """32 769 isolated solid 31-mers: 65 538 starts, the start list's capacity 2 * keys exactly, in 257 blocks of 256 -- the 257th is
+    scanned in the second round of kunitig_scan_sums_kernel, with the first round's carry.  The count call and the full call against
+    the closed form, the model and the host twin (tests/kunitig_cases.py: check_isolated)."""
+    G.check_isolated(0, twin=-1)
+
+
 def test_two_compactions_back_to_back_on_one_stream():
     """Two full calls with different thresholds queued one after the other with no host wait in between -- the second reuses the index's
     scratch behind the first's end --, their outputs read afterwards: each is its own model's."""

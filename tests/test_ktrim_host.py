@@ -29,6 +29,13 @@ def test_cut_over_ranks_gives_the_single_tables_words(flavour):
     E.check_ranks(flavour[0], flavour[1], lambda n: (-1,) * n)
 
 
+def test_batches_of_one_scan_round_and_one_block_more():
+    """65 536 reads (256 blocks of 256: exactly one round of the device's scan over the blocks' sums) and 65 537 (one block in the
+    second round), K = 13, each read kept whole or dropped by a seeded random bit: totals, src_out, word_off_out and kmer_base_out are
+    cumulative sums of the bit vector and packed_out is the kept template's word repeated (tests/ktrim_cases.py: check_rounds)."""
+    E.check_rounds(-1)
+
+
 def test_argument_errors():
     K = 31
     t = E.Trimmer(K, False, -1)

@@ -49,6 +49,13 @@ def test_api_and_round_trip(flavour):
     G.check_api(flavour[0], flavour[1], -1)
 
 
+def test_isolated_kmers_fill_the_start_list():
+    """32 769 isolated solid 31-mers (distinct random keys, every arc counter zero): 65 538 starts, which is the start list's capacity
+    2 * keys exactly -- 257 blocks of 256, one more than a round of the device's scan over the blocks' sums.  The count call and the
+    full call give 32 769 unitigs of K bases, both reasons DEAD_END, no ring, nothing cut: the model's, as sorted lists."""
+    G.check_isolated(-1)
+
+
 # ---- the host twin under the sanitizers, in a program of its own ----
 def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     """tests/kunitig_asan.cpp: both flavours, a linear genome, a ring and isolated k-mers in one index, the output buffers on the heap at
