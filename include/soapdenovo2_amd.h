@@ -568,6 +568,25 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       walk chases its lookups in one table); nothing is written then.  Device memory of the index's device,
  *                       asynchronous on `stream`; the index keeps scratch of 3 words a stored k-mer and a bit a slot, which grows
  *                       to the size needed, and only that growth waits.  Host memory for a host-twin index.
+ *   pg_kindex_clip_tips one round of tip clipping on the graph of the index (csrc/ktip.hpp).  Solid, the arc sets, the side test, the end
+ *                       reasons, min_cov (1..255) and min_arc (1..63) are pg_kindex_unitigs'.  A tip candidate is a linear unitig
+ *                       x0 -> .. -> x(n-1) oriented so that the left side of x0 is free (reason 3 dead end or 5 weak next), the right
+ *                       side of x(n-1) has reason 6 branch in, and n <= max_tip (1 .. 2^16 k-mers); every other pair of reasons is
+ *                       none.  y, the junction, is the solid k-mer behind the attached side as the step reaches it, a the first base
+ *                       of x(n-1), and c_t y's 6-bit in-counter for a (left counter a where y is its canonical form, else right
+ *                       counter a ^ 2).  The candidate is minor, and clipped, iff c_t is strictly smaller than the largest of y's
+ *                       other three in-counters: raw counters, ties kept.  The round decides over the index as it stood when it
+ *                       began, then applies: the cnt word of every k-mer of every minor tip becomes 0 -- the key stays in its slot, so
+ *                       every other key is found as before, and the k-mer itself reads as absent to every operator --, and in y's
+ *                       word the one counter c_t becomes 0.  Nothing else is written: an arc below min_arc that points at a clipped
+ *                       k-mer from elsewhere stays, so use a clipped index at the same or higher thresholds.  The records the index
+ *                       was built from are not touched: build it again to have the tips back.  Clipping can make a new tip, so call
+ *                       rounds until out_totals[0] == 0.  out_totals[4], always written: [0] tips clipped, [1] k-mers removed,
+ *                       [2] solid k-mers before the round, [3] candidates kept because not minor.
+ *                       PG_EINVAL: a threshold or max_tip out of range, out_totals null; PG_ESTATE: an index cut over ranks (a walk
+ *                       chases its lookups in one table); nothing is written then and the index is untouched.  Device memory of the
+ *                       index's device, asynchronous on `stream`, no host wait; the scratch is pg_kindex_unitigs'.  Host memory for a
+ *                       host-twin index.  Not done: a cut index, bubbles, isolated short unitigs.
  *   pg_kindex_correct_rows       pg_kindex_correct on any index, by rounds over merged rows (csrc/kcorrect_rows.hpp).  The batch, its
  *                       tail, n_words and n_kmers are pg_kindex_query_words' and pg_kindex_trim's; packed_out, out_report, in-place
  *                       use, the report word, the rule and the argument errors are pg_kindex_correct's, and so is the result, bit for
@@ -611,6 +630,7 @@ int pg_kindex_walk(pg_kindex *ix, const uint64_t *packed, uint64_t n_words, cons
 int pg_kindex_unitigs(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_kmers, uint64_t cap_unitigs, uint64_t cap_words,
                       uint64_t *packed_out, uint64_t *word_off_out, uint64_t *kmer_base_out, uint64_t *out_report, uint64_t *out_totals,
                       void *stream);
+int pg_kindex_clip_tips(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_tip, uint64_t *out_totals, void *stream);
 int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
 void pg_kindex_destroy(pg_kindex *ix);
 uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */

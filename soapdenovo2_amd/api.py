@@ -189,6 +189,7 @@ def lib() -> C.CDLL:
     L.pg_kindex_walk.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u64p,
                                  C.c_void_p]
     L.pg_kindex_unitigs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p, u64p, C.c_void_p]
+    L.pg_kindex_clip_tips.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
     L.pg_kindex_info.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_destroy.argtypes = [C.c_void_p]
     L.pg_kindex_destroy.restype = None
@@ -224,7 +225,7 @@ EXPORTED_SYMBOLS = [
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
     "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times", "pg_kindex_correct_rows", "pg_kindex_correct_rows_stats",
-    "pg_kindex_walk", "pg_kindex_unitigs",
+    "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_clip_tips",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
@@ -940,6 +941,19 @@ def unitig_fields(report) -> dict:
             "coverage_sum": w[:, 1].astype(np.int64)}
 
 
+# The tips (pg_kindex_clip_tips).  TIP_MAX_BOUND is the most max_tip the entry takes; its default is 2 K, the reference's tip length.
+TIP_MAX_BOUND = 1 << 16
+TIP_TOTALS_FIELDS = ["tips", "kmers", "solid", "kept"]
+
+
+def tip_fields(totals) -> dict:
+    """A round's totals (pg_kindex_clip_tips) by name: `tips` clipped, `kmers` removed, `solid` k-mers before the round, and the
+    candidates `kept` because they were not minor.  Takes a numpy array or a torch tensor of 4 words."""
+    if not isinstance(totals, np.ndarray):
+        totals = totals.cpu().numpy()
+    return {k: int(v) for k, v in zip(TIP_TOTALS_FIELDS, np.ascontiguousarray(totals).view(np.uint64))}
+
+
 def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
     """pg_host_kindex_bytes: the table an index of n_records k-mers cuts (no GPU)."""
     return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
@@ -1237,6 +1251,25 @@ class KmerIndex:
         if int(t[7]):
             raise PgError("KmerIndex.unitigs: the full call needs more than the count call said")
         return Unitigs(packed[:words], word_off[:n + 1], kmer_base[:n + 1], report[:2 * n], t)
+
+    def clip_tips(self, min_cov: int, min_arc: int, max_tip=None, max_rounds: int = 64) -> list:
+        """Minor tips clipped from the index's graph, in place (pg_kindex_clip_tips): a tip is a chain of at most max_tip k-mers
+        (default 2 K) that is free -- a dead end or a weak successor -- on one side and joins a k-mer with several arcs in on the
+        other, and it is minor, and removed, when its arc into that k-mer has a strictly smaller counter than the strongest of the
+        others.  A removed k-mer reads as absent from then on, to every operator; the records the index came from are not touched.
+        Clipping a tip can turn the path it hung on into a tip, so rounds are called until one clips nothing or max_rounds is reached;
+        each round's totals are read once -- the one wait for the GPU a round.  Returns the rounds' totals, a list of numpy arrays of
+        TIP_TOTALS_FIELDS (tip_fields names them), the round that clipped nothing included.  Use the clipped index at the same or
+        higher thresholds.  An index cut over ranks is refused."""
+        max_tip = 2 * self.K if max_tip is None else max_tip
+        rounds = []
+        while len(rounds) < max_rounds:
+            totals = np.zeros(4, dtype=np.uint64) if self.device < 0 else self.torch.zeros(4, dtype=self.torch.int64, device=f"cuda:{self.device}")
+            _check(lib().pg_kindex_clip_tips(self.h, min_cov, min_arc, max_tip, self._ptr(totals), self._stream()), "pg_kindex_clip_tips")
+            rounds.append(totals if self.device < 0 else totals.cpu().numpy().view(np.uint64))
+            if not int(rounds[-1][0]):
+                break
+        return rounds
 
     def info(self) -> dict:
         out = np.zeros(4, dtype=np.uint64)

@@ -67,6 +67,15 @@
 //                              kunitig_scan_sums_kernel (the totals, the overflow decision the write kernel obeys, the last offsets and
 //                              the tail's zero words)
 //   kunitig_write_kernel       a lane per start: its offsets from the scan, and a kept start walks once more into its row
+// The tips (ktip.hpp; pg_kindex_clip_tips): one round, four launches on the caller's stream over the unitigs' scratch
+//   kunitig_ends_kernel        as above: the start list and the solid count
+//   ktip_decide_kernel         a lane per start: one whose left side is not free ends at once, the others walk at most max_tip k-mers
+//                              (ktip_decide) and, at a BRANCH_IN, test the junction's word; n into the length list for a minor tip, else
+//                              0; the candidates kept counted a wave at a time.  Reads the table only
+//   ktip_apply_kernel          a lane per start with n != 0: ktip_apply -- a plain store of 0 over each of its n k-mers' words, one
+//                              atomicAnd on the 32-bit half of the junction's word that holds the tip's in-counter (the one word two lanes
+//                              may write together).  Tips and k-mers counted a wave at a time
+//   ktip_totals_kernel         the four totals from the counters
 // The corrector on an index cut over ranks (kcorrect_rows.hpp; pg_kindex_correct_rows): rounds of plan, query, decide on the
 // caller's stream, every query kidx_query_ranks, and the host reads the round's trial count back once a round
 //   kcor_rows_begin_kernel     a lane per read over its row of the read as given: weak count, anchor, first weak k-mer behind it, the
@@ -92,6 +101,7 @@
 #include "kcorrect.hpp"
 #include "kcorrect_rows.hpp"
 #include "kindex.hpp"
+#include "ktip.hpp"
 #include "ktrim.hpp"
 #include "kunitig.hpp"
 #include "kwalk.hpp"
@@ -550,6 +560,60 @@ __global__ __launch_bounds__(256) void kunitig_write_kernel(const uint64_t* __re
         report[2 * u] = kunitig_report_word(own.c[2] + (uint64_t)K - 1, left, w.reason);
         report[2 * u + 1] = w.cov;
     }
+}
+
+// ---- the tips: ends (the unitigs' kernel), decide, apply, the totals (ktip.hpp) ----
+// A round's counters lie behind the unitigs' in the same scratch: tips clipped, k-mers removed, candidates kept
+enum : int { KTIP_C_TIPS = 5, KTIP_C_KMERS = 6, KTIP_C_KEPT = 7 };
+static_assert(KTIP_C_KEPT < KUNITIG_CTRS && KTIP_C_TIPS > KUNITIG_C_GO, "the tips' counters lie in the scratch, behind the unitigs'");
+
+// a lane per start: the decision, n into the length list for a minor tip and 0 for every other start.  Only reads the table
+template <int NW>
+__global__ __launch_bounds__(256) void ktip_decide_kernel(const uint64_t* __restrict__ tab, uint64_t mask, int K, KtipParams pr, KunitigScratch s) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    KtipDecision d{0, false, false};
+    if (i < kunitig_n_starts(s)) {
+        const uint64_t start = s.starts[i];
+        const uint32_t left = kunitig_start_reason(start);
+        if (ktip_free(left))                       // (any other start ends at once: its slot is not even read)
+            d = ktip_decide<NW>(kunitig_start_node<NW>(tab, start, K), left, K, pr,
+                                [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); });
+        s.lens[i] = d.minor ? d.n : 0;
+    }
+    const uint64_t wave_kept = __ballot(d.candidate && !d.minor);                 // (every lane of the wave is here)
+    if ((threadIdx.x & 63) == 0 && wave_kept) atomicAdd(s.ctr + KTIP_C_KEPT, (unsigned long long)__popcll(wave_kept));
+}
+
+// a lane per start with n != 0: its n k-mers' words zeroed with plain stores -- they are in no other tip --, its counter taken out of the
+// junction's word with an atomicAnd on the 32-bit half that holds it: another tip's lane may clear another counter of that half
+template <int NW>
+__global__ __launch_bounds__(256) void ktip_apply_kernel(uint64_t* tab, uint64_t mask, int K, KtipParams pr, KunitigScratch s) {
+    constexpr int SW = map_slot_words<NW>();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n = i < kunitig_n_starts(s) ? s.lens[i] : 0;
+    if (n)
+        ktip_apply<NW>(kunitig_start_node<NW>(tab, s.starts[i], K), n, K, pr,
+                       [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); },
+                       [tab](uint64_t slot) { tab[slot * SW + NW] = 0; },
+                       [tab](uint64_t slot, bool fwd, int a) {
+                           atomicAnd((unsigned int*)(tab + slot * SW + NW) + ktip_in_half(fwd), ktip_keep_mask(fwd, a));
+                       });
+    const uint64_t wave_tips = __ballot(n != 0);                                 // (every lane of the wave is here)
+    uint32_t wave_kmers = n;                       // (64 lanes of at most 2^16 k-mers)
+#pragma unroll
+    for (int d = 32; d; d >>= 1) wave_kmers += __shfl_xor(wave_kmers, d);
+    if ((threadIdx.x & 63) == 0 && wave_tips) {
+        atomicAdd(s.ctr + KTIP_C_TIPS, (unsigned long long)__popcll(wave_tips));
+        atomicAdd(s.ctr + KTIP_C_KMERS, (unsigned long long)wave_kmers);
+    }
+}
+
+__global__ void ktip_totals_kernel(KunitigScratch s, uint64_t* __restrict__ totals) {
+    if (threadIdx.x != 0) return;
+    totals[KTIP_T_TIPS] = s.ctr[KTIP_C_TIPS];
+    totals[KTIP_T_KMERS] = s.ctr[KTIP_C_KMERS];
+    totals[KTIP_T_SOLID] = s.ctr[KUNITIG_C_SOLID];
+    totals[KTIP_T_KEPT] = s.ctr[KTIP_C_KEPT];
 }
 
 // ---- the corrector on an index cut over ranks: rounds over merged rows (kcorrect_rows.hpp) ----
@@ -1158,6 +1222,43 @@ int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t ca
                                    d_word_off_out, d_kmer_base_out, d_report);
             }))
             return rc;
+    return kidx_scratch_end(ix->uni, st);
+}
+
+// ---- the tips ----
+// One round, four launches on the caller's stream and no host wait: the unitigs' ends sweep, decide, apply, the totals.  The scratch is
+// the unitigs' -- a round and a compaction never run at once on one index, and the scratch's end event orders them across streams --
+// with their counters, start list and length list and nothing else: no covered bits, no scan
+int ktip_device_clip(::pg_kindex* ix, const KtipParams& pr, uint64_t* d_totals, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const KidxRank& t = ix->ranks[0];
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    const uint64_t cap = std::max<uint64_t>(2 * t.keys, 1);
+    dim3 slot_grid, start_grid;
+    if (int rc = kidx_launch_blocks(t.slots, 256, "table too large", &slot_grid)) return rc;
+    if (int rc = kidx_launch_blocks(cap, 256, "too many starts", &start_grid)) return rc;
+    if (int rc = kidx_scratch_begin(ix->uni, KUNITIG_CTRS + cap + (cap + 1) / 2, st)) return rc;
+    KunitigScratch s;
+    s.ctr = (unsigned long long*)ix->uni.d;
+    s.starts = ix->uni.d + KUNITIG_CTRS;
+    s.lens = (uint32_t*)(s.starts + cap);
+    s.sums = nullptr;
+    s.bits = nullptr;
+    s.cap = cap;
+    KIDX_HIP(hipMemsetAsync(s.ctr, 0, KUNITIG_CTRS * sizeof(uint64_t), st));
+    const dim3 block(256);
+    const int K = ix->K;
+    const uint64_t mask = t.slots - 1;
+    const KunitigParams ends{pr.min_cov, pr.min_arc, pr.max_tip};
+    if (int rc = kidx_launch(ix, [&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            hipLaunchKernelGGL((kunitig_ends_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, ends, s);
+            hipLaunchKernelGGL((ktip_decide_kernel<NW>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
+            hipLaunchKernelGGL((ktip_apply_kernel<NW>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
+        }))
+        return rc;
+    hipLaunchKernelGGL(ktip_totals_kernel, dim3(1), dim3(64), 0, st, s, d_totals);
+    KIDX_HIP(hipGetLastError());
     return kidx_scratch_end(ix->uni, st);
 }
 

@@ -74,7 +74,8 @@ PG_HD uint64_t map_find(const uint64_t* tab, uint64_t mask, const Kmer<NW>& ck, 
 }
 
 // Its sibling over the k-mer index of kindex.hpp, whose value is a pass-1 record's counter word: the word as it was stored, 0 when the
-// key is not in the set (a stored word has coverage >= 1 in bits 31:24; no key of that table is ever deleted)
+// key is not in the set (a stored word has coverage >= 1 in bits 31:24; no key of that table is ever taken out of its slot: a k-mer that
+// tip clipping removes, ktip.hpp, keeps its slot with the word 0 and so reads as absent here)
 template <int NW>
 PG_HD uint64_t kidx_find(const uint64_t* tab, uint64_t mask, const Kmer<NW>& ck) {
     const uint64_t* sl = map_probe<NW>(tab, mask, ck);

@@ -1,0 +1,45 @@
+"""Tip clipping on the CPU: the host twin (pg_kindex_clip_tips on a device = -1 index: csrc/ktip_host.cpp, the rule the kernels share in
+csrc/ktip.hpp) against the independent model (tests/ktip_model.py) on the designs of tests/ktip_cases.py -- each also against what its
+construction dictates: the totals and the word of every key of the original set after every round --, every refusal, KmerIndex.clip_tips,
+and under -fsanitize=address,undefined in a stand-alone program.  tests/test_gpu_ktip.py runs the same through the kernels.  All
+comparisons are of integers and exact."""
+import os
+import subprocess
+
+import pytest
+
+import ktip_cases as G
+from conftest import ROOT
+
+
+@pytest.mark.parametrize("flavour", G.FLAVOURS, ids=G.flavour_id)
+@pytest.mark.parametrize("design", G.DESIGNS, ids=lambda d: d.__name__[6:])
+def test_host_twin_matches_model_and_design(design, flavour):
+    """A 1-read branch of 1 and 7 k-mers on a 5-read path, at max_tip n - 1 and n, the junction canonical and not, the reads reverse
+    complemented, and the clipped index beside one built without the tip; a free side that is WEAK_NEXT by coverage and by the deleted
+    bit; two dead ends from one k-mer with counters 1:1, 2:1 and 63:63; two minor tips at one junction side; a tip on a tip, by rounds,
+    by two calls back to back and by clip_tips; the start of the graph before a fork, an island, a ring and a hairpin's chain, all kept;
+    tombstones in the middle of probe runs; an empty index; 257 and 513 tips on one path; noisy reads of a genome with a repeat to the
+    fixed point."""
+    design(flavour[0], flavour[1], -1)
+
+
+@pytest.mark.parametrize("flavour", G.FLAVOURS, ids=G.flavour_id)
+def test_refusals(flavour):
+    G.check_refusals(flavour[0], flavour[1], -1, (-1, -1))
+
+
+# ---- the host twin under the sanitizers, in a program of its own ----
+def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
+    """tests/ktip_asan.cpp: both flavours, a path with one-k-mer tips and a tip on a tip, clipped by rounds to the fixed point and
+    checked against the construction -- compiled with the host twin's sources and -fsanitize=address,undefined, and run.  Nothing loaded
+    into Python is sanitised."""
+    exe = str(tmp_path / "ktip_asan")
+    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
+           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "ktip_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
+           os.path.join(csrc, "kunitig_host.cpp"), os.path.join(csrc, "ktip_host.cpp"), "-o", exe]
+    built = subprocess.run(cmd, capture_output=True, text=True)
+    assert built.returncode == 0, built.stderr
+    ran = subprocess.run([exe], capture_output=True, text=True)
+    assert ran.returncode == 0 and "ktip host twin: ok" in ran.stdout, ran.stdout + ran.stderr
