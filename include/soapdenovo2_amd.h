@@ -586,7 +586,30 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       PG_EINVAL: a threshold or max_tip out of range, out_totals null; PG_ESTATE: an index cut over ranks (a walk
  *                       chases its lookups in one table); nothing is written then and the index is untouched.  Device memory of the
  *                       index's device, asynchronous on `stream`, no host wait; the scratch is pg_kindex_unitigs'.  Host memory for a
- *                       host-twin index.  Not done: a cut index, bubbles, isolated short unitigs.
+ *                       host-twin index.  Not done: a cut index, isolated short unitigs; bubbles are pg_kindex_pop_bubbles'.
+ *   pg_kindex_pop_bubbles        one round of bubble popping on the graph of the index (csrc/kbubble.hpp).  Solid, the arc sets, the side
+ *                       test, the end reasons, min_cov (1..255) and min_arc (1..63) are pg_kindex_unitigs'.  A branch is a linear
+ *                       unitig P = x0 -> .. -> x(n-1) whose two sides both have reason 6 branch in, with n <= max_len (1 .. 2^16
+ *                       k-mers) and two junctions that are different canonical k-mers: v, the solid k-mer behind the right side as
+ *                       the step reaches it, and L, the k-mer behind the left side as the step from rc(x0) reaches it; u = rc(L) is
+ *                       the fork.  A unitig whose junctions are one canonical k-mer (a loop u -> P -> u or u -> P -> rc(u)) is never
+ *                       touched.  Two branches are siblings when they have the same u and the same v, each the same k-mer in the same
+ *                       orientation, and their lengths differ by at most max_diff (0 .. 2^16) k-mers.  P is minor, and popped, iff
+ *                       some sibling Q has a strictly greater mean coverage: cov_P n_Q < cov_Q n_P in 64-bit integers, cov the sum
+ *                       of the branch's coverages; ties are kept, so the strongest branch of every bubble survives, and of three
+ *                       siblings A < B < C, A and B go in one round.  A weak path beside an alternative that is no such branch (a tip
+ *                       on it, a bubble in it, longer than max_len, an arc from u to v with no k-mer between) is kept: alternate
+ *                       rounds with pg_kindex_clip_tips.  The round decides over the index as it stood when it began, each branch
+ *                       once, from the end its unitig is emitted from, then applies: the cnt word of every k-mer of every minor
+ *                       branch becomes 0 (pg_kindex_clip_tips' tombstone), in v's word the in-counter for the first base of x(n-1)
+ *                       becomes 0, and in L's word the in-counter for the first base of rc(x0) -- u's out-counter for the branch.
+ *                       Nothing else is written; use a popped index at the same or higher thresholds.  out_totals[4], always
+ *                       written: [0] branches popped, [1] k-mers removed, [2] solid k-mers before the round, [3] candidates kept:
+ *                       the branches, in their deciding orientation, that were not popped.  Call rounds until out_totals[0] == 0.
+ *                       PG_EINVAL: a threshold, max_len or max_diff out of range, out_totals null; PG_ESTATE: an index cut over ranks;
+ *                       nothing is written then and the index is untouched.  Device memory of the index's device, asynchronous on
+ *                       `stream`, no host wait; the scratch is pg_kindex_unitigs'.  Host memory for a host-twin index.  Not done: a
+ *                       cut index, alternatives that are not simple, a comparison of the branches' bases.
  *   pg_kindex_correct_rows       pg_kindex_correct on any index, by rounds over merged rows (csrc/kcorrect_rows.hpp).  The batch, its
  *                       tail, n_words and n_kmers are pg_kindex_query_words' and pg_kindex_trim's; packed_out, out_report, in-place
  *                       use, the report word, the rule and the argument errors are pg_kindex_correct's, and so is the result, bit for
@@ -631,6 +654,8 @@ int pg_kindex_unitigs(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_
                       uint64_t *packed_out, uint64_t *word_off_out, uint64_t *kmer_base_out, uint64_t *out_report, uint64_t *out_totals,
                       void *stream);
 int pg_kindex_clip_tips(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_tip, uint64_t *out_totals, void *stream);
+int pg_kindex_pop_bubbles(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_len, uint32_t max_diff, uint64_t *out_totals,
+                          void *stream);
 int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
 void pg_kindex_destroy(pg_kindex *ix);
 uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */

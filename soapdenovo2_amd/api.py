@@ -190,6 +190,7 @@ def lib() -> C.CDLL:
                                  C.c_void_p]
     L.pg_kindex_unitigs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p, u64p, C.c_void_p]
     L.pg_kindex_clip_tips.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
+    L.pg_kindex_pop_bubbles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
     L.pg_kindex_info.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_destroy.argtypes = [C.c_void_p]
     L.pg_kindex_destroy.restype = None
@@ -225,7 +226,7 @@ EXPORTED_SYMBOLS = [
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
     "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times", "pg_kindex_correct_rows", "pg_kindex_correct_rows_stats",
-    "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_clip_tips",
+    "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_clip_tips", "pg_kindex_pop_bubbles",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
@@ -954,6 +955,19 @@ def tip_fields(totals) -> dict:
     return {k: int(v) for k, v in zip(TIP_TOTALS_FIELDS, np.ascontiguousarray(totals).view(np.uint64))}
 
 
+# The bubbles (pg_kindex_pop_bubbles).  BUBBLE_MAX_BOUND is the most max_len and max_diff the entry takes; max_len's default is 2 K.
+BUBBLE_MAX_BOUND = 1 << 16
+BUBBLE_TOTALS_FIELDS = ["branches", "kmers", "solid", "kept"]
+
+
+def bubble_fields(totals) -> dict:
+    """A round's totals (pg_kindex_pop_bubbles) by name: `branches` popped, `kmers` removed, `solid` k-mers before the round, and the
+    candidates `kept`: the branches that were not popped.  Takes a numpy array or a torch tensor of 4 words."""
+    if not isinstance(totals, np.ndarray):
+        totals = totals.cpu().numpy()
+    return {k: int(v) for k, v in zip(BUBBLE_TOTALS_FIELDS, np.ascontiguousarray(totals).view(np.uint64))}
+
+
 def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
     """pg_host_kindex_bytes: the table an index of n_records k-mers cuts (no GPU)."""
     return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
@@ -1270,6 +1284,43 @@ class KmerIndex:
             if not int(rounds[-1][0]):
                 break
         return rounds
+
+    def pop_bubbles(self, min_cov: int, min_arc: int, max_len=None, max_diff: int = 0, max_rounds: int = 64) -> list:
+        """Simple bubbles popped from the index's graph, in place (pg_kindex_pop_bubbles): a branch is a chain of at most max_len
+        k-mers (default 2 K) that leaves one k-mer with several arcs out and joins another with several arcs in; two branches between
+        the same two k-mers whose lengths differ by at most max_diff are siblings, and a branch is removed when a sibling has a strictly
+        greater mean coverage -- ties are kept, so the strongest branch of every bubble stays.  A removed k-mer reads as absent from
+        then on, to every operator; the records the index came from are not touched.  A bubble on a branch makes the outer bubble
+        wait, so rounds are called until one pops nothing or max_rounds is reached; each round's totals are read once -- the one wait
+        for the GPU a round.  Returns the rounds' totals, a list of numpy arrays of BUBBLE_TOTALS_FIELDS (bubble_fields names them),
+        the round that popped nothing included.  Use the popped index at the same or higher thresholds.  An index cut over ranks is
+        refused."""
+        max_len = 2 * self.K if max_len is None else max_len
+        rounds = []
+        while len(rounds) < max_rounds:
+            totals = np.zeros(4, dtype=np.uint64) if self.device < 0 else self.torch.zeros(4, dtype=self.torch.int64, device=f"cuda:{self.device}")
+            _check(lib().pg_kindex_pop_bubbles(self.h, min_cov, min_arc, max_len, max_diff, self._ptr(totals), self._stream()),
+                   "pg_kindex_pop_bubbles")
+            rounds.append(totals if self.device < 0 else totals.cpu().numpy().view(np.uint64))
+            if not int(rounds[-1][0]):
+                break
+        return rounds
+
+    def simplify(self, min_cov: int, min_arc: int, max_tip=None, max_len=None, max_diff: int = 0, max_rounds: int = 64) -> list:
+        """clip_tips to its fixed point, then pop_bubbles to its own, and both again -- a tip on a branch hides a bubble, a popped bubble
+        can leave a tip -- until a whole cycle removes nothing or max_rounds rounds were called in all.  Returns the rounds in call
+        order, a list of ("tips" | "bubbles", totals)."""
+        out = []
+        while len(out) < max_rounds:
+            removed = 0
+            for name in ("tips", "bubbles"):
+                left = max_rounds - len(out)
+                rounds = self.clip_tips(min_cov, min_arc, max_tip, left) if name == "tips" else self.pop_bubbles(min_cov, min_arc, max_len, max_diff, left)
+                out += [(name, r) for r in rounds]
+                removed += sum(int(r[0]) for r in rounds)
+            if not removed:
+                break
+        return out
 
     def info(self) -> dict:
         out = np.zeros(4, dtype=np.uint64)
