@@ -1,0 +1,209 @@
+#!/usr/bin/env python3
+"""What a round of an operator that edits the index's graph costs on an MI355X next to the unitigs' count call of the same run, and what
+it does to the unitigs: the reads of scripts/kunitig_bench.py (10 M x 100 bp over 4.6 Mb, K = 31, --err 0.005 substitutions), resident in
+HBM, are counted once, and every run indexes them afresh (KmerCounter.index(): an edited index is not restored, it is rebuilt) and then
+times, each by a pair of events around the one call: the unitigs' count call on the index as built -- the yardstick: a round makes the
+same ends sweep and two launches over the same start list --, and then the operator's rounds to the fixed point, the totals read after
+each.  --runs runs after one warm-up run.  No rate is asserted anywhere.
+
+    --op tips      pg_kindex_clip_tips round by round.  The first run also compacts the graph before the clipping and the
+                   last one after it, count call and full call timed: the unitig count, N50 and longest unitig on both sides, and what
+                   the long chains that are left cost the one-lane-a-chain walk.  Writes profiles/ktip.json.
+    --op bubbles   pg_kindex_clip_tips and pg_kindex_pop_bubbles round by round in KmerIndex.simplify's order.  The first
+                   run compacts the graph as built and after the tips' first fixed point, the last one after the whole simplification:
+                   the unitig count, N50, longest unitig and side reasons at the three places.  Writes profiles/kbubble.json.
+
+Every setting is measured by a child process of its own under a time limit (--limit seconds; the parent does not touch the GPU), and the
+first child that fails or runs out of time ends the script: nothing more is started on the card after it.  Needs a GPU; nothing falls back.
+
+    python scripts/kedit_bench.py --op tips|bubbles [--reads 10000000] [--setting 3:2] [--max-tip 62] [--max-len 62] [--max-diff 0]
+                                  [--runs 3] [--limit 900] [--out profiles/ktip.json|profiles/kbubble.json]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+REPEATS = "a repeat-rich graph (the simulated genome is random: what branches there are come from read errors)"
+ONE_CARD = "an index that does not fit one card (a cut index is refused)"
+NOT_MEASURED = {
+    "tips": ["the 127-mer build (K > 63: slots of 48 bytes, four-word keys)", REPEATS, "the idle share of lanes in the decide pass (a start "
+             "that is not free ends at once, a free one walks up to max_tip k-mers: no counters were collected and no estimate made)", ONE_CARD],
+    "bubbles": ["the 127-mer build (K > 63: slots of 48 bytes, four-word keys, a decide kernel of 104 VGPRs at half the occupancy)",
+                "max_diff > 0 on reads with insertions and deletions (the simulated errors are substitutions: every bubble has arms of K and K)",
+                REPEATS, "the idle share of lanes in the decide pass (a start whose left side is not BRANCH_IN ends at once, a branch's deciding "
+                "start walks its arm and up to three siblings: no counters were collected and no estimate made)", ONE_CARD]}
+# the calls of one cycle, in order; the summary fields printed at the end
+OPS = {"tips": (("tips",), ("rounds_needed", "median_unitigs_count_call_seconds", "median_first_round_seconds", "median_all_rounds_seconds",
+                            "first_round_over_count_call")),
+       "bubbles": (("tips", "bubbles"), ("calls_needed", "median_unitigs_count_call_seconds", "median_first_popping_round_seconds",
+                                         "median_first_empty_bubble_round_seconds", "popping_round_over_count_call", "empty_round_over_count_call",
+                                         "median_all_calls_seconds"))}
+
+
+def n50(lens):
+    lens = np.sort(np.asarray(lens, dtype=np.int64))[::-1]
+    if not len(lens):
+        return 0
+    return int(lens[np.searchsorted(np.cumsum(lens), lens.sum() / 2.0)])
+
+
+def child(a):
+    """One setting, in this process: a JSON object into a.child_out."""
+    import torch
+    from soapdenovo2_amd import api, synth
+    assert torch.cuda.is_available(), "kedit_bench.py measures on a GPU"
+    K, L, n = a.kmer, a.read_len, a.reads
+    min_cov, min_arc = (int(x) for x in a.child.split(":"))
+    wpr = api.packed_words(L)
+    packed = torch.zeros(n * wpr + 8, dtype=torch.int64, device="cuda")
+    codes = synth.gpu_reads_codes(a.genome, n, L, a.err, 1)
+    for lo in range(0, n, 1_000_000):                                  # (the packer pads to whole words in 64-bit lanes: a chunk at a time)
+        hi = min(n, lo + 1_000_000)
+        packed[lo * wpr:hi * wpr] = torch.from_numpy(api.pack_reads_uniform(codes[lo:hi])[:(hi - lo) * wpr].view(np.int64)).cuda()
+    del codes
+    expected = a.genome + int(n * L * a.err * K)
+    kc = api.KmerCounter(K, n_sets=8, log2_slots=max(16, int(np.ceil(np.log2(expected / 0.7)))))
+    kc.count_uniform(packed, n, L, 0)
+    kc.finalize(0)
+    del packed
+    L_ = api.lib()
+    new = lambda m: torch.zeros(max(m, 1), dtype=torch.int64, device="cuda")
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(f):
+        e0.record()
+        assert f() == 0, L_.pg_last_error()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e-3
+
+    def compaction(ix):
+        """The count call and the full call, timed, and what came out."""
+        totals = new(8)
+        sec_count = timed(lambda: L_.pg_kindex_unitigs(ix.h, min_cov, min_arc, a.max_kmers, 0, 0, None, None, None, None, ix._ptr(totals), ix._stream()))
+        t = totals.cpu().numpy().view(np.uint64).copy()
+        n_uni, words = int(t[0]), int(t[1])
+        outs = [new(words), new(n_uni + 1), new(n_uni + 1), new(2 * n_uni)]
+        sec_full = timed(lambda: L_.pg_kindex_unitigs(ix.h, min_cov, min_arc, a.max_kmers, n_uni, words, *[ix._ptr(o) for o in outs], ix._ptr(totals),
+                                                      ix._stream()))
+        f = api.unitig_fields(outs[3])
+        reasons = {r: int((f["left_code"] == c).sum() + (f["right_code"] == c).sum()) for c, r in api.UNITIG_REASONS.items()}
+        return {"count_seconds": sec_count, "full_seconds": sec_full, "totals": {k: int(v) for k, v in zip(api.UNITIG_TOTALS_FIELDS, t)},
+                "n50_bases": n50(f["len"]), "longest_bases": int(f["len"].max()) if len(f["len"]) else 0, "reasons": reasons}
+
+    def one_round(ix, name, t4):
+        if name == "tips":
+            sec = timed(lambda: L_.pg_kindex_clip_tips(ix.h, min_cov, min_arc, a.max_tip, ix._ptr(t4), ix._stream()))
+            return dict(api.tip_fields(t4), call="tips", removed=int(api.tip_fields(t4)["tips"]), seconds=sec)
+        sec = timed(lambda: L_.pg_kindex_pop_bubbles(ix.h, min_cov, min_arc, a.max_len, a.max_diff, ix._ptr(t4), ix._stream()))
+        return dict(api.bubble_fields(t4), call="bubbles", removed=int(api.bubble_fields(t4)["branches"]), seconds=sec)
+
+    names = OPS[a.op][0]
+    runs, built, tips_only, last, info = [], None, None, None, None
+    for i in range(a.runs + 1):                                        # (run 0 warms every path up)
+        ix = kc.index()
+        info = ix.info()
+        if i == 0:
+            built = compaction(ix)
+        totals = new(8)
+        yard = timed(lambda: L_.pg_kindex_unitigs(ix.h, min_cov, min_arc, a.max_kmers, 0, 0, None, None, None, None, ix._ptr(totals), ix._stream()))
+        calls, t4, cycle_removed, cycles = [], new(4), 1, 0
+        while cycle_removed:                                           # (KmerIndex.simplify's order: every operator to its fixed point, and again)
+            cycle_removed = 0
+            for name in names:
+                while True:
+                    calls.append(one_round(ix, name, t4))
+                    cycle_removed += calls[-1]["removed"]
+                    assert len(calls) <= 64
+                    if not calls[-1]["removed"]:
+                        break
+                if i == 0 and name == "tips" and cycles == 0 and len(names) > 1:
+                    tips_only = compaction(ix)
+            cycles += 1
+            if len(names) == 1:                                        # (one operator: its fixed point is the whole of it)
+                break
+        if i == a.runs:
+            last = compaction(ix)
+        ix.close()
+        print(f"[{a.child}] run {i}: count call {yard:.4f} s, {len(calls)} calls " + " ".join(f"{c['call'][0]}{c['seconds']:.4f}" for c in calls), flush=True)
+        if i:
+            runs.append({"unitigs_count_call_seconds": yard, "calls": calls})
+    kc.close()
+    yard = float(np.median([r["unitigs_count_call_seconds"] for r in runs]))
+    total = float(np.median([sum(c["seconds"] for c in r["calls"]) for r in runs]))
+    res = {"min_cov": min_cov, "min_arc": min_arc, "max_tip": a.max_tip}
+    if a.op == "tips":
+        first = float(np.median([r["calls"][0]["seconds"] for r in runs]))
+        strip = lambda c: {k: v for k, v in c.items() if k not in ("call", "removed")}
+        runs = [{"unitigs_count_call_seconds": r["unitigs_count_call_seconds"], "rounds": [strip(c) for c in r["calls"]]} for r in runs]
+        res.update({"max_kmers": a.max_kmers, "index": info, "runs": runs, "rounds_needed": len(runs[0]["rounds"]),
+                    "median_unitigs_count_call_seconds": yard, "median_first_round_seconds": first, "median_all_rounds_seconds": total,
+                    "first_round_over_count_call": first / yard, "unitigs_before": built, "unitigs_after": last})
+    else:
+        pick = lambda r, popping: [c["seconds"] for c in r["calls"] if c["call"] == "bubbles" and (c["removed"] > 0) == popping]
+        popping = float(np.median([pick(r, True)[0] for r in runs if pick(r, True)])) if any(pick(r, True) for r in runs) else None
+        empty = float(np.median([pick(r, False)[0] for r in runs]))
+        res.update({"max_len": a.max_len, "max_diff": a.max_diff, "max_kmers": a.max_kmers, "index": info, "runs": runs,
+                    "calls_needed": len(runs[0]["calls"]), "median_unitigs_count_call_seconds": yard,
+                    "median_first_popping_round_seconds": popping, "median_first_empty_bubble_round_seconds": empty,
+                    "popping_round_over_count_call": popping / yard if popping is not None else None, "empty_round_over_count_call": empty / yard,
+                    "median_all_calls_seconds": total, "unitigs_as_built": built, "unitigs_after_tips_only": tips_only, "unitigs_simplified": last})
+    json.dump(res, open(a.child_out, "w"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--op", choices=sorted(OPS), required=True)
+    ap.add_argument("--reads", type=int, default=10_000_000)
+    ap.add_argument("--read-len", type=int, default=100)
+    ap.add_argument("--genome", type=int, default=4_600_000)
+    ap.add_argument("--err", type=float, default=0.005)
+    ap.add_argument("--kmer", type=int, default=31)
+    ap.add_argument("--setting", nargs="+", default=["3:2"], help="min_cov:min_arc")
+    ap.add_argument("--max-tip", type=int, default=62)
+    ap.add_argument("--max-len", type=int, default=62)
+    ap.add_argument("--max-diff", type=int, default=0)
+    ap.add_argument("--max-kmers", type=int, default=1 << 24)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--limit", type=int, default=900, help="seconds a setting's child process may take")
+    ap.add_argument("--out", default=None, help="default: profiles/ktip.json (--op tips), profiles/kbubble.json (--op bubbles)")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child-out", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        return child(a)
+    out_path = a.out or os.path.join(ROOT, "profiles", "ktip.json" if a.op == "tips" else "kbubble.json")
+    reads = f"{a.reads} resident reads x {a.read_len} bp, genome {a.genome}, err {a.err}, K={a.kmer}, counted once and indexed afresh every run; "
+    if a.op == "tips":
+        what = (f"pg_kindex_clip_tips with max_tip {a.max_tip} round by round to the fixed point at each min_cov:min_arc, beside the "
+                f"unitigs' count call (max_kmers {a.max_kmers}) on the index as built; the unitigs before the clipping and after it")
+    else:
+        what = (f"pg_kindex_clip_tips (max_tip {a.max_tip}) and pg_kindex_pop_bubbles (max_len {a.max_len}, max_diff {a.max_diff}) round by "
+                f"round in KmerIndex.simplify's order to the fixed point at each min_cov:min_arc, beside the unitigs' count call (max_kmers "
+                f"{a.max_kmers}) on the index as built; the unitigs as built, after the tips alone and simplified")
+    res = {"workload": reads + what, "settings": {}, "not_measured": NOT_MEASURED[a.op]}
+    passed = [x for x in sys.argv[1:]]
+    with tempfile.TemporaryDirectory() as tmp:
+        for s in a.setting:
+            out = os.path.join(tmp, "setting.json")
+            # a fresh process a setting, under its own time limit; one that fails or hangs ends the script
+            rc = subprocess.call(["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__)] + passed + ["--child", s, "--child-out", out])
+            if rc != 0:
+                sys.exit(f"kedit_bench.py: setting {s} ended with status {rc}; nothing more is started")
+            res["settings"][s] = json.load(open(out))
+            os.remove(out)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    json.dump(res, open(out_path, "w"), indent=1)
+    print(json.dumps({s: {k: v[k] for k in OPS[a.op][1]} for s, v in res["settings"].items()}))
+
+
+if __name__ == "__main__":
+    main()

@@ -942,6 +942,13 @@ def unitig_fields(report) -> dict:
             "coverage_sum": w[:, 1].astype(np.int64)}
 
 
+# a round's four totals of an operator that edits the graph (the tips, the bubbles) by the operator's names
+def _edit_fields(names, totals) -> dict:
+    if not isinstance(totals, np.ndarray):
+        totals = totals.cpu().numpy()
+    return {k: int(v) for k, v in zip(names, np.ascontiguousarray(totals).view(np.uint64))}
+
+
 # The tips (pg_kindex_clip_tips).  TIP_MAX_BOUND is the most max_tip the entry takes; its default is 2 K, the reference's tip length.
 TIP_MAX_BOUND = 1 << 16
 TIP_TOTALS_FIELDS = ["tips", "kmers", "solid", "kept"]
@@ -950,9 +957,7 @@ TIP_TOTALS_FIELDS = ["tips", "kmers", "solid", "kept"]
 def tip_fields(totals) -> dict:
     """A round's totals (pg_kindex_clip_tips) by name: `tips` clipped, `kmers` removed, `solid` k-mers before the round, and the
     candidates `kept` because they were not minor.  Takes a numpy array or a torch tensor of 4 words."""
-    if not isinstance(totals, np.ndarray):
-        totals = totals.cpu().numpy()
-    return {k: int(v) for k, v in zip(TIP_TOTALS_FIELDS, np.ascontiguousarray(totals).view(np.uint64))}
+    return _edit_fields(TIP_TOTALS_FIELDS, totals)
 
 
 # The bubbles (pg_kindex_pop_bubbles).  BUBBLE_MAX_BOUND is the most max_len and max_diff the entry takes; max_len's default is 2 K.
@@ -963,9 +968,7 @@ BUBBLE_TOTALS_FIELDS = ["branches", "kmers", "solid", "kept"]
 def bubble_fields(totals) -> dict:
     """A round's totals (pg_kindex_pop_bubbles) by name: `branches` popped, `kmers` removed, `solid` k-mers before the round, and the
     candidates `kept`: the branches that were not popped.  Takes a numpy array or a torch tensor of 4 words."""
-    if not isinstance(totals, np.ndarray):
-        totals = totals.cpu().numpy()
-    return {k: int(v) for k, v in zip(BUBBLE_TOTALS_FIELDS, np.ascontiguousarray(totals).view(np.uint64))}
+    return _edit_fields(BUBBLE_TOTALS_FIELDS, totals)
 
 
 def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
@@ -1266,6 +1269,17 @@ class KmerIndex:
             raise PgError("KmerIndex.unitigs: the full call needs more than the count call said")
         return Unitigs(packed[:words], word_off[:n + 1], kmer_base[:n + 1], report[:2 * n], t)
 
+    def _edit_rounds(self, entry: str, args: tuple, max_rounds: int) -> list:
+        """Rounds of the ABI entry `entry` with `args` until one removes nothing or max_rounds were called; each round's four totals."""
+        call, rounds = getattr(lib(), entry), []
+        while len(rounds) < max_rounds:
+            totals = np.zeros(4, dtype=np.uint64) if self.device < 0 else self.torch.zeros(4, dtype=self.torch.int64, device=f"cuda:{self.device}")
+            _check(call(self.h, *args, self._ptr(totals), self._stream()), entry)
+            rounds.append(totals if self.device < 0 else totals.cpu().numpy().view(np.uint64))
+            if not int(rounds[-1][0]):
+                break
+        return rounds
+
     def clip_tips(self, min_cov: int, min_arc: int, max_tip=None, max_rounds: int = 64) -> list:
         """Minor tips clipped from the index's graph, in place (pg_kindex_clip_tips): a tip is a chain of at most max_tip k-mers
         (default 2 K) that is free -- a dead end or a weak successor -- on one side and joins a k-mer with several arcs in on the
@@ -1276,14 +1290,7 @@ class KmerIndex:
         TIP_TOTALS_FIELDS (tip_fields names them), the round that clipped nothing included.  Use the clipped index at the same or
         higher thresholds.  An index cut over ranks is refused."""
         max_tip = 2 * self.K if max_tip is None else max_tip
-        rounds = []
-        while len(rounds) < max_rounds:
-            totals = np.zeros(4, dtype=np.uint64) if self.device < 0 else self.torch.zeros(4, dtype=self.torch.int64, device=f"cuda:{self.device}")
-            _check(lib().pg_kindex_clip_tips(self.h, min_cov, min_arc, max_tip, self._ptr(totals), self._stream()), "pg_kindex_clip_tips")
-            rounds.append(totals if self.device < 0 else totals.cpu().numpy().view(np.uint64))
-            if not int(rounds[-1][0]):
-                break
-        return rounds
+        return self._edit_rounds("pg_kindex_clip_tips", (min_cov, min_arc, max_tip), max_rounds)
 
     def pop_bubbles(self, min_cov: int, min_arc: int, max_len=None, max_diff: int = 0, max_rounds: int = 64) -> list:
         """Simple bubbles popped from the index's graph, in place (pg_kindex_pop_bubbles): a branch is a chain of at most max_len
@@ -1296,15 +1303,7 @@ class KmerIndex:
         the round that popped nothing included.  Use the popped index at the same or higher thresholds.  An index cut over ranks is
         refused."""
         max_len = 2 * self.K if max_len is None else max_len
-        rounds = []
-        while len(rounds) < max_rounds:
-            totals = np.zeros(4, dtype=np.uint64) if self.device < 0 else self.torch.zeros(4, dtype=self.torch.int64, device=f"cuda:{self.device}")
-            _check(lib().pg_kindex_pop_bubbles(self.h, min_cov, min_arc, max_len, max_diff, self._ptr(totals), self._stream()),
-                   "pg_kindex_pop_bubbles")
-            rounds.append(totals if self.device < 0 else totals.cpu().numpy().view(np.uint64))
-            if not int(rounds[-1][0]):
-                break
-        return rounds
+        return self._edit_rounds("pg_kindex_pop_bubbles", (min_cov, min_arc, max_len, max_diff), max_rounds)
 
     def simplify(self, min_cov: int, min_arc: int, max_tip=None, max_len=None, max_diff: int = 0, max_rounds: int = 64) -> list:
         """clip_tips to its fixed point, then pop_bubbles to its own, and both again -- a tip on a branch hides a bubble, a popped bubble

@@ -58,18 +58,16 @@
 // such records the mirrored view may also see other siblings than this one; a branch is decided from one start only, so the round is
 // a function of the index all the same.)
 //
-// One piece of PG_HD code for the kernels (kindex_kernels.hip: kbubble_decide_kernel, kbubble_apply_kernel) and the host twin
-// (kbubble_host.cpp): kbubble_decide reads, kbubble_apply writes through two functions of the caller and leaves the right side and the
-// zeroing to ktip_apply.  Loop state is kept with selects (DESIGN.md §11 on what stores under branches inside such a loop became).
+// One piece of PG_HD code for the round's kernels (kindex_kernels.hip: kedit_decide_kernel, kedit_apply_kernel) and its host twin
+// (kedit_host.cpp), which see it as KbubbleOp (kedit.hpp): kbubble_decide reads, kbubble_apply writes through two functions of the caller
+// and leaves the right side and the zeroing to ktip_apply.  Loop state is kept with selects (DESIGN.md §11 on what stores under branches
+// inside such a loop became).
 #pragma once
 #include "ktip.hpp"
 
 namespace pg {
 
 constexpr uint32_t KBUBBLE_MAX_LEN = 1u << 16, KBUBBLE_MAX_DIFF = 1u << 16;
-constexpr int KBUBBLE_TOTALS = KTIP_TOTALS;
-// out_totals: branches popped, k-mers removed, solid k-mers before the round, candidates kept -- the tips' layout (the totals kernel is theirs)
-enum : int { KBUBBLE_T_BRANCHES = KTIP_T_TIPS, KBUBBLE_T_KMERS = KTIP_T_KMERS, KBUBBLE_T_SOLID = KTIP_T_SOLID, KBUBBLE_T_KEPT = KTIP_T_KEPT };
 
 struct KbubbleParams {
     uint32_t min_cov, min_arc, max_len, max_diff;
@@ -79,51 +77,21 @@ struct KbubbleParams {
 template <int NW>
 PG_HD KwalkNode<NW> kbubble_flip(const KwalkNode<NW>& x) { return KwalkNode<NW>{x.b, x.a, x.w, x.slot, !x.fwd}; }
 
-// What a walk found: n k-mers, the reason of the side behind the n-th, the sum of their coverage
-struct KbubblePath {
-    uint32_t n, reason;
-    uint64_t cov;
-};
-
-// From the solid node x to the right through open sides, at most pr.max_kmers k-mers.  Afterwards x is the last k-mer and y the node
-// behind its right side (BRANCH_IN: the junction, its word in hand)
+// The decision for the start x0 whose left side has reason `left`; candidate: a branch in its deciding orientation.  Only reads
 template <int NW, typename Find>
-PG_HD KbubblePath kbubble_path(KwalkNode<NW>& x, KwalkNode<NW>& y, int K, const Kmer<NW>& filter, const KunitigParams& pr, Find find) {
-    uint32_t n = 1, reason = 0;
-    uint64_t cov = kidx_coverage(x.w);
-    for (;;) {
-        int base = 0;
-        reason = kunitig_side<NW>(x, K, filter, pr, find, y, base);
-        reason = !reason && n == pr.max_kmers ? KUNITIG_CUT : reason;
-        if (reason) break;
-        n++;
-        cov += kidx_coverage(y.w);
-        x = y;
-    }
-    return KbubblePath{n, reason, cov};
-}
-
-// What the decide pass says of a start: n k-mers walked; candidate: a branch in its deciding orientation; minor: a candidate that is popped
-struct KbubbleDecision {
-    uint32_t n;
-    bool candidate, minor;
-};
-
-// The decision for the start x0 whose left side has reason `left`.  Only reads
-template <int NW, typename Find>
-PG_HD KbubbleDecision kbubble_decide(const KwalkNode<NW>& x0, uint32_t left, int K, const KbubbleParams& pr, Find find) {
+PG_HD KeditDecision kbubble_decide(const KwalkNode<NW>& x0, uint32_t left, int K, const KbubbleParams& pr, Find find) {
     const Kmer<NW> filter = kmer_filter<NW>(K);
     const KunitigParams up{pr.min_cov, pr.min_arc, pr.max_len};
-    if (left != KWALK_BRANCH_IN) return KbubbleDecision{0, false, false};
+    if (left != KWALK_BRANCH_IN) return KeditDecision{0, false, false};
     // 1. P, to v; decided from the start that is not greater
     KwalkNode<NW> x = x0, v;
-    const KbubblePath P = kbubble_path<NW>(x, v, K, filter, up, find);
-    if (P.reason != KWALK_BRANCH_IN || kmer_less<NW>(x.b, x0.a)) return KbubbleDecision{P.n, false, false};
+    const KeditPath P = kedit_path<NW>(x, v, K, filter, up, find);
+    if (P.reason != KWALK_BRANCH_IN || kmer_less<NW>(x.b, x0.a)) return KeditDecision{P.n, false, false};
     // 2. L behind the left side, and the fork u = rc(L)
     KwalkNode<NW> L;
     int base = 0;
     const uint32_t behind = kunitig_side<NW>(kbubble_flip<NW>(x0), K, filter, up, find, L, base);
-    if (behind != KWALK_BRANCH_IN || kmer_eq<NW>(kwalk_canon<NW>(L), kwalk_canon<NW>(v))) return KbubbleDecision{P.n, false, false};
+    if (behind != KWALK_BRANCH_IN || kmer_eq<NW>(kwalk_canon<NW>(L), kwalk_canon<NW>(v))) return KeditDecision{P.n, false, false};
     const KwalkNode<NW> u = kbubble_flip<NW>(L);
     const uint32_t others = kwalk_out_set(u.w, u.fwd, pr.min_arc) & ~(1u << (int)(x0.a.w[NW - 1] & 3));
     bool minor = false;
@@ -139,12 +107,12 @@ PG_HD KbubbleDecision kbubble_decide(const KwalkNode<NW>& x0, uint32_t left, int
         const uint32_t back = kunitig_side<NW>(kbubble_flip<NW>(q), K, filter, up, find, y, base);
         if (back != KWALK_BRANCH_IN || !kmer_eq<NW>(y.a, L.a)) continue;
         // 4., 5. Q, to v in v's orientation, the lengths within max_diff; the means compared by cross-multiplication
-        const KbubblePath Q = kbubble_path<NW>(q, y, K, filter, up, find);
+        const KeditPath Q = kedit_path<NW>(q, y, K, filter, up, find);
         const uint32_t diff = P.n > Q.n ? P.n - Q.n : Q.n - P.n;
         const bool sibling = Q.reason == KWALK_BRANCH_IN && kmer_eq<NW>(y.a, v.a) && diff <= pr.max_diff;
         minor = sibling && P.cov * (uint64_t)Q.n < Q.cov * (uint64_t)P.n ? true : minor;
     }
-    return KbubbleDecision{P.n, true, minor};
+    return KeditDecision{P.n, true, minor};
 }
 
 // The minor branch of n k-mers from x0 applied: L is named by the single out arc of rc(x0) as x0's own word has it and looked up
@@ -164,7 +132,19 @@ PG_HD void kbubble_apply(const KwalkNode<NW>& x0, uint32_t n, int K, const Kbubb
     ktip_apply<NW>(x0, n, K, KtipParams{pr.min_cov, pr.min_arc, pr.max_len}, find, zero, clear);
 }
 
-// The caller's side of the device engine (kindex_kernels.hip), one round, asynchronous on `stream`
-int kbubble_device_pop(::pg_kindex* ix, const KbubbleParams& pr, uint64_t* d_totals, void* stream);
+// The bubbles as the round sees them (kedit.hpp)
+struct KbubbleOp {
+    using Params = KbubbleParams;
+    static PG_HD KunitigParams ends(const Params& pr) { return KunitigParams{pr.min_cov, pr.min_arc, pr.max_len}; }
+    static PG_HD bool starts(uint32_t left) { return left == KWALK_BRANCH_IN; }
+    template <int NW, typename Find>
+    static PG_HD KeditDecision decide(const KwalkNode<NW>& x0, uint32_t left, int K, const Params& pr, Find find) {
+        return kbubble_decide<NW>(x0, left, K, pr, find);
+    }
+    template <int NW, typename Find, typename Zero, typename Clear>
+    static PG_HD void apply(const KwalkNode<NW>& x0, uint32_t n, int K, const Params& pr, Find find, Zero zero, Clear clear) {
+        kbubble_apply<NW>(x0, n, K, pr, find, zero, clear);
+    }
+};
 
 }  // namespace pg

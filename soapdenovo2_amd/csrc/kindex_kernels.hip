@@ -67,23 +67,20 @@
 //                              kunitig_scan_sums_kernel (the totals, the overflow decision the write kernel obeys, the last offsets and
 //                              the tail's zero words)
 //   kunitig_write_kernel       a lane per start: its offsets from the scan, and a kept start walks once more into its row
-// The tips (ktip.hpp; pg_kindex_clip_tips): one round, four launches on the caller's stream over the unitigs' scratch
+// The operators that edit the graph (kedit.hpp): one round of an operator Op, four launches on the caller's stream over the
+// unitigs' scratch
 //   kunitig_ends_kernel        as above: the start list and the solid count
-//   ktip_decide_kernel         a lane per start: one whose left side is not free ends at once, the others walk at most max_tip k-mers
-//                              (ktip_decide) and, at a BRANCH_IN, test the junction's word; n into the length list for a minor tip, else
-//                              0; the candidates kept counted a wave at a time.  Reads the table only
-//   ktip_apply_kernel          a lane per start with n != 0: ktip_apply -- a plain store of 0 over each of its n k-mers' words, one
-//                              atomicAnd on the 32-bit half of the junction's word that holds the tip's in-counter (the one word two lanes
-//                              may write together).  Tips and k-mers counted a wave at a time
-//   ktip_totals_kernel         the four totals from the counters
-// The bubbles (kbubble.hpp; pg_kindex_pop_bubbles): one round, the tips' four launches with the bubbles' two in the middle
-//   kunitig_ends_kernel        as above
-//   kbubble_decide_kernel      a lane per start: one whose left side is not BRANCH_IN ends at once, the others walk their branch, take the
-//                              fork from the step out of rc(x0) and walk at most three siblings (kbubble_decide); n into the length list
-//                              for a minor branch, else 0; the candidates kept counted a wave at a time.  Reads the table only
-//   kbubble_apply_kernel       a lane per start with n != 0: kbubble_apply -- one atomicAnd on the in-half of the left junction's word,
-//                              then ktip_apply: plain stores of 0 over the n words and one atomicAnd on the right junction's in-half
-//   ktip_totals_kernel         the four totals: the counters and the totals are laid out as the tips'
+//   kedit_decide_kernel<Op>    a lane per start: one whose left reason Op::starts refuses ends at once, the others walk (Op::decide); n
+//                              into the length list for a minor candidate, else 0; the candidates kept counted a wave at a time.  Reads
+//                              the table only
+//   kedit_apply_kernel<Op>     a lane per start with n != 0: Op::apply -- a plain store of 0 over each of its n k-mers' words, one
+//                              atomicAnd on the 32-bit half of a junction's word that holds the removed arc's in-counter (the one word two
+//                              lanes may write together).  Removals and k-mers counted a wave at a time
+//   kedit_totals_kernel        the four totals from the counters
+// The tips (ktip.hpp: KtipOp; pg_kindex_clip_tips): a start that is free on the left walks at most max_tip k-mers and, at a
+// BRANCH_IN, tests the junction's word; apply cuts the tip from that one junction
+// The bubbles (kbubble.hpp: KbubbleOp; pg_kindex_pop_bubbles): a start with BRANCH_IN on the left walks its branch, takes the
+// fork from the step out of rc(x0) and walks at most three siblings; apply cuts the branch from both junctions
 // The corrector on an index cut over ranks (kcorrect_rows.hpp; pg_kindex_correct_rows): rounds of plan, query, decide on the
 // caller's stream, every query kidx_query_ranks, and the host reads the round's trial count back once a round
 //   kcor_rows_begin_kernel     a lane per read over its row of the read as given: weak count, anchor, first weak k-mer behind it, the
@@ -109,6 +106,7 @@
 #include "kbubble.hpp"
 #include "kcorrect.hpp"
 #include "kcorrect_rows.hpp"
+#include "kedit.hpp"
 #include "kindex.hpp"
 #include "ktip.hpp"
 #include "ktrim.hpp"
@@ -571,103 +569,72 @@ __global__ __launch_bounds__(256) void kunitig_write_kernel(const uint64_t* __re
     }
 }
 
-// ---- the tips: ends (the unitigs' kernel), decide, apply, the totals (ktip.hpp) ----
-// A round's counters lie behind the unitigs' in the same scratch: tips clipped, k-mers removed, candidates kept
-enum : int { KTIP_C_TIPS = 5, KTIP_C_KMERS = 6, KTIP_C_KEPT = 7 };
-static_assert(KTIP_C_KEPT < KUNITIG_CTRS && KTIP_C_TIPS > KUNITIG_C_GO, "the tips' counters lie in the scratch, behind the unitigs'");
+// ---- the operators that edit the graph: ends (the unitigs' kernel), decide, apply, the totals (kedit.hpp; ktip.hpp, kbubble.hpp) ----
+// A round's counters lie behind the unitigs' in the same scratch: unitigs removed, k-mers removed, candidates kept
+enum : int { KEDIT_C_REMOVED = 5, KEDIT_C_KMERS = 6, KEDIT_C_KEPT = 7 };
+static_assert(KEDIT_C_KEPT < KUNITIG_CTRS && KEDIT_C_REMOVED > KUNITIG_C_GO, "a round's counters lie in the scratch, behind the unitigs'");
 
-// a lane per start: the decision, n into the length list for a minor tip and 0 for every other start.  Only reads the table
+// the table as an operator reaches it: the lookup, a k-mer's word zeroed with a plain store, and a junction's counter taken out with an
+// atomicAnd on the 32-bit half that holds it: another lane may clear another counter of that half
 template <int NW>
-__global__ __launch_bounds__(256) void ktip_decide_kernel(const uint64_t* __restrict__ tab, uint64_t mask, int K, KtipParams pr, KunitigScratch s) {
+struct KeditFind {
+    const uint64_t* tab;
+    uint64_t mask;
+    __device__ uint64_t operator()(const Kmer<NW>& ck, uint64_t& slot) const { return kunitig_probe<NW>(tab, mask, ck, slot); }
+};
+template <int NW>
+struct KeditZero {
+    uint64_t* tab;
+    __device__ void operator()(uint64_t slot) const { tab[slot * map_slot_words<NW>() + NW] = 0; }
+};
+template <int NW>
+struct KeditClear {
+    uint64_t* tab;
+    __device__ void operator()(uint64_t slot, bool fwd, int a) const {
+        atomicAnd((unsigned int*)(tab + slot * map_slot_words<NW>() + NW) + kedit_in_half(fwd), kedit_keep_mask(fwd, a));
+    }
+};
+
+// a lane per start: the decision, n into the length list for a minor candidate and 0 for every other start.  Only reads the table
+template <int NW, class Op>
+__global__ __launch_bounds__(256) void kedit_decide_kernel(const uint64_t* __restrict__ tab, uint64_t mask, int K, typename Op::Params pr, KunitigScratch s) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    KtipDecision d{0, false, false};
+    KeditDecision d{0, false, false};
     if (i < kunitig_n_starts(s)) {
         const uint64_t start = s.starts[i];
         const uint32_t left = kunitig_start_reason(start);
-        if (ktip_free(left))                       // (any other start ends at once: its slot is not even read)
-            d = ktip_decide<NW>(kunitig_start_node<NW>(tab, start, K), left, K, pr,
-                                [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); });
+        if (Op::starts(left))                      // (any other start ends at once: its slot is not even read)
+            d = Op::template decide<NW>(kunitig_start_node<NW>(tab, start, K), left, K, pr, KeditFind<NW>{tab, mask});
         s.lens[i] = d.minor ? d.n : 0;
     }
     const uint64_t wave_kept = __ballot(d.candidate && !d.minor);                 // (every lane of the wave is here)
-    if ((threadIdx.x & 63) == 0 && wave_kept) atomicAdd(s.ctr + KTIP_C_KEPT, (unsigned long long)__popcll(wave_kept));
+    if ((threadIdx.x & 63) == 0 && wave_kept) atomicAdd(s.ctr + KEDIT_C_KEPT, (unsigned long long)__popcll(wave_kept));
 }
 
-// a lane per start with n != 0: its n k-mers' words zeroed with plain stores -- they are in no other tip --, its counter taken out of the
-// junction's word with an atomicAnd on the 32-bit half that holds it: another tip's lane may clear another counter of that half
-template <int NW>
-__global__ __launch_bounds__(256) void ktip_apply_kernel(uint64_t* tab, uint64_t mask, int K, KtipParams pr, KunitigScratch s) {
-    constexpr int SW = map_slot_words<NW>();
+// a lane per start with n != 0: its n k-mers' words zeroed -- they are in no other lane's unitig --, its counters taken out of the
+// junctions' words
+template <int NW, class Op>
+__global__ __launch_bounds__(256) void kedit_apply_kernel(uint64_t* tab, uint64_t mask, int K, typename Op::Params pr, KunitigScratch s) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t n = i < kunitig_n_starts(s) ? s.lens[i] : 0;
     if (n)
-        ktip_apply<NW>(kunitig_start_node<NW>(tab, s.starts[i], K), n, K, pr,
-                       [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); },
-                       [tab](uint64_t slot) { tab[slot * SW + NW] = 0; },
-                       [tab](uint64_t slot, bool fwd, int a) {
-                           atomicAnd((unsigned int*)(tab + slot * SW + NW) + ktip_in_half(fwd), ktip_keep_mask(fwd, a));
-                       });
-    const uint64_t wave_tips = __ballot(n != 0);                                 // (every lane of the wave is here)
+        Op::template apply<NW>(kunitig_start_node<NW>(tab, s.starts[i], K), n, K, pr, KeditFind<NW>{tab, mask}, KeditZero<NW>{tab}, KeditClear<NW>{tab});
+    const uint64_t wave_removed = __ballot(n != 0);                              // (every lane of the wave is here)
     uint32_t wave_kmers = n;                       // (64 lanes of at most 2^16 k-mers)
 #pragma unroll
     for (int d = 32; d; d >>= 1) wave_kmers += __shfl_xor(wave_kmers, d);
-    if ((threadIdx.x & 63) == 0 && wave_tips) {
-        atomicAdd(s.ctr + KTIP_C_TIPS, (unsigned long long)__popcll(wave_tips));
-        atomicAdd(s.ctr + KTIP_C_KMERS, (unsigned long long)wave_kmers);
+    if ((threadIdx.x & 63) == 0 && wave_removed) {
+        atomicAdd(s.ctr + KEDIT_C_REMOVED, (unsigned long long)__popcll(wave_removed));
+        atomicAdd(s.ctr + KEDIT_C_KMERS, (unsigned long long)wave_kmers);
     }
 }
 
-__global__ void ktip_totals_kernel(KunitigScratch s, uint64_t* __restrict__ totals) {
+__global__ void kedit_totals_kernel(KunitigScratch s, uint64_t* __restrict__ totals) {
     if (threadIdx.x != 0) return;
-    totals[KTIP_T_TIPS] = s.ctr[KTIP_C_TIPS];
-    totals[KTIP_T_KMERS] = s.ctr[KTIP_C_KMERS];
-    totals[KTIP_T_SOLID] = s.ctr[KUNITIG_C_SOLID];
-    totals[KTIP_T_KEPT] = s.ctr[KTIP_C_KEPT];
-}
-
-// ---- the bubbles: ends (the unitigs' kernel), decide, apply, the totals (the tips' kernel) (kbubble.hpp) ----
-// A round's counters are the tips': branches popped, k-mers removed, candidates kept
-enum : int { KBUBBLE_C_BRANCHES = KTIP_C_TIPS, KBUBBLE_C_KMERS = KTIP_C_KMERS, KBUBBLE_C_KEPT = KTIP_C_KEPT };
-
-// a lane per start: one whose left side is not BRANCH_IN ends at once without reading its slot; the others decide (kbubble_decide).  n
-// into the length list for a minor branch and 0 for every other start.  Only reads the table
-template <int NW>
-__global__ __launch_bounds__(256) void kbubble_decide_kernel(const uint64_t* __restrict__ tab, uint64_t mask, int K, KbubbleParams pr, KunitigScratch s) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    KbubbleDecision d{0, false, false};
-    if (i < kunitig_n_starts(s)) {
-        const uint64_t start = s.starts[i];
-        if (kunitig_start_reason(start) == KWALK_BRANCH_IN)
-            d = kbubble_decide<NW>(kunitig_start_node<NW>(tab, start, K), KWALK_BRANCH_IN, K, pr,
-                                   [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); });
-        s.lens[i] = d.minor ? d.n : 0;
-    }
-    const uint64_t wave_kept = __ballot(d.candidate && !d.minor);                 // (every lane of the wave is here)
-    if ((threadIdx.x & 63) == 0 && wave_kept) atomicAdd(s.ctr + KBUBBLE_C_KEPT, (unsigned long long)__popcll(wave_kept));
-}
-
-// a lane per start with n != 0: its n k-mers' words zeroed with plain stores -- they are in no other branch --, its counter taken out of
-// each junction's word with an atomicAnd on the 32-bit half that holds it: a sibling's lane may clear another counter of that half
-template <int NW>
-__global__ __launch_bounds__(256) void kbubble_apply_kernel(uint64_t* tab, uint64_t mask, int K, KbubbleParams pr, KunitigScratch s) {
-    constexpr int SW = map_slot_words<NW>();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t n = i < kunitig_n_starts(s) ? s.lens[i] : 0;
-    if (n)
-        kbubble_apply<NW>(kunitig_start_node<NW>(tab, s.starts[i], K), n, K, pr,
-                          [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); },
-                          [tab](uint64_t slot) { tab[slot * SW + NW] = 0; },
-                          [tab](uint64_t slot, bool fwd, int a) {
-                              atomicAnd((unsigned int*)(tab + slot * SW + NW) + ktip_in_half(fwd), ktip_keep_mask(fwd, a));
-                          });
-    const uint64_t wave_branches = __ballot(n != 0);                             // (every lane of the wave is here)
-    uint32_t wave_kmers = n;                       // (64 lanes of at most 2^16 k-mers)
-#pragma unroll
-    for (int d = 32; d; d >>= 1) wave_kmers += __shfl_xor(wave_kmers, d);
-    if ((threadIdx.x & 63) == 0 && wave_branches) {
-        atomicAdd(s.ctr + KBUBBLE_C_BRANCHES, (unsigned long long)__popcll(wave_branches));
-        atomicAdd(s.ctr + KBUBBLE_C_KMERS, (unsigned long long)wave_kmers);
-    }
+    totals[KEDIT_T_REMOVED] = s.ctr[KEDIT_C_REMOVED];
+    totals[KEDIT_T_KMERS] = s.ctr[KEDIT_C_KMERS];
+    totals[KEDIT_T_SOLID] = s.ctr[KUNITIG_C_SOLID];
+    totals[KEDIT_T_KEPT] = s.ctr[KEDIT_C_KEPT];
 }
 
 // ---- the corrector on an index cut over ranks: rounds over merged rows (kcorrect_rows.hpp) ----
@@ -1279,15 +1246,12 @@ int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t ca
     return kidx_scratch_end(ix->uni, st);
 }
 
-// ---- the tips ----
-// One round, four launches on the caller's stream and no host wait: the unitigs' ends sweep, decide, apply, the totals.  The scratch is
-// the unitigs' -- a round and a compaction never run at once on one index, and the scratch's end event orders them across streams --
+// ---- the operators that edit the graph ----
+// One round of Op, four launches on the caller's stream and no host wait: the unitigs' ends sweep, decide, apply, the totals.  The scratch
+// is the unitigs' -- a round and a compaction never run at once on one index, and the scratch's end event orders them across streams --
 // with their counters, start list and length list and nothing else: no covered bits, no scan
-namespace {
-// what the tips' and the bubbles' rounds share: the scratch cut, the counters zeroed, the ends sweep, the operator's decide and apply
-// kernels -- passes(nw, start_grid, block, s) launches them --, the totals
-template <typename Passes>
-int kidx_graph_round(::pg_kindex* ix, const KunitigParams& ends, uint64_t* d_totals, void* stream, Passes passes) {
+template <class Op>
+int kedit_device_round(::pg_kindex* ix, const typename Op::Params& pr, uint64_t* d_totals, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const KidxRank& t = ix->ranks[0];
     if (int rc = kidx_set_device(ix->device)) return rc;
@@ -1306,44 +1270,20 @@ int kidx_graph_round(::pg_kindex* ix, const KunitigParams& ends, uint64_t* d_tot
     KIDX_HIP(hipMemsetAsync(s.ctr, 0, KUNITIG_CTRS * sizeof(uint64_t), st));
     const dim3 block(256);
     const int K = ix->K;
+    const uint64_t mask = t.slots - 1;
     if (int rc = kidx_launch(ix, [&](auto nw) {
             constexpr int NW = decltype(nw)::value;
-            hipLaunchKernelGGL((kunitig_ends_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, ends, s);
-            passes(nw, start_grid, block, s);
+            hipLaunchKernelGGL((kunitig_ends_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, Op::ends(pr), s);
+            hipLaunchKernelGGL((kedit_decide_kernel<NW, Op>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
+            hipLaunchKernelGGL((kedit_apply_kernel<NW, Op>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
         }))
         return rc;
-    hipLaunchKernelGGL(ktip_totals_kernel, dim3(1), dim3(64), 0, st, s, d_totals);
+    hipLaunchKernelGGL(kedit_totals_kernel, dim3(1), dim3(64), 0, st, s, d_totals);
     KIDX_HIP(hipGetLastError());
     return kidx_scratch_end(ix->uni, st);
 }
-}  // namespace
-
-int ktip_device_clip(::pg_kindex* ix, const KtipParams& pr, uint64_t* d_totals, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const KidxRank& t = ix->ranks[0];
-    const int K = ix->K;
-    const uint64_t mask = t.slots - 1;
-    return kidx_graph_round(ix, KunitigParams{pr.min_cov, pr.min_arc, pr.max_tip}, d_totals, stream, [&](auto nw, dim3 start_grid, dim3 block, const KunitigScratch& s) {
-        constexpr int NW = decltype(nw)::value;
-        hipLaunchKernelGGL((ktip_decide_kernel<NW>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
-        hipLaunchKernelGGL((ktip_apply_kernel<NW>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
-    });
-}
-
-// ---- the bubbles ----
-// One round, as the tips': the unitigs' ends sweep, decide, apply, the totals, in the unitigs' scratch, on the caller's stream with no
-// host wait
-int kbubble_device_pop(::pg_kindex* ix, const KbubbleParams& pr, uint64_t* d_totals, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const KidxRank& t = ix->ranks[0];
-    const int K = ix->K;
-    const uint64_t mask = t.slots - 1;
-    return kidx_graph_round(ix, KunitigParams{pr.min_cov, pr.min_arc, pr.max_len}, d_totals, stream, [&](auto nw, dim3 start_grid, dim3 block, const KunitigScratch& s) {
-        constexpr int NW = decltype(nw)::value;
-        hipLaunchKernelGGL((kbubble_decide_kernel<NW>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
-        hipLaunchKernelGGL((kbubble_apply_kernel<NW>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
-    });
-}
+template int kedit_device_round<KtipOp>(::pg_kindex*, const KtipParams&, uint64_t*, void*);
+template int kedit_device_round<KbubbleOp>(::pg_kindex*, const KbubbleParams&, uint64_t*, void*);
 
 // ---- the corrector on an index cut over ranks ----
 namespace {

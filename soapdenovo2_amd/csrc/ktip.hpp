@@ -37,18 +37,15 @@
 // their two ends can make y a member of another tip.  The result is still one: that tip's walk reads y's out-half, the atomicAnd clears
 // a counter of its in-half that was below min_arc already, and a zeroed word stays zero under the AND in either order.)
 //
-// One piece of PG_HD code for the kernels (kindex_kernels.hip: ktip_decide_kernel, ktip_apply_kernel) and the host twin
-// (ktip_host.cpp): ktip_decide reads, ktip_apply writes through two functions of the caller.  Loop state is kept with selects
-// (DESIGN.md §11 on what stores under branches inside such a loop became).
+// One piece of PG_HD code for the round's kernels (kindex_kernels.hip: kedit_decide_kernel, kedit_apply_kernel) and its host twin
+// (kedit_host.cpp), which see it as KtipOp (kedit.hpp): ktip_decide reads, ktip_apply writes through two functions of the caller.  Loop
+// state is kept with selects (DESIGN.md §11 on what stores under branches inside such a loop became).
 #pragma once
-#include "kunitig.hpp"
+#include "kedit.hpp"
 
 namespace pg {
 
 constexpr uint32_t KTIP_MAX_TIP = 1u << 16;
-constexpr int KTIP_TOTALS = 4;
-// out_totals
-enum : int { KTIP_T_TIPS = 0, KTIP_T_KMERS = 1, KTIP_T_SOLID = 2, KTIP_T_KEPT = 3 };
 
 struct KtipParams {
     uint32_t min_cov, min_arc, max_tip;
@@ -56,16 +53,10 @@ struct KtipParams {
 
 PG_HD bool ktip_free(uint32_t reason) { return reason == KWALK_DEAD_END || reason == KWALK_WEAK_NEXT; }
 
-// the in-counter for base a of a node whose canonical form has word w: which 32-bit half of w (0 the low one), and which of its four
-PG_HD int ktip_in_half(bool fwd) { return fwd ? 0 : 1; }
-PG_HD int ktip_in_index(bool fwd, int a) { return fwd ? a : a ^ 2; }
-// what the atomicAnd leaves of that half: everything but the counter
-PG_HD uint32_t ktip_keep_mask(bool fwd, int a) { return ~(63u << (6 * ktip_in_index(fwd, a))); }
-
 // the minor test on the junction's word: c_t strictly below the largest of the other three in-counters
 PG_HD bool ktip_minor(uint64_t w, bool fwd, int a) {
-    const uint32_t half = ktip_in_half(fwd) ? (uint32_t)(w >> 32) : (uint32_t)w;
-    const int t = ktip_in_index(fwd, a);
+    const uint32_t half = kedit_in_half(fwd) ? (uint32_t)(w >> 32) : (uint32_t)w;
+    const int t = kedit_in_index(fwd, a);
     uint32_t c_t = 0, other = 0;
 #pragma unroll
     for (int b = 0; b < 4; b++) {
@@ -76,36 +67,21 @@ PG_HD bool ktip_minor(uint64_t w, bool fwd, int a) {
     return c_t < other;
 }
 
-// What the decide pass says of a start: n k-mers walked; candidate: free on the left, BRANCH_IN on the right, n <= max_tip; minor:
-// a candidate that is clipped
-struct KtipDecision {
-    uint32_t n;
-    bool candidate, minor;
-};
-
-// The decision for the start x0 whose left side has reason `left`: at most max_tip k-mers to the right through open sides.  Only reads
+// The decision for the start x0 whose left side has reason `left`: at most max_tip k-mers to the right through open sides; candidate:
+// free on the left, BRANCH_IN on the right, n <= max_tip.  Only reads
 template <int NW, typename Find>
-PG_HD KtipDecision ktip_decide(const KwalkNode<NW>& x0, uint32_t left, int K, const KtipParams& pr, Find find) {
-    const Kmer<NW> filter = kmer_filter<NW>(K);
-    const KunitigParams up{pr.min_cov, pr.min_arc, pr.max_tip};
-    KwalkNode<NW> x = x0, y = x0;
-    uint32_t n = 1, reason = ktip_free(left) ? 0 : KUNITIG_CUT;
-    while (!reason) {
-        int base = 0;
-        reason = kunitig_side<NW>(x, K, filter, up, find, y, base);               // (BRANCH_IN: y is the junction, its word in hand)
-        reason = !reason && n == pr.max_tip ? KUNITIG_CUT : reason;
-        if (reason) break;
-        n++;
-        x = y;
-    }
-    const bool candidate = reason == KWALK_BRANCH_IN;
+PG_HD KeditDecision ktip_decide(const KwalkNode<NW>& x0, uint32_t left, int K, const KtipParams& pr, Find find) {
+    if (!ktip_free(left)) return KeditDecision{1, false, false};
+    KwalkNode<NW> x = x0, y;
+    const KeditPath P = kedit_path<NW>(x, y, K, kmer_filter<NW>(K), KunitigParams{pr.min_cov, pr.min_arc, pr.max_tip}, find);
+    const bool candidate = P.reason == KWALK_BRANCH_IN;                          // (y is the junction, its word in hand)
     const int a = (int)(x.b.w[NW - 1] & 3) ^ 2;                                  // (x's first base: the complement of its reverse complement's last)
-    return KtipDecision{n, candidate, candidate && ktip_minor(y.w, y.fwd, a)};
+    return KeditDecision{P.n, candidate, candidate && ktip_minor(y.w, y.fwd, a)};
 }
 
 // The minor tip of n k-mers from x0 applied: every k-mer's successor is named by the single out arc of the k-mer's own word and looked
 // up -- find(ck, slot) = kunitig_probe --, then zero(slot) is called for the k-mer just left; behind the n-th, clear(slot, fwd, a)
-// for the junction, which takes the counter ktip_keep_mask(fwd, a) leaves out from half ktip_in_half(fwd) of its word
+// for the junction, which takes the counter kedit_keep_mask(fwd, a) leaves out from half kedit_in_half(fwd) of its word
 template <int NW, typename Find, typename Zero, typename Clear>
 PG_HD void ktip_apply(const KwalkNode<NW>& x0, uint32_t n, int K, const KtipParams& pr, Find find, Zero zero, Clear clear) {
     const Kmer<NW> filter = kmer_filter<NW>(K);
@@ -124,7 +100,19 @@ PG_HD void ktip_apply(const KwalkNode<NW>& x0, uint32_t n, int K, const KtipPara
     clear(x.slot, x.fwd, a);
 }
 
-// The caller's side of the device engine (kindex_kernels.hip), one round, asynchronous on `stream`
-int ktip_device_clip(::pg_kindex* ix, const KtipParams& pr, uint64_t* d_totals, void* stream);
+// The tips as the round sees them (kedit.hpp)
+struct KtipOp {
+    using Params = KtipParams;
+    static PG_HD KunitigParams ends(const Params& pr) { return KunitigParams{pr.min_cov, pr.min_arc, pr.max_tip}; }
+    static PG_HD bool starts(uint32_t left) { return ktip_free(left); }
+    template <int NW, typename Find>
+    static PG_HD KeditDecision decide(const KwalkNode<NW>& x0, uint32_t left, int K, const Params& pr, Find find) {
+        return ktip_decide<NW>(x0, left, K, pr, find);
+    }
+    template <int NW, typename Find, typename Zero, typename Clear>
+    static PG_HD void apply(const KwalkNode<NW>& x0, uint32_t n, int K, const Params& pr, Find find, Zero zero, Clear clear) {
+        ktip_apply<NW>(x0, n, K, pr, find, zero, clear);
+    }
+};
 
 }  // namespace pg

@@ -38,49 +38,18 @@ FLANK = 40                                    # path k-mers before a design's fi
 
 class Bubbler(TC.Clipper):
     """ktip_cases.Clipper -- the index under test, its model, maybe a twin, the word of every original key -- with a round of bubbles
-    beside the round of tips.  sources: sequences that hold every k-mer of the records, so that a large set's batch is cut from them
-    and not unpacked key by key."""
-
-    def __init__(self, records, K, mer127, device, twin=None, sources=()):
-        self.K, self.mer127, self.device = K, mer127, device
-        self.nw = 4 if mer127 else 2
-        self.model = M.Model.from_records(records, K, self.nw)
-        self.keys = sorted(set(self.model.cnt) | self.model.deleted)
-        text = {}
-        for s in sources:
-            for j, k in enumerate(M.canonical_kmers(s, K)):
-                text.setdefault(k, s[j:j + K])
-        self.batch = api.pack_seqs_ragged([text[k] if k in text else E.codes_of_key(k, K) for k in self.keys], K)
-        self.ix = api.KmerIndex.from_records(records, K, mer127, device)
-        self.twin = api.KmerIndex.from_records(records, K, mer127, twin) if twin is not None else None
+    beside the round of tips."""
 
     def pop_call(self, min_cov, min_arc, max_len, max_diff, totals, ix=None):
         ix = ix or self.ix
         return api.lib().pg_kindex_pop_bubbles(ix.h, min_cov, min_arc, max_len, max_diff, ix._ptr(totals), ix._stream())
 
     def pop(self, min_cov, min_arc, max_len, max_diff=0, what=""):
-        """One round of bubbles: (totals, removed keys, cleared counters as (junction key, half, counter)) after every comparison."""
-        before = self.words()
-        assert (before == self.want_words()).all(), what
-        totals = self.totals()
-        assert self.pop_call(min_cov, min_arc, max_len, max_diff, totals) == 0, api.lib().pg_last_error()
-        got = [int(v) for v in self.down(self.ix, totals)]
-        want, removed, cleared = B.pop_round(self.model, min_cov, min_arc, max_len, max_diff)
-        assert got == want, "%s: totals %s, the model's %s" % (what, got, want)
-        if self.twin is not None:
-            t = self.totals(self.twin)
-            assert self.pop_call(min_cov, min_arc, max_len, max_diff, t, self.twin) == 0, api.lib().pg_last_error()
-            assert [int(v) for v in self.down(self.twin, t)] == got, what + ": the device's totals differ from the host twin's"
-        self.compare(before, removed, cleared, what)
-        return got, removed, cleared
+        """One round of bubbles, as Clipper._round returns it."""
+        return self._round(self.pop_call, B.pop_round, (min_cov, min_arc, max_len, max_diff), what)
 
     def pop_settle(self, min_cov, min_arc, max_len, max_diff=0, what=""):
-        """Rounds of bubbles to the fixed point: the list of their totals, the empty one included."""
-        out = []
-        while not out or out[-1][0]:
-            out.append(self.pop(min_cov, min_arc, max_len, max_diff, "%s round %d" % (what, len(out) + 1))[0])
-            assert len(out) <= 64
-        return out
+        return self._settle(lambda w: self.pop(min_cov, min_arc, max_len, max_diff, w), what)
 
     def simplify_by_rounds(self, min_cov, min_arc, max_tip, max_len, max_diff=0, what=""):
         """KmerIndex.simplify's order of calls made one ABI round at a time, each compared: the list of (name, totals)."""

@@ -41,12 +41,16 @@ class Clipper:
     """An index under test with its model and, maybe, a twin index: device = -1 the host twin over numpy, else the device build over
     torch tensors.  A round goes straight to pg_kindex_clip_tips with a totals buffer pre-filled with FILL."""
 
-    def __init__(self, records, K, mer127, device, twin=None):
+    def __init__(self, records, K, mer127, device, twin=None, sources=()):
         self.K, self.mer127, self.device = K, mer127, device
         self.nw = 4 if mer127 else 2
         self.model = M.Model.from_records(records, K, self.nw)
         self.keys = sorted(set(self.model.cnt) | self.model.deleted)            # every key of the original set
-        self.batch = api.pack_seqs_ragged([E.codes_of_key(k, K) for k in self.keys], K)
+        text = {}                                   # (sources: sequences that hold the records' k-mers, so that a large set's batch
+        for s in sources:                           # is cut from them and not unpacked key by key)
+            for j, k in enumerate(M.canonical_kmers(s, K)):
+                text.setdefault(k, s[j:j + K])
+        self.batch = api.pack_seqs_ragged([text[k] if k in text else E.codes_of_key(k, K) for k in self.keys], K)
         self.ix = api.KmerIndex.from_records(records, K, mer127, device)
         self.twin = api.KmerIndex.from_records(records, K, mer127, twin) if twin is not None else None
 
@@ -102,29 +106,38 @@ class Clipper:
         if self.twin is not None:
             assert (self.words(self.twin) == after).all(), what + ": the device differs from the host twin"
 
-    def round(self, min_cov, min_arc, max_tip=MAX_TIP, what=""):
-        """One round: (totals, removed keys, cleared counters as (junction key, half, counter)) after every comparison."""
+    def _round(self, call, model_round, args, what):
+        """One round of an operator -- call(*args, totals, ix=None) its ABI entry, model_round(model, *args) its model --: (totals,
+        removed keys, cleared counters as (junction key, half, counter)) after every comparison."""
         before = self.words()
         assert (before == self.want_words()).all(), what
         totals = self.totals()
-        assert self.call(min_cov, min_arc, max_tip, totals) == 0, api.lib().pg_last_error()
+        assert call(*args, totals) == 0, api.lib().pg_last_error()
         got = [int(v) for v in self.down(self.ix, totals)]
-        want, removed, cleared = T.clip_round(self.model, min_cov, min_arc, max_tip)
+        want, removed, cleared = model_round(self.model, *args)
         assert got == want, "%s: totals %s, the model's %s" % (what, got, want)
         if self.twin is not None:
             t = self.totals(self.twin)
-            assert self.call(min_cov, min_arc, max_tip, t, self.twin) == 0, api.lib().pg_last_error()
+            assert call(*args, t, self.twin) == 0, api.lib().pg_last_error()
             assert [int(v) for v in self.down(self.twin, t)] == got, what + ": the device's totals differ from the host twin's"
         self.compare(before, removed, cleared, what)
         return got, removed, cleared
 
-    def settle(self, min_cov, min_arc, max_tip=MAX_TIP, what=""):
-        """Rounds to the fixed point: the list of their totals, the empty one included."""
+    @staticmethod
+    def _settle(one_round, what):
+        """Rounds to the fixed point -- one_round(what) makes one --: the list of their totals, the empty one included."""
         out = []
         while not out or out[-1][0]:
-            out.append(self.round(min_cov, min_arc, max_tip, "%s round %d" % (what, len(out) + 1))[0])
+            out.append(one_round("%s round %d" % (what, len(out) + 1))[0])
             assert len(out) <= 64
         return out
+
+    def round(self, min_cov, min_arc, max_tip=MAX_TIP, what=""):
+        """One round of tips, as _round returns it."""
+        return self._round(self.call, T.clip_round, (min_cov, min_arc, max_tip), what)
+
+    def settle(self, min_cov, min_arc, max_tip=MAX_TIP, what=""):
+        return self._settle(lambda w: self.round(min_cov, min_arc, max_tip, w), what)
 
     def unitigs(self, min_cov, min_arc):
         """(sorted (text, left, right), totals as a dict) of the index as it stands."""

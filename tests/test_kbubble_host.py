@@ -1,15 +1,12 @@
-"""Bubble popping on the CPU: the host twin (pg_kindex_pop_bubbles on a device = -1 index: csrc/kbubble_host.cpp, the rule the kernels
+"""Bubble popping on the CPU: the host twin (pg_kindex_pop_bubbles on a device = -1 index: csrc/kedit_host.cpp, the rule the kernels
 share in csrc/kbubble.hpp) against the independent model (tests/kbubble_model.py) on the designs of tests/kbubble_cases.py -- each also
 against what its construction dictates: the totals and the word of every key of the original set after every round --, every refusal,
-KmerIndex.pop_bubbles and KmerIndex.simplify, and under -fsanitize=address,undefined in a stand-alone program.
-tests/test_gpu_kbubble.py runs the same through the kernels.  All comparisons are of integers and exact."""
-import os
-import subprocess
-
+KmerIndex.pop_bubbles and KmerIndex.simplify.  The stand-alone program under -fsanitize=address,undefined is the tips' and the bubbles'
+in one (tests/kedit_asan.cpp, built and run by tests/test_ktip_host.py).  tests/test_gpu_kbubble.py runs the same through the kernels.
+All comparisons are of integers and exact."""
 import pytest
 
 import kbubble_cases as G
-from conftest import ROOT
 
 
 @pytest.mark.parametrize("flavour", G.FLAVOURS, ids=G.flavour_id)
@@ -29,18 +26,3 @@ def test_host_twin_matches_model_and_design(design, flavour):
 def test_refusals(flavour):
     G.check_refusals(flavour[0], flavour[1], -1, (-1, -1))
 
-
-# ---- the host twin under the sanitizers, in a program of its own ----
-def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
-    """tests/kbubble_asan.cpp: both flavours, three arms of one bubble and a bubble on an arm, popped by rounds to the fixed point and
-    checked against the construction -- compiled with the host twin's sources and -fsanitize=address,undefined, and run.  Nothing loaded
-    into Python is sanitised."""
-    exe = str(tmp_path / "kbubble_asan")
-    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kbubble_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           os.path.join(csrc, "kunitig_host.cpp"), os.path.join(csrc, "kbubble_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "kbubble host twin: ok" in ran.stdout, ran.stdout + ran.stderr

@@ -1,4 +1,4 @@
-"""Tip clipping on the CPU: the host twin (pg_kindex_clip_tips on a device = -1 index: csrc/ktip_host.cpp, the rule the kernels share in
+"""Tip clipping on the CPU: the host twin (pg_kindex_clip_tips on a device = -1 index: csrc/kedit_host.cpp, the rule the kernels share in
 csrc/ktip.hpp) against the independent model (tests/ktip_model.py) on the designs of tests/ktip_cases.py -- each also against what its
 construction dictates: the totals and the word of every key of the original set after every round --, every refusal, KmerIndex.clip_tips,
 and under -fsanitize=address,undefined in a stand-alone program.  tests/test_gpu_ktip.py runs the same through the kernels.  All
@@ -31,15 +31,16 @@ def test_refusals(flavour):
 
 # ---- the host twin under the sanitizers, in a program of its own ----
 def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
-    """tests/ktip_asan.cpp: both flavours, a path with one-k-mer tips and a tip on a tip, clipped by rounds to the fixed point and
-    checked against the construction -- compiled with the host twin's sources and -fsanitize=address,undefined, and run.  Nothing loaded
-    into Python is sanitised."""
-    exe = str(tmp_path / "ktip_asan")
+    """tests/kedit_asan.cpp, the tips' and the bubbles' designs in one program over the one host twin: both flavours, a path with
+    one-k-mer tips and a tip on a tip, clipped by rounds to the fixed point, then three arms of one bubble and a bubble on an arm, popped
+    by rounds to theirs, each checked against the construction -- compiled with the host twin's sources and
+    -fsanitize=address,undefined, and run.  Nothing loaded into Python is sanitised."""
+    exe = str(tmp_path / "kedit_asan")
     csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "ktip_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           os.path.join(csrc, "kunitig_host.cpp"), os.path.join(csrc, "ktip_host.cpp"), "-o", exe]
+           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kedit_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
+           os.path.join(csrc, "kunitig_host.cpp"), os.path.join(csrc, "kedit_host.cpp"), "-o", exe]
     built = subprocess.run(cmd, capture_output=True, text=True)
     assert built.returncode == 0, built.stderr
     ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "ktip host twin: ok" in ran.stdout, ran.stdout + ran.stderr
+    assert ran.returncode == 0 and "ktip host twin: ok" in ran.stdout and "kbubble host twin: ok" in ran.stdout, ran.stdout + ran.stderr
