@@ -609,7 +609,36 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       PG_EINVAL: a threshold, max_len or max_diff out of range, out_totals null; PG_ESTATE: an index cut over ranks;
  *                       nothing is written then and the index is untouched.  Device memory of the index's device, asynchronous on
  *                       `stream`, no host wait; the scratch is pg_kindex_unitigs'.  Host memory for a host-twin index.  Not done: a
- *                       cut index, alternatives that are not simple, a comparison of the branches' bases.
+ *                       cut index, a comparison of the branches' bases; alternatives that are not simple are pg_kindex_pop_bulges'.
+ *   pg_kindex_drop_weak_arcs     one round that drops the arcs to weak k-mers from the graph of the index (csrc/karc.hpp).  Solid, the
+ *                       arc sets, the end reasons, min_cov (1..255) and min_arc (1..63) are pg_kindex_unitigs'.  The arc of a solid
+ *                       oriented k-mer r by base b, its out-counter in r's word at least min_arc, is dangling when next(r, b) is not
+ *                       solid: no record, a word of 0 (a tombstone), or coverage below min_cov.  The round decides over the index
+ *                       as it stood when it began, then sets every dangling arc's out-counter to 0, in r's own word only: the weak
+ *                       k-mer's word and every counter below min_arc stay as they are, no k-mer is removed, and no k-mer's being
+ *                       solid changes, so a second round finds nothing.  A side can hold a dangling arc only if its reason is 4
+ *                       branch out or 5 weak next.  out_totals[4], always written: [0] sides pruned, [1] arcs cleared (at most 4 a
+ *                       side), [2] solid k-mers before the round, [3] sides kept: those of reason 4 or 5 with no dangling arc.
+ *                       PG_EINVAL: a threshold out of range, out_totals null; PG_ESTATE: an index cut over ranks; nothing is
+ *                       written then and the index is untouched.  Device memory of the index's device, asynchronous on `stream`, no
+ *                       host wait; the scratch is pg_kindex_unitigs'.  Host memory for a host-twin index.  Not done: a cut index.
+ *   pg_kindex_pop_bulges         one round of bubble popping on strongest paths (csrc/kbulge.hpp).  The arm P = x0 -> .. -> x(n-1),
+ *                       its fork u, its join v, L, max_len (1 .. 2^16) and max_diff (0 .. 2^16) are pg_kindex_pop_bubbles' branch.
+ *                       A step x -> y is strong when b is the one base whose out-counter in x's word is at least min_arc and
+ *                       strictly greater than the other three (a single arc qualifies), y = next(x, b) is solid, canon(y) !=
+ *                       canon(x), and in y's word the in-counter for x's first base is at least min_arc and strictly greater than
+ *                       y's other three in-counters: raw counters, and ties end the path.  x -> y is strong exactly when rc(y) ->
+ *                       rc(x) is, a k-mer has at most one strong successor and one strong predecessor, and an open step is strong.
+ *                       The strongest path S starts at u and takes strong steps; it succeeds when it reaches v, the same k-mer in
+ *                       the same orientation, with m k-mers strictly between, and fails when there is no strong step, when it
+ *                       reaches u's k-mer or v's in the other orientation, or when m would exceed n + max_diff.  P is minor, and
+ *                       popped, iff S succeeds, m >= 1, S's first k-mer is not x0, |n - m| <= max_diff and cov_P m < cov_S n in
+ *                       64-bit integers, the sums over the k-mers strictly between u and v.  No k-mer of any S is removed in the
+ *                       round that uses it (csrc/kbulge.hpp has the argument), so u stays connected to v.  Decided once an arm,
+ *                       over the index as it stood when the round began; applied as pg_kindex_pop_bubbles applies a branch.
+ *                       out_totals[4], always written: [0] arms popped, [1] k-mers removed, [2] solid k-mers before the round,
+ *                       [3] arms kept.  Call rounds until out_totals[0] == 0.  PG_EINVAL, PG_ESTATE, the memory and the stream are
+ *                       pg_kindex_pop_bubbles'.  Not done: a cut index, a comparison of the arms' bases, a choice among tied paths.
  *   pg_kindex_correct_rows       pg_kindex_correct on any index, by rounds over merged rows (csrc/kcorrect_rows.hpp).  The batch, its
  *                       tail, n_words and n_kmers are pg_kindex_query_words' and pg_kindex_trim's; packed_out, out_report, in-place
  *                       use, the report word, the rule and the argument errors are pg_kindex_correct's, and so is the result, bit for
@@ -656,6 +685,9 @@ int pg_kindex_unitigs(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_
 int pg_kindex_clip_tips(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_tip, uint64_t *out_totals, void *stream);
 int pg_kindex_pop_bubbles(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_len, uint32_t max_diff, uint64_t *out_totals,
                           void *stream);
+int pg_kindex_drop_weak_arcs(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint64_t *out_totals, void *stream);
+int pg_kindex_pop_bulges(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_len, uint32_t max_diff, uint64_t *out_totals,
+                         void *stream);
 int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
 void pg_kindex_destroy(pg_kindex *ix);
 uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */

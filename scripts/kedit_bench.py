@@ -12,12 +12,17 @@ each.  --runs runs after one warm-up run.  No rate is asserted anywhere.
     --op bubbles   pg_kindex_clip_tips and pg_kindex_pop_bubbles round by round in KmerIndex.simplify's order.  The first
                    run compacts the graph as built and after the tips' first fixed point, the last one after the whole simplification:
                    the unitig count, N50, longest unitig and side reasons at the three places.  Writes profiles/kbubble.json.
+    --op arcs      pg_kindex_drop_weak_arcs alone, round by round.  Writes profiles/karc.json.
+    --op bulges    pg_kindex_pop_bulges alone, round by round.  Writes profiles/kbulge.json.
+    --op all       the four operators in the order of KmerIndex.simplify(ops=("arcs", "tips", "bubbles", "bulges")): per-call times and
+                   totals, every operator's first and first empty round as a ratio of the count call, then the unitigs, N50 and longest
+                   unitig of the simplified index with its count call and full call timed.  Writes profiles/kedit_ops.json.
 
 Every setting is measured by a child process of its own under a time limit (--limit seconds; the parent does not touch the GPU), and the
 first child that fails or runs out of time ends the script: nothing more is started on the card after it.  Needs a GPU; nothing falls back.
 
-    python scripts/kedit_bench.py --op tips|bubbles [--reads 10000000] [--setting 3:2] [--max-tip 62] [--max-len 62] [--max-diff 0]
-                                  [--runs 3] [--limit 900] [--out profiles/ktip.json|profiles/kbubble.json]
+    python scripts/kedit_bench.py --op tips|bubbles|arcs|bulges|all [--reads 10000000] [--setting 3:2] [--max-tip 62] [--max-len 62] [--max-diff 0]
+                                  [--runs 3] [--limit 900] [--out profiles/NAME.json]
 """
 import argparse
 import json
@@ -40,12 +45,19 @@ NOT_MEASURED = {
                 "max_diff > 0 on reads with insertions and deletions (the simulated errors are substitutions: every bubble has arms of K and K)",
                 REPEATS, "the idle share of lanes in the decide pass (a start whose left side is not BRANCH_IN ends at once, a branch's deciding "
                 "start walks its arm and up to three siblings: no counters were collected and no estimate made)", ONE_CARD]}
+for _op in ("arcs", "bulges", "all"):
+    NOT_MEASURED[_op] = ["the 127-mer build (K > 63: slots of 48 bytes, four-word keys)", "max_diff > 0 on reads with insertions and deletions",
+                         REPEATS, "the idle share of lanes in the decide passes (no counters were collected and no estimate made)", ONE_CARD]
+GENERIC_SUMMARY = ("calls_needed", "median_unitigs_count_call_seconds", "first_round_over_count_call", "median_all_calls_seconds", "unitigs", "n50_bases",
+                   "longest_bases", "unitigs_count_call_after_seconds", "unitigs_full_call_after_seconds")
 # the calls of one cycle, in order; the summary fields printed at the end
 OPS = {"tips": (("tips",), ("rounds_needed", "median_unitigs_count_call_seconds", "median_first_round_seconds", "median_all_rounds_seconds",
                             "first_round_over_count_call")),
        "bubbles": (("tips", "bubbles"), ("calls_needed", "median_unitigs_count_call_seconds", "median_first_popping_round_seconds",
                                          "median_first_empty_bubble_round_seconds", "popping_round_over_count_call", "empty_round_over_count_call",
-                                         "median_all_calls_seconds"))}
+                                         "median_all_calls_seconds")),
+       "arcs": (("arcs",), GENERIC_SUMMARY), "bulges": (("bulges",), GENERIC_SUMMARY), "all": (("arcs", "tips", "bubbles", "bulges"), GENERIC_SUMMARY)}
+DEFAULT_OUT = {"tips": "ktip.json", "bubbles": "kbubble.json", "arcs": "karc.json", "bulges": "kbulge.json", "all": "kedit_ops.json"}
 
 
 def n50(lens):
@@ -103,6 +115,12 @@ def child(a):
         if name == "tips":
             sec = timed(lambda: L_.pg_kindex_clip_tips(ix.h, min_cov, min_arc, a.max_tip, ix._ptr(t4), ix._stream()))
             return dict(api.tip_fields(t4), call="tips", removed=int(api.tip_fields(t4)["tips"]), seconds=sec)
+        if name == "arcs":
+            sec = timed(lambda: L_.pg_kindex_drop_weak_arcs(ix.h, min_cov, min_arc, ix._ptr(t4), ix._stream()))
+            return dict(api.arc_fields(t4), call="arcs", removed=int(api.arc_fields(t4)["sides"]), seconds=sec)
+        if name == "bulges":
+            sec = timed(lambda: L_.pg_kindex_pop_bulges(ix.h, min_cov, min_arc, a.max_len, a.max_diff, ix._ptr(t4), ix._stream()))
+            return dict(api.bulge_fields(t4), call="bulges", removed=int(api.bulge_fields(t4)["arms"]), seconds=sec)
         sec = timed(lambda: L_.pg_kindex_pop_bubbles(ix.h, min_cov, min_arc, a.max_len, a.max_diff, ix._ptr(t4), ix._stream()))
         return dict(api.bubble_fields(t4), call="bubbles", removed=int(api.bubble_fields(t4)["branches"]), seconds=sec)
 
@@ -125,7 +143,7 @@ def child(a):
                     assert len(calls) <= 64
                     if not calls[-1]["removed"]:
                         break
-                if i == 0 and name == "tips" and cycles == 0 and len(names) > 1:
+                if i == 0 and name == "tips" and cycles == 0 and a.op == "bubbles":
                     tips_only = compaction(ix)
             cycles += 1
             if len(names) == 1:                                        # (one operator: its fixed point is the whole of it)
@@ -133,7 +151,7 @@ def child(a):
         if i == a.runs:
             last = compaction(ix)
         ix.close()
-        print(f"[{a.child}] run {i}: count call {yard:.4f} s, {len(calls)} calls " + " ".join(f"{c['call'][0]}{c['seconds']:.4f}" for c in calls), flush=True)
+        print(f"[{a.child}] run {i}: count call {yard:.4f} s, {len(calls)} calls " + " ".join(f"{'g' if c['call'] == 'bulges' else c['call'][0]}{c['seconds']:.4f}" for c in calls), flush=True)
         if i:
             runs.append({"unitigs_count_call_seconds": yard, "calls": calls})
     kc.close()
@@ -147,6 +165,21 @@ def child(a):
         res.update({"max_kmers": a.max_kmers, "index": info, "runs": runs, "rounds_needed": len(runs[0]["rounds"]),
                     "median_unitigs_count_call_seconds": yard, "median_first_round_seconds": first, "median_all_rounds_seconds": total,
                     "first_round_over_count_call": first / yard, "unitigs_before": built, "unitigs_after": last})
+    elif a.op in ("arcs", "bulges", "all"):
+        # every operator's first round (the one on the index as the operators before it left it) and its last, empty one, as ratios of the yardstick
+        per_op = {}
+        for name in names:
+            firsts = [[c for c in r["calls"] if c["call"] == name][0] for r in runs]
+            empties = [[c for c in r["calls"] if c["call"] == name and not c["removed"]][0] for r in runs]
+            first, empty = float(np.median([c["seconds"] for c in firsts])), float(np.median([c["seconds"] for c in empties]))
+            per_op[name] = {"first_round": {k: v for k, v in firsts[0].items() if k != "seconds"}, "median_first_round_seconds": first,
+                            "first_round_over_count_call": first / yard, "median_first_empty_round_seconds": empty, "empty_round_over_count_call": empty / yard}
+        res.update({"max_len": a.max_len, "max_diff": a.max_diff, "max_kmers": a.max_kmers, "index": info, "runs": runs, "calls_needed": len(runs[0]["calls"]),
+                    "median_unitigs_count_call_seconds": yard, "operators": per_op,
+                    "first_round_over_count_call": {k: v["first_round_over_count_call"] for k, v in per_op.items()}, "median_all_calls_seconds": total,
+                    "unitigs_as_built": built, "unitigs_simplified": last, "unitigs": last["totals"]["unitigs"], "n50_bases": last["n50_bases"],
+                    "longest_bases": last["longest_bases"], "unitigs_count_call_after_seconds": last["count_seconds"],
+                    "unitigs_full_call_after_seconds": last["full_seconds"]})
     else:
         pick = lambda r, popping: [c["seconds"] for c in r["calls"] if c["call"] == "bubbles" and (c["removed"] > 0) == popping]
         popping = float(np.median([pick(r, True)[0] for r in runs if pick(r, True)])) if any(pick(r, True) for r in runs) else None
@@ -174,17 +207,24 @@ def main():
     ap.add_argument("--max-kmers", type=int, default=1 << 24)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--limit", type=int, default=900, help="seconds a setting's child process may take")
-    ap.add_argument("--out", default=None, help="default: profiles/ktip.json (--op tips), profiles/kbubble.json (--op bubbles)")
+    ap.add_argument("--out", default=None, help="default: profiles/ktip.json, kbubble.json, karc.json, kbulge.json, kedit_ops.json by --op")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child-out", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
         return child(a)
-    out_path = a.out or os.path.join(ROOT, "profiles", "ktip.json" if a.op == "tips" else "kbubble.json")
+    out_path = a.out or os.path.join(ROOT, "profiles", DEFAULT_OUT[a.op])
     reads = f"{a.reads} resident reads x {a.read_len} bp, genome {a.genome}, err {a.err}, K={a.kmer}, counted once and indexed afresh every run; "
     if a.op == "tips":
         what = (f"pg_kindex_clip_tips with max_tip {a.max_tip} round by round to the fixed point at each min_cov:min_arc, beside the "
                 f"unitigs' count call (max_kmers {a.max_kmers}) on the index as built; the unitigs before the clipping and after it")
+    elif a.op in ("arcs", "bulges", "all"):
+        entries = {"arcs": "pg_kindex_drop_weak_arcs", "tips": f"pg_kindex_clip_tips (max_tip {a.max_tip})",
+                   "bubbles": f"pg_kindex_pop_bubbles (max_len {a.max_len}, max_diff {a.max_diff})",
+                   "bulges": f"pg_kindex_pop_bulges (max_len {a.max_len}, max_diff {a.max_diff})"}
+        what = (", ".join(entries[n] for n in OPS[a.op][0]) + " round by round in KmerIndex.simplify's order to the fixed point at each "
+                f"min_cov:min_arc, beside the unitigs' count call (max_kmers {a.max_kmers}) on the index as built; the unitigs as built and "
+                "afterwards, their count call and full call timed")
     else:
         what = (f"pg_kindex_clip_tips (max_tip {a.max_tip}) and pg_kindex_pop_bubbles (max_len {a.max_len}, max_diff {a.max_diff}) round by "
                 f"round in KmerIndex.simplify's order to the fixed point at each min_cov:min_arc, beside the unitigs' count call (max_kmers "

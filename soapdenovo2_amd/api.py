@@ -191,6 +191,8 @@ def lib() -> C.CDLL:
     L.pg_kindex_unitigs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p, u64p, C.c_void_p]
     L.pg_kindex_clip_tips.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
     L.pg_kindex_pop_bubbles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
+    L.pg_kindex_drop_weak_arcs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
+    L.pg_kindex_pop_bulges.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
     L.pg_kindex_info.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_destroy.argtypes = [C.c_void_p]
     L.pg_kindex_destroy.restype = None
@@ -226,7 +228,7 @@ EXPORTED_SYMBOLS = [
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
     "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times", "pg_kindex_correct_rows", "pg_kindex_correct_rows_stats",
-    "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_clip_tips", "pg_kindex_pop_bubbles",
+    "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_clip_tips", "pg_kindex_pop_bubbles", "pg_kindex_drop_weak_arcs", "pg_kindex_pop_bulges",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
@@ -971,6 +973,24 @@ def bubble_fields(totals) -> dict:
     return _edit_fields(BUBBLE_TOTALS_FIELDS, totals)
 
 
+# The arcs (pg_kindex_drop_weak_arcs) and the bulges (pg_kindex_pop_bulges, whose bounds are the bubbles').
+ARC_TOTALS_FIELDS = ["sides", "arcs", "solid", "kept"]
+BULGE_TOTALS_FIELDS = ["arms", "kmers", "solid", "kept"]
+SIMPLIFY_OPS = ("arcs", "tips", "bubbles", "bulges")          # every operator simplify knows, in the order of the full set
+
+
+def arc_fields(totals) -> dict:
+    """A round's totals (pg_kindex_drop_weak_arcs) by name: `sides` pruned, `arcs` cleared, `solid` k-mers before the round, and the
+    sides `kept`: those with several arcs out none of which dangles.  Takes a numpy array or a torch tensor of 4 words."""
+    return _edit_fields(ARC_TOTALS_FIELDS, totals)
+
+
+def bulge_fields(totals) -> dict:
+    """A round's totals (pg_kindex_pop_bulges) by name: `arms` popped, `kmers` removed, `solid` k-mers before the round, and the
+    arms `kept`.  Takes a numpy array or a torch tensor of 4 words."""
+    return _edit_fields(BULGE_TOTALS_FIELDS, totals)
+
+
 def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
     """pg_host_kindex_bytes: the table an index of n_records k-mers cuts (no GPU)."""
     return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
@@ -1305,16 +1325,45 @@ class KmerIndex:
         max_len = 2 * self.K if max_len is None else max_len
         return self._edit_rounds("pg_kindex_pop_bubbles", (min_cov, min_arc, max_len, max_diff), max_rounds)
 
-    def simplify(self, min_cov: int, min_arc: int, max_tip=None, max_len=None, max_diff: int = 0, max_rounds: int = 64) -> list:
-        """clip_tips to its fixed point, then pop_bubbles to its own, and both again -- a tip on a branch hides a bubble, a popped bubble
-        can leave a tip -- until a whole cycle removes nothing or max_rounds rounds were called in all.  Returns the rounds in call
-        order, a list of ("tips" | "bubbles", totals)."""
+    def drop_weak_arcs(self, min_cov: int, min_arc: int, max_rounds: int = 64) -> list:
+        """Arcs to weak k-mers dropped from the index's graph, in place (pg_kindex_drop_weak_arcs): an arc of a solid k-mer whose
+        counter is at least min_arc and whose target is not solid -- no such k-mer, a removed one, or coverage below min_cov -- gets
+        the counter 0 in the solid k-mer's own word.  No k-mer is removed and none changes between solid and weak, so the second round
+        finds nothing; rounds are called until one clears nothing or max_rounds is reached.  Returns the rounds' totals, a list of
+        numpy arrays of ARC_TOTALS_FIELDS (arc_fields names them).  An index cut over ranks is refused."""
+        return self._edit_rounds("pg_kindex_drop_weak_arcs", (min_cov, min_arc), max_rounds)
+
+    def pop_bulges(self, min_cov: int, min_arc: int, max_len=None, max_diff: int = 0, max_rounds: int = 64) -> list:
+        """Bubbles popped on their strongest paths, in place (pg_kindex_pop_bulges): an arm is pop_bubbles' branch, a chain of at most
+        max_len k-mers (default 2 K) between a fork and a join; it is removed when the walk from the fork along the strictly
+        strongest arc out of every k-mer, each also the strictly strongest arc into the next, reaches the join another way, with a
+        length within max_diff of the arm's and a strictly greater mean coverage.  That path need not be a simple chain -- two errors
+        less than K apart, a bubble or a tip on it --, it is never removed in the round that uses it, and ties end it, so the arm is
+        then kept.  Rounds are called until one pops nothing or max_rounds is reached.  Returns the rounds' totals, a list of numpy
+        arrays of BULGE_TOTALS_FIELDS (bulge_fields names them).  An index cut over ranks is refused."""
+        max_len = 2 * self.K if max_len is None else max_len
+        return self._edit_rounds("pg_kindex_pop_bulges", (min_cov, min_arc, max_len, max_diff), max_rounds)
+
+    def simplify(self, min_cov: int, min_arc: int, max_tip=None, max_len=None, max_diff: int = 0, max_rounds: int = 64,
+                 ops=("tips", "bubbles")) -> list:
+        """Every operator named in ops to its fixed point, in the order given, and all of them again -- a tip on a branch hides a
+        bubble, a popped bubble can leave a tip, a removed k-mer leaves its neighbours' arcs dangling -- until a whole cycle removes
+        nothing or max_rounds rounds were called in all.  ops: names of SIMPLIFY_OPS -- "arcs" (drop_weak_arcs), "tips" (clip_tips),
+        "bubbles" (pop_bubbles), "bulges" (pop_bulges); the default is the tips and the bubbles, SIMPLIFY_OPS itself the full set; a
+        name that is none of them raises ValueError.  Returns the rounds in call order, a list of (name, totals)."""
+        ops = tuple(ops)
+        for name in ops:
+            if name not in SIMPLIFY_OPS:
+                raise ValueError("KmerIndex.simplify: ops holds %r; the operators are %s" % (name, ", ".join(SIMPLIFY_OPS)))
+        run = {"arcs": lambda left: self.drop_weak_arcs(min_cov, min_arc, left), "tips": lambda left: self.clip_tips(min_cov, min_arc, max_tip, left),
+               "bubbles": lambda left: self.pop_bubbles(min_cov, min_arc, max_len, max_diff, left),
+               "bulges": lambda left: self.pop_bulges(min_cov, min_arc, max_len, max_diff, left)}
         out = []
         while len(out) < max_rounds:
             removed = 0
-            for name in ("tips", "bubbles"):
+            for name in ops:
                 left = max_rounds - len(out)
-                rounds = self.clip_tips(min_cov, min_arc, max_tip, left) if name == "tips" else self.pop_bubbles(min_cov, min_arc, max_len, max_diff, left)
+                rounds = run[name](left)
                 out += [(name, r) for r in rounds]
                 removed += sum(int(r[0]) for r in rounds)
             if not removed:

@@ -77,21 +77,41 @@ struct KbubbleParams {
 template <int NW>
 PG_HD KwalkNode<NW> kbubble_flip(const KwalkNode<NW>& x) { return KwalkNode<NW>{x.b, x.a, x.w, x.slot, !x.fwd}; }
 
+// Steps 1 and 2 of the decision, which the bulges (kbulge.hpp) share.  branch: the start is a branch in its deciding orientation, and then
+// v and L are its junctions; P.n is the k-mers walked (0: the left side is not BRANCH_IN)
+template <int NW>
+struct KbubbleArm {
+    bool branch;
+    KeditPath P;
+    KwalkNode<NW> v, L;
+};
+
+// The arm of the start x0 whose left side has reason `left`.  Only reads
+template <int NW, typename Find>
+PG_HD KbubbleArm<NW> kbubble_arm(const KwalkNode<NW>& x0, uint32_t left, int K, const Kmer<NW>& filter, const KunitigParams& up, Find find) {
+    KbubbleArm<NW> arm{};
+    if (left != KWALK_BRANCH_IN) return arm;
+    // 1. P, to v; decided from the start that is not greater
+    KwalkNode<NW> x = x0;
+    arm.P = kedit_path<NW>(x, arm.v, K, filter, up, find);
+    if (arm.P.reason != KWALK_BRANCH_IN || kmer_less<NW>(x.b, x0.a)) return arm;
+    // 2. L behind the left side, and the fork u = rc(L)
+    int base = 0;
+    const uint32_t behind = kunitig_side<NW>(kbubble_flip<NW>(x0), K, filter, up, find, arm.L, base);
+    arm.branch = behind == KWALK_BRANCH_IN && !kmer_eq<NW>(kwalk_canon<NW>(arm.L), kwalk_canon<NW>(arm.v));
+    return arm;
+}
+
 // The decision for the start x0 whose left side has reason `left`; candidate: a branch in its deciding orientation.  Only reads
 template <int NW, typename Find>
 PG_HD KeditDecision kbubble_decide(const KwalkNode<NW>& x0, uint32_t left, int K, const KbubbleParams& pr, Find find) {
     const Kmer<NW> filter = kmer_filter<NW>(K);
     const KunitigParams up{pr.min_cov, pr.min_arc, pr.max_len};
-    if (left != KWALK_BRANCH_IN) return KeditDecision{0, false, false};
-    // 1. P, to v; decided from the start that is not greater
-    KwalkNode<NW> x = x0, v;
-    const KeditPath P = kedit_path<NW>(x, v, K, filter, up, find);
-    if (P.reason != KWALK_BRANCH_IN || kmer_less<NW>(x.b, x0.a)) return KeditDecision{P.n, false, false};
-    // 2. L behind the left side, and the fork u = rc(L)
-    KwalkNode<NW> L;
+    const KbubbleArm<NW> arm = kbubble_arm<NW>(x0, left, K, filter, up, find);
+    if (!arm.branch) return KeditDecision{arm.P.n, false, false};
+    const KeditPath& P = arm.P;
+    const KwalkNode<NW>&v = arm.v, &L = arm.L;
     int base = 0;
-    const uint32_t behind = kunitig_side<NW>(kbubble_flip<NW>(x0), K, filter, up, find, L, base);
-    if (behind != KWALK_BRANCH_IN || kmer_eq<NW>(kwalk_canon<NW>(L), kwalk_canon<NW>(v))) return KeditDecision{P.n, false, false};
     const KwalkNode<NW> u = kbubble_flip<NW>(L);
     const uint32_t others = kwalk_out_set(u.w, u.fwd, pr.min_arc) & ~(1u << (int)(x0.a.w[NW - 1] & 3));
     bool minor = false;

@@ -1,8 +1,8 @@
-// kedit.hpp -- what the operators that write to the table of the k-mer index share: the tips (ktip.hpp) and the
-// bubbles (kbubble.hpp) today.  A ROUND of such an operator is the unitigs' ends sweep (kunitig.hpp: the start list), a decide pass that
+// kedit.hpp -- what the operators that write to the table of the k-mer index share: the tips (ktip.hpp),
+// the bubbles (kbubble.hpp), the arcs (karc.hpp) and the bulges (kbulge.hpp).  A ROUND of such an operator is the unitigs' ends sweep (kunitig.hpp: the start list), a decide pass that
 // only reads -- every start over the index as it stood when the round began --, an apply pass that writes, and four totals.  The round
 // exists once for the device (kindex_kernels.hip: kedit_decide_kernel, kedit_apply_kernel, kedit_device_round) and once for the host
-// (kedit_host.cpp: kedit_host_round); the operator is a stateless struct Op, and this is all of it that either sees:
+// (kedit_host.hpp: kedit_host_round); the operator is a stateless struct Op, and this is all of it that either sees:
 //     using Params                            the ABI entry's thresholds, passed to the kernels by value
 //     static KunitigParams ends(pr)           what the ends sweep runs with
 //     static bool starts(left)                the pre-filter on a start's left reason: any other start ends at once, its slot not even read

@@ -1,96 +1,11 @@
-// kedit_host.cpp -- the C ABI of the operators that edit the graph of the k-mer index, pg_kindex_clip_tips and pg_kindex_pop_bubbles
-// (include/soapdenovo2_amd.h section 3), and the round's host twin (a device = -1 index in one table): the operator's rule (kedit.hpp;
-// ktip.hpp, kbubble.hpp) over host memory, the kernels' passes one after the other -- ends, decide over every start, then apply: the
-// snapshot rule, not a sequential sweep --, every lookup kunitig_probe.  What the CPU tests run, and the kernels' yardstick.  A file of
-// its own beside kindex_host.cpp, as kunitig_host.cpp is: a program that links the index's host half alone with stubs for its device
-// engine keeps linking.
-#include <string>
-#include <vector>
-
-#include "../../include/soapdenovo2_amd.h"
+// kedit_host.cpp -- the C ABI of the first two operators that edit the graph of the k-mer index, pg_kindex_clip_tips and
+// pg_kindex_pop_bubbles (include/soapdenovo2_amd.h section 3), through the round's host half (kedit_host.hpp: the host twin, the
+// refusals, the dispatch).  A file of its own beside kindex_host.cpp, as kunitig_host.cpp is: a program that links the index's host half
+// alone with stubs for its device engine keeps linking -- and the later operators (kedit_ops_host.cpp) have a file of theirs for the
+// same reason: a program that links this file with stubs for these two operators' device rounds keeps linking too.
 #include "kbubble.hpp"
-#include "kindex.hpp"
+#include "kedit_host.hpp"
 #include "ktip.hpp"
-
-void pg_set_error(const std::string& s);
-
-namespace pg {
-namespace {
-
-template <int NW, class Op>
-void kedit_host_round(pg_kindex* ix, const typename Op::Params& pr, uint64_t* totals) {
-    constexpr int SW = map_slot_words<NW>();
-    const int K = ix->K;
-    KidxRank& t = ix->ranks[0];
-    uint64_t* tab = t.tab.data();
-    const uint64_t mask = t.slots - 1;
-    const KunitigParams up = Op::ends(pr);
-    std::vector<uint64_t> starts;
-    std::vector<uint32_t> lens;
-    auto find = [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); };
-    auto zero = [tab](uint64_t slot) { tab[slot * SW + NW] = 0; };
-    auto clear = [tab](uint64_t slot, bool fwd, int a) {
-        const uint64_t keep = (uint64_t)kedit_keep_mask(fwd, a);
-        tab[slot * SW + NW] &= kedit_in_half(fwd) ? keep << 32 | 0xffffffffull : keep | 0xffffffffull << 32;
-    };
-    auto node_of = [&](uint64_t start) {
-        const uint64_t* sl = tab + kunitig_start_slot(start) * SW;
-        return kunitig_node<NW>(kidx_record_key<NW>(sl), sl[NW], kunitig_start_slot(start), kunitig_start_fwd(start), K);
-    };
-    uint64_t solid = 0, removed = 0, kmers = 0, kept = 0;
-    // 1. the ends, as the unitigs find them: every end side of a solid k-mer is a start
-    for (uint64_t e = 0; e < t.slots; e++) {
-        if (tab[e * SW + NW + 1] == KIDX_EMPTY || !kcor_solid_word(tab[e * SW + NW], pr.min_cov)) continue;
-        solid++;
-        uint32_t reasons[2];
-        const uint32_t ends = kunitig_ends<NW>(kidx_record_key<NW>(tab + e * SW), tab[e * SW + NW], e, K, up, find, reasons);
-        for (int side = 0; side < 2; side++)
-            if (ends >> side & 1) starts.push_back(kunitig_start(e, side == 0, reasons[side]));
-    }
-    // 2. decide: every start over the table as it stands
-    for (uint64_t s : starts) {
-        const uint32_t left = kunitig_start_reason(s);
-        KeditDecision d{0, false, false};
-        if (Op::starts(left)) d = Op::template decide<NW>(node_of(s), left, K, pr, find);
-        lens.push_back(d.minor ? d.n : 0);
-        kept += d.candidate && !d.minor;
-    }
-    // 3. apply
-    for (size_t i = 0; i < starts.size(); i++) {
-        if (!lens[i]) continue;
-        Op::template apply<NW>(node_of(starts[i]), lens[i], K, pr, find, zero, clear);
-        removed++;
-        kmers += lens[i];
-    }
-    totals[KEDIT_T_REMOVED] = removed;
-    totals[KEDIT_T_KMERS] = kmers;
-    totals[KEDIT_T_SOLID] = solid;
-    totals[KEDIT_T_KEPT] = kept;
-}
-
-// The refusals every entry shares, in the order they are made: a null index, an index cut over ranks (cut_tail ends that message), the
-// operator's own ranges (range: the message, or empty when they hold), null totals.  PG_OK: nothing to refuse
-int kedit_refuse(const std::string& entry, const pg_kindex* ix, const char* cut_tail, const std::string& range, const uint64_t* out_totals) {
-    if (!ix) { pg_set_error(entry + ": null index"); return PG_EINVAL; }
-    if (ix->cut) {
-        pg_set_error(entry + ": the index is cut over ranks; a walk chases one lookup after the other in one table, each step's key "
-                             "named by the answer before it: " + cut_tail);
-        return PG_ESTATE;
-    }
-    if (!range.empty()) { pg_set_error(entry + ": " + range); return PG_EINVAL; }
-    if (!out_totals) { pg_set_error(entry + ": out_totals is null"); return PG_EINVAL; }
-    return PG_OK;
-}
-
-template <class Op>
-int kedit_round(pg_kindex* ix, const typename Op::Params& pr, uint64_t* out_totals, void* stream) {
-    if (ix->device >= 0) return kedit_device_round<Op>(ix, pr, out_totals, stream);
-    kidx_with_nw(ix->nw, [&](auto nw) { kedit_host_round<decltype(nw)::value, Op>(ix, pr, out_totals); });
-    return PG_OK;
-}
-
-}  // namespace
-}  // namespace pg
 
 extern "C" int pg_kindex_clip_tips(pg_kindex* ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_tip, uint64_t* out_totals, void* stream) {
     const bool ok = min_cov && min_cov <= 255 && min_arc && min_arc <= 63 && max_tip && max_tip <= pg::KTIP_MAX_TIP;

@@ -81,6 +81,10 @@
 // BRANCH_IN, tests the junction's word; apply cuts the tip from that one junction
 // The bubbles (kbubble.hpp: KbubbleOp; pg_kindex_pop_bubbles): a start with BRANCH_IN on the left walks its branch, takes the
 // fork from the step out of rc(x0) and walks at most three siblings; apply cuts the branch from both junctions
+// The arcs (karc.hpp: KarcOp; pg_kindex_drop_weak_arcs): a start with BRANCH_OUT or WEAK_NEXT on the left looks up the
+// up-to-four targets of that side's arcs; apply looks them up again and takes the dangling ones out of the start's own word
+// The bulges (kbulge.hpp: KbulgeOp; pg_kindex_pop_bulges): the bubbles' start, branch and apply; in place of the siblings one
+// walk from the fork along the strictly strongest arcs to the join
 // The corrector on an index cut over ranks (kcorrect_rows.hpp; pg_kindex_correct_rows): rounds of plan, query, decide on the
 // caller's stream, every query kidx_query_ranks, and the host reads the round's trial count back once a round
 //   kcor_rows_begin_kernel     a lane per read over its row of the read as given: weak count, anchor, first weak k-mer behind it, the
@@ -103,7 +107,9 @@
 #include "arena.hpp"
 #include "device_ctx.hpp"
 #include "env.hpp"
+#include "karc.hpp"
 #include "kbubble.hpp"
+#include "kbulge.hpp"
 #include "kcorrect.hpp"
 #include "kcorrect_rows.hpp"
 #include "kedit.hpp"
@@ -1284,6 +1290,8 @@ int kedit_device_round(::pg_kindex* ix, const typename Op::Params& pr, uint64_t*
 }
 template int kedit_device_round<KtipOp>(::pg_kindex*, const KtipParams&, uint64_t*, void*);
 template int kedit_device_round<KbubbleOp>(::pg_kindex*, const KbubbleParams&, uint64_t*, void*);
+template int kedit_device_round<KarcOp>(::pg_kindex*, const KarcParams&, uint64_t*, void*);
+template int kedit_device_round<KbulgeOp>(::pg_kindex*, const KbubbleParams&, uint64_t*, void*);
 
 // ---- the corrector on an index cut over ranks ----
 namespace {
