@@ -568,6 +568,18 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       walk chases its lookups in one table); nothing is written then.  Device memory of the index's device,
  *                       asynchronous on `stream`; the index keeps scratch of 3 words a stored k-mer and a bit a slot, which grows
  *                       to the size needed, and only that growth waits.  Host memory for a host-twin index.
+ *   pg_kindex_unitigs_ranked  pg_kindex_unitigs by list ranking (csrc/krank.hpp): the same rule, the same outputs word for word and the
+ *                       same capacities, without max_kmers: a chain of n k-mers costs ceil(log2 n) rounds over all k-mers in parallel
+ *                       instead of n dependent lookups of one lane, so nothing is cut (out_totals[6] is 0, out_totals[3] ==
+ *                       out_totals[4]) and a ring of any length is emitted.  Where pg_kindex_unitigs cuts nothing and drops no ring
+ *                       the two return the same set of unitigs, reasons, coverage sums and totals.  The host launches
+ *                       3 ceil(log2(keys + 1)) rounds whatever the graph; the device ends those with nothing to do.
+ *                       PG_EINVAL: a threshold out of range, out_totals null, an index of more than 2^31 - 2 keys (node ids are
+ *                       32-bit with the strand in bit 0, which also keeps every length below 2^32 bases); PG_ESTATE: an index cut
+ *                       over ranks; nothing is written then.  Asynchronous on `stream`, no host wait.  The scratch is
+ *                       pg_kindex_unitigs', grown to 12.5 words (100 bytes) a stored k-mer (two generations of a 16-byte record for either
+ *                       strand, the first successors, the node's slot, the start and length lists) and half a word a slot (the slot's
+ *                       node): 10.7 GB for 95.9 M keys in 268 M slots.  Host memory for a host-twin index.
  *   pg_kindex_clip_tips one round of tip clipping on the graph of the index (csrc/ktip.hpp).  Solid, the arc sets, the side test, the end
  *                       reasons, min_cov (1..255) and min_arc (1..63) are pg_kindex_unitigs'.  A tip candidate is a linear unitig
  *                       x0 -> .. -> x(n-1) oriented so that the left side of x0 is free (reason 3 dead end or 5 weak next), the right
@@ -682,6 +694,9 @@ int pg_kindex_walk(pg_kindex *ix, const uint64_t *packed, uint64_t n_words, cons
 int pg_kindex_unitigs(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_kmers, uint64_t cap_unitigs, uint64_t cap_words,
                       uint64_t *packed_out, uint64_t *word_off_out, uint64_t *kmer_base_out, uint64_t *out_report, uint64_t *out_totals,
                       void *stream);
+int pg_kindex_unitigs_ranked(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint64_t cap_unitigs, uint64_t cap_words,
+                             uint64_t *packed_out, uint64_t *word_off_out, uint64_t *kmer_base_out, uint64_t *out_report,
+                             uint64_t *out_totals, void *stream);
 int pg_kindex_clip_tips(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_tip, uint64_t *out_totals, void *stream);
 int pg_kindex_pop_bubbles(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_len, uint32_t max_diff, uint64_t *out_totals,
                           void *stream);

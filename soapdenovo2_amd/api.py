@@ -189,6 +189,7 @@ def lib() -> C.CDLL:
     L.pg_kindex_walk.argtypes = [C.c_void_p, u64p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u64p,
                                  C.c_void_p]
     L.pg_kindex_unitigs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p, u64p, C.c_void_p]
+    L.pg_kindex_unitigs_ranked.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u64p, u64p, C.c_void_p]
     L.pg_kindex_clip_tips.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
     L.pg_kindex_pop_bubbles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
     L.pg_kindex_drop_weak_arcs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
@@ -228,7 +229,7 @@ EXPORTED_SYMBOLS = [
     "pg_kindex_build", "pg_kindex_from_ctx", "pg_kindex_query", "pg_kindex_correct", "pg_kindex_info", "pg_kindex_destroy", "pg_host_kindex_bytes",
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
     "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times", "pg_kindex_correct_rows", "pg_kindex_correct_rows_stats",
-    "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_clip_tips", "pg_kindex_pop_bubbles", "pg_kindex_drop_weak_arcs", "pg_kindex_pop_bulges",
+    "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_unitigs_ranked", "pg_kindex_clip_tips", "pg_kindex_pop_bubbles", "pg_kindex_drop_weak_arcs", "pg_kindex_pop_bulges",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
 ]
 
@@ -926,6 +927,7 @@ def walk_fields(report) -> dict:
 UNITIG_REASONS = {3: "dead_end", 4: "branch_out", 5: "weak_next", 6: "branch_in", 9: "hairpin", 10: "cycle", 11: "cut"}
 UNITIG_MAX_KMERS = 1 << 24
 UNITIG_KMERS_BOUND = 1 << 26
+UNITIG_ENGINES = ("walk", "rank")
 UNITIG_TOTALS_FIELDS = ["unitigs", "words", "bases", "covered", "solid", "cyclic", "cut", "overflow"]
 Unitigs = collections.namedtuple("Unitigs", "packed word_off kmer_base report totals")
 
@@ -1263,7 +1265,7 @@ class KmerIndex:
         """walk_uniform for sequences of any lengths (pack_seqs_ragged); one shorter than K gives two empty walks, reason no_kmer."""
         return self._walk(d_packed, d_word_off, d_kmer_base, n_seqs, 0, min_cov, min_arc, max_ext)
 
-    def unitigs(self, min_cov: int, min_arc: int = 1, max_kmers: int = UNITIG_MAX_KMERS) -> "Unitigs":
+    def unitigs(self, min_cov: int, min_arc: int = 1, max_kmers: int = UNITIG_MAX_KMERS, engine: str = "walk") -> "Unitigs":
         """The whole graph of the index compacted into unitigs (pg_kindex_unitigs): every maximal unambiguous path -- exactly one arc
         with a counter >= min_arc out, a solid successor (coverage >= min_cov) with exactly that arc in -- once, in the orientation
         whose first k-mer is not greater, rings from their least k-mer; a walk stops after max_kmers k-mers (reason cut).  Returns
@@ -1271,19 +1273,29 @@ class KmerIndex:
         KmerCounter.count_ragged take as it lies (word_off and kmer_base have one entry more than there are unitigs, packed the
         readable tail), report = two words a unitig (unitig_fields) and totals = UNITIG_TOTALS_FIELDS as a numpy array.  Two calls:
         a count call, whose totals are read -- the one wait for the GPU here -- to allocate exactly, and the full call.  The order of
-        the unitigs is unspecified.  An index cut over ranks is refused."""
+        the unitigs is unspecified.  An index cut over ranks is refused.
+        engine: "walk" (the default) walks every chain with one lane, a dependent lookup a k-mer; "rank" (pg_kindex_unitigs_ranked) ranks
+        all chains at once in ceil(log2 n) rounds and has no guard -- nothing is cut, a ring of any length is emitted, and a max_kmers
+        other than the default is a ValueError -- at the price of scratch of 100 bytes a stored k-mer.  Where "walk" cuts nothing the
+        two return the same unitigs.  The library does not choose between them."""
+        if engine not in UNITIG_ENGINES:
+            raise ValueError("KmerIndex.unitigs: engine is one of %s, not %r" % (", ".join(UNITIG_ENGINES), engine))
+        if engine == "rank" and max_kmers != UNITIG_MAX_KMERS:
+            raise ValueError("KmerIndex.unitigs: engine 'rank' has no guard: max_kmers stays at its default")
         if self.device < 0:
             new = lambda n: np.zeros(max(n, 1), dtype=np.uint64)
         else:
             new = lambda n: self.torch.zeros(max(n, 1), dtype=self.torch.int64, device=f"cuda:{self.device}")
+        if engine == "rank":
+            name, call = "pg_kindex_unitigs_ranked", lambda *a: lib().pg_kindex_unitigs_ranked(self.h, min_cov, min_arc, *a)
+        else:
+            name, call = "pg_kindex_unitigs", lambda *a: lib().pg_kindex_unitigs(self.h, min_cov, min_arc, max_kmers, *a)
         totals = new(8)
-        _check(lib().pg_kindex_unitigs(self.h, min_cov, min_arc, max_kmers, 0, 0, None, None, None, None, self._ptr(totals), self._stream()),
-               "pg_kindex_unitigs")
+        _check(call(0, 0, None, None, None, None, self._ptr(totals), self._stream()), name)
         t = totals if self.device < 0 else totals.cpu().numpy().view(np.uint64)
         n, words = int(t[0]), int(t[1])
         packed, word_off, kmer_base, report = new(words), new(n + 1), new(n + 1), new(2 * n)
-        _check(lib().pg_kindex_unitigs(self.h, min_cov, min_arc, max_kmers, n, words, self._ptr(packed), self._ptr(word_off), self._ptr(kmer_base),
-                                       self._ptr(report), self._ptr(totals), self._stream()), "pg_kindex_unitigs")
+        _check(call(n, words, self._ptr(packed), self._ptr(word_off), self._ptr(kmer_base), self._ptr(report), self._ptr(totals), self._stream()), name)
         t = totals.copy() if self.device < 0 else totals.cpu().numpy().view(np.uint64)
         if int(t[7]):
             raise PgError("KmerIndex.unitigs: the full call needs more than the count call said")
@@ -1495,10 +1507,10 @@ def extend_seqs(seqs: Sequence[np.ndarray], index: KmerIndex, min_cov: int, min_
     return out, f
 
 
-def unitig_seqs(index: KmerIndex, min_cov: int, min_arc: int = 1, max_kmers: int = UNITIG_MAX_KMERS):
+def unitig_seqs(index: KmerIndex, min_cov: int, min_arc: int = 1, max_kmers: int = UNITIG_MAX_KMERS, engine: str = "walk"):
     """The unitigs of the index's graph as base codes, for tests and small uses: (a list of base-code arrays, the fields of all of them
     -- see unitig_fields --, the totals as a dict of UNITIG_TOTALS_FIELDS).  The order of the unitigs is unspecified."""
-    u = index.unitigs(min_cov, min_arc, max_kmers)
+    u = index.unitigs(min_cov, min_arc, max_kmers, engine)
     down = (lambda a: a) if index.device < 0 else (lambda a: a.cpu().numpy().view(np.uint64))
     packed, word_off, report = down(u.packed), down(u.word_off), down(u.report)
     f = unitig_fields(report)

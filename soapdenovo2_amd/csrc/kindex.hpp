@@ -226,7 +226,8 @@ struct pg_kindex {
     // trim (ktrim.hpp): the spans and source indices the caller did not ask for and the scan's block sums; e_trim are a trim's begin,
     // spans done and scan done, and its end is the scratch's.  cor (kcorrect_rows.hpp): the reads' state words and as-given bits, a
     // round's trial batch, its rows, the read of each trial and the claim counter.  uni (kunitig.hpp): the counters, the start list, the
-    // lengths, the scan's block sums and a covered bit a slot; a round of tip clipping (ktip.hpp) uses its counters, start list and lengths
+    // lengths, the scan's block sums and a covered bit a slot; a round of tip clipping (ktip.hpp) uses its counters, start list and lengths,
+    // and the ranked unitigs (krank.hpp) put their control words, records and node maps behind the counters
     pg::KidxScratch trim, cor, uni;
     hipEvent_t e_trim[3] = {nullptr, nullptr, nullptr};
     uint64_t cor_stats[4] = {0, 0, 0, 0};   // the last pg_kindex_correct_rows: rounds, trials, k-mers asked in trials, host waits

@@ -67,6 +67,20 @@
 //                              kunitig_scan_sums_kernel (the totals, the overflow decision the write kernel obeys, the last offsets and
 //                              the tail's zero words)
 //   kunitig_write_kernel       a lane per start: its offsets from the scan, and a kept start walks once more into its row
+// The unitigs by list ranking (krank.hpp; pg_kindex_unitigs_ranked): the same unitigs, a chain of n k-mers in ceil(log2 n)
+// rounds over all k-mers instead of n dependent lookups of one lane; 3 R + 7 launches (R = krank_rounds(keys)), 3 more in full mode
+//   krank_number_kernel        a workgroup per 4 096 slots: a solid key takes a node id, one atomicAdd a workgroup
+//   krank_sweep_kernel         a lane per slot: kunitig_side on both sides (the ends kernel's two lookups); an end side becomes an end
+//                              record and a start, an open one a link to its successor
+//   krank_jump_kernel          round j over the oriented nodes, a grid of at most 4 096 workgroups striding them: krank_jump from the
+//                              generation the control words name into the other; a round behind one in which no record became done ends
+//                              after one read a workgroup
+//   krank_ring_init_kernel, krank_min_kernel, krank_ring_cut_kernel   what is not done lies on a ring: the least canonical key of each
+//                              directed ring by windows that double, the ring cut there into a chain, its least member appended to the
+//                              starts; then the jump rounds again.  All but the first end at once when there is no ring
+//   krank_measure_kernel       a lane per start: length and far end from its record, the orientation rule; then the unitigs' scan
+//   krank_zero_kernel, krank_place_kernel, krank_emit_kernel   full mode: the rows zeroed, a lane per start (offsets, report words, a
+//                              place record at the start's node), a lane per k-mer (its base ORed into its row at its rank)
 // The operators that edit the graph (kedit.hpp): one round of an operator Op, four launches on the caller's stream over the
 // unitigs' scratch
 //   kunitig_ends_kernel        as above: the start list and the solid count
@@ -114,6 +128,7 @@
 #include "kcorrect_rows.hpp"
 #include "kedit.hpp"
 #include "kindex.hpp"
+#include "krank.hpp"
 #include "ktip.hpp"
 #include "ktrim.hpp"
 #include "kunitig.hpp"
@@ -573,6 +588,181 @@ __global__ __launch_bounds__(256) void kunitig_write_kernel(const uint64_t* __re
         report[2 * u] = kunitig_report_word(own.c[2] + (uint64_t)K - 1, left, w.reason);
         report[2 * u + 1] = w.cov;
     }
+}
+
+// ---- the unitigs by list ranking: number, sweep, rounds, rings, measure, the unitigs' scan, zero, place, emit (krank.hpp) ----
+// The kernels over the nodes stride a grid of at most KRANK_BLOCKS workgroups: a round with nothing to do ends after one read a
+// workgroup.  n = the oriented nodes in use, two a solid k-mer
+constexpr unsigned KRANK_BLOCKS = 4096;
+__device__ __forceinline__ uint64_t krank_n(const KunitigScratch& s) { return 2 * (uint64_t)s.ctr[KUNITIG_C_SOLID]; }
+__device__ __forceinline__ uint64_t krank_lane() { return (uint64_t)blockIdx.x * 256 + threadIdx.x; }
+__device__ __forceinline__ uint64_t krank_stride() { return (uint64_t)gridDim.x * 256; }
+
+// A workgroup per 256 * KRANK_NUMBER_EACH slots, a lane KRANK_NUMBER_EACH of them (coalesced a turn): the published solid keys take the next
+// node ids, a workgroup's with one atomicAdd -- one a wave of 64 slots, with its answer waited for, made this pass 33 ms of a 43 ms
+// call on a 268 M-slot table.  The lane's solid slots are a bit each in a register between the count and the ids
+constexpr int KRANK_NUMBER_EACH = 16;
+template <int NW>
+__global__ __launch_bounds__(256) void krank_number_kernel(const uint64_t* __restrict__ tab, uint64_t slots, uint32_t min_cov, KunitigScratch s, KrankView v) {
+    constexpr int SW = map_slot_words<NW>();
+    __shared__ uint32_t wave_sums[4];
+    __shared__ unsigned long long block_first;
+    const uint64_t base = (uint64_t)blockIdx.x * (256 * KRANK_NUMBER_EACH) + threadIdx.x;
+    uint32_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < KRANK_NUMBER_EACH; k++) {
+        const uint64_t e = base + (uint64_t)k * 256;
+        const uint64_t* sl = tab + e * SW;
+        const uint64_t w = e < slots && sl[NW + 1] != KIDX_EMPTY ? sl[NW] : 0;
+        mine |= kcor_solid_word(w, min_cov) ? 1u << k : 0u;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t upto = (uint32_t)__popc(mine);         // the inclusive scan of the lanes' counts over the workgroup (every lane is here)
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(upto, d);
+        upto += lane >= d ? o : 0;
+    }
+    if (lane == 63) wave_sums[wave] = upto;
+    __syncthreads();
+    uint32_t before = upto - (uint32_t)__popc(mine), all = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        before += w < wave ? wave_sums[w] : 0;
+        all += wave_sums[w];
+    }
+    if (threadIdx.x == 0) block_first = all ? atomicAdd(s.ctr + KUNITIG_C_SOLID, (unsigned long long)all) : 0ull;
+    __syncthreads();
+    uint32_t node = (uint32_t)block_first + before;
+#pragma unroll
+    for (int k = 0; k < KRANK_NUMBER_EACH; k++)
+        if (mine >> k & 1u) {
+            const uint64_t e = base + (uint64_t)k * 256;
+            v.node_of[e] = node;
+            v.slot_of[node++] = (uint32_t)e;
+        }
+}
+
+// a lane per table slot: krank_sweep, the unitigs' ends sweep that also writes every oriented node's first record
+template <int NW>
+__global__ __launch_bounds__(256) void krank_sweep_kernel(const uint64_t* __restrict__ tab, uint64_t slots, int K, KunitigParams pr, KunitigScratch s, KrankView v,
+                                                          uint32_t* ctl) {
+    constexpr int SW = map_slot_words<NW>();
+    const uint64_t e = krank_lane(), mask = slots - 1;
+    const uint64_t* sl = tab + e * SW;
+    const uint64_t w = e < slots && sl[NW + 1] != KIDX_EMPTY ? sl[NW] : 0;
+    bool open = false;
+    if (kcor_solid_word(w, pr.min_cov))
+        open = krank_sweep<NW>(v, sl, e, K, pr, [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); },
+                               [&s](uint64_t start) { kunitig_append(s, start, 0); });
+    if (open) ctl[KRANK_GO] = 1;                   // (every writer writes the same)
+}
+
+// round j: every record jumps from the generation the control words name into the other; a round behind one in which nothing became
+// done passes the generation on and ends
+__global__ __launch_bounds__(256) void krank_jump_kernel(KunitigScratch s, KrankView v, uint32_t* ctl, int j) {
+    const uint32_t g = ctl[KRANK_GEN + j];
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    if (!ctl[KRANK_GO + j]) {                      // (uniform over the launch)
+        if (first) ctl[KRANK_GEN + j + 1] = g;
+        return;
+    }
+    const KrankRec* src = v.rec + (uint64_t)g * v.n2;
+    KrankRec* dst = v.rec + (uint64_t)(g ^ 1u) * v.n2;
+    bool any = false;
+    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) {
+        bool became;
+        dst[x] = krank_jump(src[x], src, became);
+        any = any || became;
+    }
+    if (any) ctl[KRANK_GO + j + 1] = 1;
+    if (first) ctl[KRANK_GEN + j + 1] = g ^ 1u;
+}
+
+// the rings: a record the R rounds did not finish opens its window in the free generation
+__global__ __launch_bounds__(256) void krank_ring_init_kernel(KunitigScratch s, KrankView v, uint32_t* ctl, int R) {
+    const uint32_t g = ctl[KRANK_GEN + R];
+    const KrankRec* fin = v.rec + (uint64_t)g * v.n2;
+    KrankRec* spare = v.rec + (uint64_t)(g ^ 1u) * v.n2;
+    bool any = false;
+    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) {
+        if (krank_done(fin[x])) continue;
+        krank_min_store(spare + x, 0, KrankMin{v.succ0[x], (uint32_t)x});
+        any = true;
+    }
+    if (any) ctl[KRANK_RING] = 1;
+}
+
+// round r of the rings' windows; ends at once when there is no ring
+template <int NW>
+__global__ __launch_bounds__(256) void krank_min_kernel(const uint64_t* __restrict__ tab, KunitigScratch s, KrankView v, const uint32_t* ctl, int R, int r) {
+    if (!ctl[KRANK_RING]) return;                  // (uniform over the launch)
+    const uint32_t g = ctl[KRANK_GEN + R];
+    const KrankRec* fin = v.rec + (uint64_t)g * v.n2;
+    KrankRec* spare = v.rec + (uint64_t)(g ^ 1u) * v.n2;
+    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) {
+        if (krank_done(fin[x])) continue;
+        krank_min_store(spare + x, (r & 1) ^ 1, krank_min_jump<NW>(krank_min_load(spare + x, r & 1), spare, r & 1, tab, v));
+    }
+}
+
+// the rings become chains from their least members, which are appended to the start list, and the rounds may run again
+template <int NW>
+__global__ __launch_bounds__(256) void krank_ring_cut_kernel(const uint64_t* __restrict__ tab, KunitigScratch s, KrankView v, uint32_t* ctl, int R) {
+    if (!ctl[KRANK_RING]) return;                  // (uniform over the launch)
+    const uint32_t g = ctl[KRANK_GEN + R];
+    KrankRec* fin = v.rec + (uint64_t)g * v.n2;
+    const KrankRec* spare = v.rec + (uint64_t)(g ^ 1u) * v.n2;
+    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) {
+        if (krank_done(fin[x])) continue;
+        const uint32_t best = krank_min_load(spare + x, R & 1).best;
+        fin[x] = krank_ring_cut((uint32_t)x, best, v.succ0[x], [tab, &v](uint32_t y) { return kidx_coverage(krank_slot<NW>(tab, v, y)[NW]); });
+        if (best == (uint32_t)x && krank_fwd(best)) {
+            kunitig_append(s, kunitig_start(v.slot_of[x >> 1], true, KUNITIG_CYCLE), 0);
+            atomicAdd(s.ctr + KUNITIG_C_CYCLIC, 1ull);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl[KRANK_GO + R] = 1;
+}
+
+// a lane per start: its length for the scan from its record
+template <int NW>
+__global__ __launch_bounds__(256) void krank_measure_kernel(const uint64_t* __restrict__ tab, int K, KunitigScratch s, KrankView v, const uint32_t* ctl, int R) {
+    const uint64_t i = krank_lane();
+    if (i >= kunitig_n_starts(s)) return;
+    s.lens[i] = krank_measure<NW>(s.starts[i], tab, v, v.rec + (uint64_t)ctl[KRANK_GEN + 2 * R] * v.n2, K);
+}
+
+// the rows' words zeroed where the scan said go: the emit pass ORs into them
+__global__ __launch_bounds__(256) void krank_zero_kernel(KunitigScratch s, const uint64_t* __restrict__ totals, int tail, uint64_t* __restrict__ packed_out) {
+    if (!s.ctr[KUNITIG_C_GO]) return;              // (uniform over the launch)
+    for (uint64_t w = krank_lane(), words = totals[KUNITIG_T_WORDS] - (uint64_t)tail; w < words; w += krank_stride()) packed_out[w] = 0;
+}
+
+// a lane per start: the scan inside the workgroup again; krank_place
+template <int NW>
+__global__ __launch_bounds__(256) void krank_place_kernel(const uint64_t* __restrict__ tab, int K, KunitigScratch s, KrankView v, const uint32_t* ctl, int R,
+                                                          uint64_t* __restrict__ word_off_out, uint64_t* __restrict__ kmer_base_out,
+                                                          uint64_t* __restrict__ report) {
+    const uint64_t n_starts = kunitig_n_starts(s);
+    if (!s.ctr[KUNITIG_C_GO] || (uint64_t)blockIdx.x * 256 >= n_starts) return;  // (uniform over the workgroup)
+    const uint64_t i = krank_lane();
+    const KidxCounts own = kunitig_lane_counts(s, n_starts, K, i), before = kidx_scan_before(own, s.sums);
+    if (i >= n_starts) return;                     // (no barrier follows)
+    const uint32_t g = ctl[KRANK_GEN + 2 * R];
+    krank_place<NW>(s.starts[i], (uint32_t)own.c[2], before.c[0], before.c[1], before.c[2], tab, v, v.rec + (uint64_t)g * v.n2,
+                    v.rec + (uint64_t)(g ^ 1u) * v.n2, K, word_off_out, kmer_base_out, report);
+}
+
+// every node into its row: krank_emit with a 64-bit atomicOr
+template <int NW>
+__global__ __launch_bounds__(256) void krank_emit_kernel(const uint64_t* __restrict__ tab, int K, KunitigScratch s, KrankView v, const uint32_t* ctl, int R,
+                                                         uint64_t* packed_out) {
+    if (!s.ctr[KUNITIG_C_GO]) return;              // (uniform over the launch)
+    const uint32_t g = ctl[KRANK_GEN + 2 * R];
+    const KrankRec *fin = v.rec + (uint64_t)g * v.n2, *place = v.rec + (uint64_t)(g ^ 1u) * v.n2;
+    for (uint64_t node = krank_lane(), n = s.ctr[KUNITIG_C_SOLID]; node < n; node += krank_stride())
+        krank_emit<NW>((uint32_t)node, tab, v, fin, place, K,
+                       [packed_out](uint64_t at, uint64_t bits) { atomicOr((unsigned long long*)packed_out + at, (unsigned long long)bits); });
 }
 
 // ---- the operators that edit the graph: ends (the unitigs' kernel), decide, apply, the totals (kedit.hpp; ktip.hpp, kbubble.hpp) ----
@@ -1247,6 +1437,71 @@ int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t ca
         if (int rc = kidx_launch(ix, [&](auto nw) {
                 hipLaunchKernelGGL((kunitig_write_kernel<decltype(nw)::value>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s, d_packed_out,
                                    d_word_off_out, d_kmer_base_out, d_report);
+            }))
+            return rc;
+    return kidx_scratch_end(ix->uni, st);
+}
+
+// The unitigs by list ranking (krank.hpp): no host wait and no guard.  R = krank_rounds(keys) is all the host knows, so
+// it launches 3 R rounds -- the chains', the rings' windows, the rings as chains -- and the device ends the ones with nothing to do:
+// 3 R + 7 launches in count mode, 3 more in full mode.  The scratch is the unitigs' with the ranking's arrays behind it
+int kunitig_device_unitigs_ranked(::pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out,
+                                  uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_report, uint64_t* d_totals, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const KidxRank& t = ix->ranks[0];
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    const uint64_t cap = std::max<uint64_t>(2 * t.keys, 2), words_bound = std::max<uint64_t>(std::min(cap_words, krank_words_bound(t.keys, ix->K)), 1);
+    dim3 slot_grid, start_grid, node_grid, word_grid;
+    if (int rc = kidx_launch_blocks(t.slots, 256, "table too large", &slot_grid)) return rc;
+    if (int rc = kidx_launch_blocks(cap, 256, "too many starts", &start_grid)) return rc;
+    const dim3 number_grid((slot_grid.x + KRANK_NUMBER_EACH - 1) / KRANK_NUMBER_EACH);
+    node_grid = dim3(std::min(start_grid.x, KRANK_BLOCKS));
+    word_grid = dim3((unsigned)std::min<uint64_t>((words_bound + 255) / 256, KRANK_BLOCKS));
+    // Scratch, in words: the counters, the control words (two a word), the records (two generations of `cap`, two words each), the
+    // starts, the lengths (two a word), the block sums, succ0 and slot_of and node_of (two a word)
+    const uint64_t w_ctl = KRANK_CTL / 2, w_rec = 4 * cap, w_lens = (cap + 1) / 2, w_sums = (uint64_t)start_grid.x * KIDX_COUNTS, w_succ = cap / 2,
+                   w_slot_of = (t.keys + 2) / 2, w_node_of = (t.slots + 1) / 2;
+    static_assert((KUNITIG_CTRS + KRANK_CTL / 2) % 2 == 0, "the records are 16-byte aligned");
+    if (int rc = kidx_scratch_begin(ix->uni, KUNITIG_CTRS + w_ctl + w_rec + cap + w_lens + w_sums + w_succ + w_slot_of + w_node_of, st)) return rc;
+    KunitigScratch s;
+    s.ctr = (unsigned long long*)ix->uni.d;
+    uint32_t* ctl = (uint32_t*)(ix->uni.d + KUNITIG_CTRS);
+    KrankView v;
+    v.rec = (KrankRec*)(ix->uni.d + KUNITIG_CTRS + w_ctl);
+    s.starts = ix->uni.d + KUNITIG_CTRS + w_ctl + w_rec;
+    s.lens = (uint32_t*)(s.starts + cap);
+    s.sums = s.starts + cap + w_lens;
+    s.bits = nullptr;
+    s.cap = cap;
+    v.succ0 = (uint32_t*)(s.sums + w_sums);
+    v.slot_of = (uint32_t*)(s.sums + w_sums + w_succ);
+    v.node_of = (uint32_t*)(s.sums + w_sums + w_succ + w_slot_of);
+    v.n2 = cap;
+    KIDX_HIP(hipMemsetAsync(ix->uni.d, 0, (KUNITIG_CTRS + w_ctl) * sizeof(uint64_t), st));
+    const dim3 block(256);
+    const int K = ix->K, tail = ix->nw + 1, R = krank_rounds(t.keys);
+    if (int rc = kidx_launch(ix, [&](auto nw) {
+            constexpr int NW = decltype(nw)::value;
+            hipLaunchKernelGGL((krank_number_kernel<NW>), number_grid, block, 0, st, t.d_tab, t.slots, pr.min_cov, s, v);
+            hipLaunchKernelGGL((krank_sweep_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, pr, s, v, ctl);
+            for (int j = 0; j < R; j++) hipLaunchKernelGGL(krank_jump_kernel, node_grid, block, 0, st, s, v, ctl, j);
+            hipLaunchKernelGGL(krank_ring_init_kernel, node_grid, block, 0, st, s, v, ctl, R);
+            for (int r = 0; r < R; r++) hipLaunchKernelGGL((krank_min_kernel<NW>), node_grid, block, 0, st, t.d_tab, s, v, ctl, R, r);
+            hipLaunchKernelGGL((krank_ring_cut_kernel<NW>), node_grid, block, 0, st, t.d_tab, s, v, ctl, R);
+            for (int j = R; j < 2 * R; j++) hipLaunchKernelGGL(krank_jump_kernel, node_grid, block, 0, st, s, v, ctl, j);
+            hipLaunchKernelGGL((krank_measure_kernel<NW>), start_grid, block, 0, st, t.d_tab, K, s, v, ctl, R);
+        }))
+        return rc;
+    hipLaunchKernelGGL(kunitig_block_sums_kernel, start_grid, block, 0, st, s, K);
+    hipLaunchKernelGGL(kunitig_scan_sums_kernel, dim3(1), block, 0, st, s, K, tail, cap_unitigs, cap_words, d_packed_out, d_word_off_out, d_kmer_base_out,
+                       d_totals);
+    KIDX_HIP(hipGetLastError());
+    if (d_packed_out)
+        if (int rc = kidx_launch(ix, [&](auto nw) {
+                constexpr int NW = decltype(nw)::value;
+                hipLaunchKernelGGL(krank_zero_kernel, word_grid, block, 0, st, s, d_totals, tail, d_packed_out);
+                hipLaunchKernelGGL((krank_place_kernel<NW>), start_grid, block, 0, st, t.d_tab, K, s, v, ctl, R, d_word_off_out, d_kmer_base_out, d_report);
+                hipLaunchKernelGGL((krank_emit_kernel<NW>), node_grid, block, 0, st, t.d_tab, K, s, v, ctl, R, d_packed_out);
             }))
             return rc;
     return kidx_scratch_end(ix->uni, st);

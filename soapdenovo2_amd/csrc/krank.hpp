@@ -1,0 +1,227 @@
+// krank.hpp -- the unitigs of kunitig.hpp found by list ranking instead of by walking (pg_kindex_unitigs_ranked, include/soapdenovo2_amd.h
+// section 3): a chain of n k-mers costs ceil(log2 n) rounds over all k-mers in parallel where kunitig_chain costs one lane
+// n dependent slot reads, and no chain or ring is too long.  The rule is kunitig.hpp's, nothing of it redefined: the side test is
+// kunitig_side, and it is asked once a side, by the ends sweep; everything behind the sweep works on what it wrote.
+//
+// An ORIENTED NODE is a solid stored k-mer as itself or as its reverse complement: id x = 2 * node + (0: the key as stored, 1: its
+// reverse complement), krank_flip(x) = x ^ 1 the other strand; the nodes are numbered 0 .. solid - 1 in any order.  succ(x) is the node
+// behind x's open right side.  Open is symmetric (kunitig.hpp), so succ is one to one where it is defined and the oriented nodes fall
+// into disjoint directed lists and directed rings; a chain and its reverse complement are two lists, and with K odd so are a ring and
+// its reverse complement (a ring that were its own would hold a k-mer equal to its reverse complement, or a hairpin step).
+//
+// A record (KrankRec, 16 bytes: one load) of x says where x's pointer stands: ptr, the steps to it (dist), and the coverage of the nodes
+// after x up to and including ptr (the low 48 bits of cov).  An END of a list points at itself with dist 0 and carries KRANK_DONE and the
+// reason of its right side in the bits of cov above the sum.  A jump replaces (ptr, dist, cov) by (ptr[ptr], dist + dist[ptr], cov +
+// cov[ptr]): at an end that adds nothing and stays, and the one addition that reaches a done record brings its flag and reason bits
+// along -- a record is done when its pointer is its list's end, and then it is left alone.  A node d steps before its end is done after
+// round floor(log2 d); a round in which no record became done leaves only rings behind (while a chain has a record that is not done, the
+// one 2^r steps before its end becomes done in round r), so the next round has nothing to do and says so to the one after it.
+// Every round reads one generation of the records and writes the other.
+//
+// The passes, in order (kindex_kernels.hip: krank_*_kernel; kunitig_rank_host.cpp runs the same bodies one after the other):
+//   number    a solid slot takes a node id: node_of a slot, slot_of a node
+//   sweep     krank_sweep, a slot: both sides through kunitig_side; an end side becomes an end record and a start of the start list
+//             (kunitig_start, as kunitig_ends_kernel appends it), an open one a link to its successor with the successor's coverage; the
+//             successor is kept (succ0) for the rings
+//   rank      krank_rounds(keys) rounds of krank_jump
+//   rings     what is not done now lies on a ring.  krank_min_jump, the same number of rounds: every member learns the oriented node of
+//             the least canonical key of its directed ring (two key reads a member a round: ring members only).  That node m is the key
+//             as stored on one of the ring's two directed copies -- the emitted one -- and its reverse complement on the other.
+//             krank_ring_cut takes the step into m out of the emitted copy and the step out of flip(m) out of the other, symmetrically,
+//             which makes the ring a chain from m to the node before it, reason KUNITIG_CYCLE on both cut sides; m is appended to the
+//             start list behind the chains' starts.  Then the rank rounds run once more; the chains' records are done and stay
+//   measure   krank_measure, a start: the far end and the length from its record; a chain is kept from the end that is not greater (one
+//             key read of the far end), a ring from m.  The length list feeds kunitig.hpp's scan unchanged
+//   place     krank_place, a start after the scan: a kept one writes its offsets and its report words; every start leaves a place
+//             record (length or 0, the row's word offset) at its own id in the generation the rounds left free
+//   emit      krank_emit, a node: the record of (node, 0) names the right end A of its chain and the steps to it, that of (node, 1) the
+//             end B of the reverse list; the chain's two starts are flip(B) -- reading the node as stored, rank = the steps to B -- and
+//             flip(A).  The one with a place record that is kept names the row; the node ORs its last base in at position rank + K - 1,
+//             the node of rank 0 all K of its bases.  The rows were zeroed by a pass before.  No lane walks a chain
+//
+// Scratch (decided on the host from keys and slots, before the solid count is known): 100 bytes a key -- records 2 generations x 2
+// oriented nodes x 16, succ0 2 x 4, slot_of 4, the start list 2 x 8, the length list 2 x 4 -- and 4 bytes a slot for node_of; the block
+// sums and the control words are small change.  The other layout, node arrays indexed by slot, needs no node_of and no numbering pass
+// but 72 bytes a slot; a table is at most half full, so that is more than twice the bytes (19.3 GB against 10.7 GB on the 95.9 M-key,
+// 268 M-slot table of DESIGN.md §14), and the rounds would sweep the empty slots every time.
+// Node ids are 32-bit with the strand in bit 0: an index of more than KRANK_MAX_KEYS = 2^31 - 2 keys is refused (PG_EINVAL); that also
+// keeps every length below 2^32 bases.
+#pragma once
+#include "kunitig.hpp"
+
+namespace pg {
+
+constexpr uint64_t KRANK_MAX_KEYS = (1ull << 31) - 2;
+constexpr uint64_t KRANK_DONE = 1ull << 63;
+constexpr int KRANK_REASON = 48;                                                // the right reason of the list's end: 4 bits from here
+constexpr uint64_t KRANK_COV = (1ull << KRANK_REASON) - 1;
+
+struct alignas(16) KrankRec {
+    uint32_t ptr, dist;
+    uint64_t cov;
+};
+struct KrankMin {                  // a ring member's window: where it ends and the oriented node of the least canonical key inside it
+    uint32_t ptr, best;
+};
+
+PG_HD uint32_t krank_id(uint32_t node, bool fwd) { return 2 * node + (fwd ? 0u : 1u); }
+PG_HD uint32_t krank_flip(uint32_t x) { return x ^ 1u; }
+PG_HD bool krank_fwd(uint32_t x) { return (x & 1u) == 0; }
+PG_HD bool krank_done(const KrankRec& r) { return (r.cov & KRANK_DONE) != 0; }
+PG_HD uint32_t krank_reason(const KrankRec& r) { return (uint32_t)(r.cov >> KRANK_REASON) & 15u; }
+PG_HD uint64_t krank_cov(const KrankRec& r) { return r.cov & KRANK_COV; }
+PG_HD KrankRec krank_end(uint32_t x, uint32_t reason) { return KrankRec{x, 0, KRANK_DONE | (uint64_t)reason << KRANK_REASON}; }
+PG_HD KrankRec krank_link(uint32_t y, uint32_t cov_y) { return KrankRec{y, 1, cov_y}; }
+
+// rounds that finish every list of at most `keys` nodes: ceil(log2(keys + 1)), the bits of keys
+PG_HD int krank_rounds(uint64_t keys) {
+    int r = 0;
+    while (keys >> r) r++;
+    return r;
+}
+
+// The scratch of the ranking behind the unitigs' (kindex_kernels.hip: KunitigScratch; the host twin's vectors): rec = two generations
+// of n2 records, generation g at rec + g * n2; n2 = 2 * keys
+struct KrankView {
+    KrankRec* rec;
+    uint32_t *succ0, *node_of, *slot_of;
+    uint64_t n2;
+};
+// The control words (32-bit, zeroed before a call).  Round j of 0 .. 2 R - 1 (the chains' rounds, then the rings' chains') runs when
+// GO + j is set and reads generation GEN + j; it sets GO + j + 1 when a record became done and writes GEN + j + 1.  RING: there is a ring
+enum : int { KRANK_GO = 0, KRANK_GEN = 64, KRANK_RING = 128, KRANK_CTL = 192 };
+
+template <int NW>
+PG_HD const uint64_t* krank_slot(const uint64_t* tab, const KrankView& v, uint32_t x) {
+    return tab + (uint64_t)v.slot_of[x >> 1] * map_slot_words<NW>();
+}
+// the k-mer of oriented node x
+template <int NW>
+PG_HD Kmer<NW> krank_kmer(const uint64_t* tab, const KrankView& v, uint32_t x, int K) {
+    const Kmer<NW> c = kidx_record_key<NW>(krank_slot<NW>(tab, v, x));
+    return krank_fwd(x) ? c : kmer_rc<NW>(c, K);
+}
+
+// sweep: the solid key of slot e (node_of is complete) writes its two records of generation 0.  append(start) puts an end side into
+// the start list.  Returns whether a side is open
+template <int NW, typename Find, typename Append>
+PG_HD bool krank_sweep(const KrankView& v, const uint64_t* sl, uint64_t e, int K, const KunitigParams& pr, Find find, Append append) {
+    const Kmer<NW> filter = kmer_filter<NW>(K), c = kidx_record_key<NW>(sl);
+    const uint32_t node = v.node_of[e];
+    bool open = false;
+    for (int o = 0; o < 2; o++) {                  // the right side of the key as stored, then of its reverse complement
+        const KwalkNode<NW> x = kunitig_node<NW>(c, sl[NW], e, o == 0, K);
+        KwalkNode<NW> y;
+        int base = 0;
+        const uint32_t reason = kunitig_side<NW>(x, K, filter, pr, find, y, base);
+        const uint32_t id = krank_id(node, o == 0);
+        const uint32_t next = reason ? id : krank_id(v.node_of[y.slot], y.fwd);
+        v.rec[id] = reason ? krank_end(id, reason) : krank_link(next, kidx_coverage(y.w));
+        v.succ0[id] = next;
+        if (reason) append(kunitig_start(e, o != 0, reason));                     // (x's right side is the left side of the walk from flip(x))
+        open = open || !reason;
+    }
+    return open;
+}
+
+// a round's step of one record: src = the generation read.  became: the record was not done and is now
+PG_HD KrankRec krank_jump(const KrankRec& own, const KrankRec* src, bool& became) {
+    became = false;
+    if (krank_done(own)) return own;
+    const KrankRec q = src[own.ptr];
+    became = krank_done(q);
+    return KrankRec{q.ptr, own.dist + q.dist, own.cov + q.cov};
+}
+
+// A ring member's two window generations lie in its record of the generation the chains' rounds left free: generation 0 in (ptr, dist),
+// generation 1 in cov.  A lane reads the halves of the generation it reads and writes the other half of its own record
+PG_HD KrankMin krank_min_load(const KrankRec* r, int g) {
+    if (g) {
+        const uint64_t c = r->cov;
+        return KrankMin{(uint32_t)c, (uint32_t)(c >> 32)};
+    }
+    return KrankMin{r->ptr, r->dist};
+}
+PG_HD void krank_min_store(KrankRec* r, int g, KrankMin m) {
+    if (g) r->cov = (uint64_t)m.ptr | (uint64_t)m.best << 32;
+    else {
+        r->ptr = m.ptr;
+        r->dist = m.best;
+    }
+}
+// a ring member's round: its window and the one behind it become one; of the two least keys the smaller (the same node: no read)
+template <int NW>
+PG_HD KrankMin krank_min_jump(const KrankMin& own, const KrankRec* free_gen, int g, const uint64_t* tab, const KrankView& v) {
+    const KrankMin q = krank_min_load(free_gen + own.ptr, g);
+    bool less = false;
+    if (q.best != own.best)
+        less = kmer_less<NW>(kidx_record_key<NW>(krank_slot<NW>(tab, v, q.best)), kidx_record_key<NW>(krank_slot<NW>(tab, v, own.best)));
+    return KrankMin{q.ptr, less ? q.best : own.best};
+}
+// A ring member x whose ring's least key sits at oriented node `best`, as a chain's record again: on the emitted copy (best is the key
+// as stored) the node whose successor is best becomes the end, on the other copy best itself does.  cov_of(y) = the coverage of node y
+template <typename Cov>
+PG_HD KrankRec krank_ring_cut(uint32_t x, uint32_t best, uint32_t succ, Cov cov_of) {
+    const bool end = krank_fwd(best) ? succ == best : x == best;
+    return end ? krank_end(x, KUNITIG_CYCLE) : krank_link(succ, cov_of(succ));
+}
+
+// measure: the length of the start `start` for the scan, 0 for the end of a chain that is not emitted.  fin = the final generation
+template <int NW>
+PG_HD uint32_t krank_measure(uint64_t start, const uint64_t* tab, const KrankView& v, const KrankRec* fin, int K) {
+    const uint32_t s = krank_id(v.node_of[kunitig_start_slot(start)], kunitig_start_fwd(start));
+    const KrankRec r = fin[s];
+    const uint32_t n = r.dist + 1;
+    if (kunitig_start_reason(start) == KUNITIG_CYCLE) return n;
+    const bool lost = kmer_less<NW>(krank_kmer<NW>(tab, v, krank_flip(r.ptr), K), krank_kmer<NW>(tab, v, s, K));
+    return lost ? 0u : n;
+}
+
+// place: start `start` of n k-mers (0: not kept) whose row begins at word `at` and which is unitig u with `base` k-mers before it.
+// fin / place = the final generation and the other one
+template <int NW>
+PG_HD void krank_place(uint64_t start, uint32_t n, uint64_t u, uint64_t at, uint64_t base, const uint64_t* tab, const KrankView& v, const KrankRec* fin,
+                       KrankRec* place, int K, uint64_t* word_off_out, uint64_t* kmer_base_out, uint64_t* report) {
+    const uint64_t slot = kunitig_start_slot(start);
+    const uint32_t s = krank_id(v.node_of[slot], kunitig_start_fwd(start)), left = kunitig_start_reason(start);
+    const KrankRec r = fin[s];
+    place[s] = KrankRec{0, n, at};
+    if (left == KUNITIG_CYCLE) place[krank_flip(r.ptr)] = KrankRec{0, 0, 0};      // (the ring's other cut side is no start: nobody else writes it)
+    if (!n) return;
+    if (word_off_out) word_off_out[u] = at;
+    if (kmer_base_out) kmer_base_out[u] = base;
+    if (report) {
+        report[2 * u] = kunitig_report_word((uint64_t)n + (uint64_t)K - 1, left, krank_reason(r));
+        report[2 * u + 1] = kidx_coverage(tab[slot * map_slot_words<NW>() + NW]) + krank_cov(r);
+    }
+}
+
+// emit: node `node` into its unitig's row.  merge(word index, bits) ORs into packed_out
+template <int NW, typename Merge>
+PG_HD void krank_emit(uint32_t node, const uint64_t* tab, const KrankView& v, const KrankRec* fin, const KrankRec* place, int K, Merge merge) {
+    const KrankRec rf = fin[krank_id(node, true)], rr = fin[krank_id(node, false)];
+    const KrankRec pb = place[krank_flip(rr.ptr)];                                // the start that reads the node as stored
+    const bool fwd = pb.dist != 0;
+    const KrankRec p = fwd ? pb : place[krank_flip(rf.ptr)];
+    if (!p.dist) return;
+    const uint32_t rank = fwd ? rr.dist : rf.dist;
+    const Kmer<NW> a = krank_kmer<NW>(tab, v, krank_id(node, fwd), K);
+    if (!rank) {
+        const Kmer<NW> first = kunitig_left_aligned<NW>(a, K);
+#pragma unroll
+        for (int q = 0; q < NW; q++)
+            if (q <= (K - 1) / 32) merge(p.cov + (uint64_t)q, first.w[q]);
+        return;
+    }
+    const uint64_t pos = (uint64_t)rank + (uint64_t)K - 1;
+    merge(p.cov + pos / 32, (a.w[NW - 1] & 3ull) << (62 - 2 * (int)(pos & 31)));
+}
+
+// words that hold every row of any compaction of an index of `keys` keys: a unitig of n k-mers has at most (n + K + 30) / 32
+PG_HD uint64_t krank_words_bound(uint64_t keys, int K) { return (keys * (uint64_t)(K + 31) + 31) / 32; }
+
+// The caller's side of the device engine (kindex_kernels.hip), asynchronous on `stream`: count mode when d_packed_out is null
+int kunitig_device_unitigs_ranked(::pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out,
+                                  uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_report, uint64_t* d_totals, void* stream);
+
+}  // namespace pg
