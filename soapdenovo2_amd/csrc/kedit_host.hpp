@@ -9,7 +9,7 @@
 
 #include "../../include/soapdenovo2_amd.h"
 #include "kedit.hpp"
-#include "kindex.hpp"
+#include "kunitig_host.hpp"
 
 void pg_set_error(const std::string& s);
 
@@ -19,44 +19,31 @@ template <int NW, class Op>
 void kedit_host_round(pg_kindex* ix, const typename Op::Params& pr, uint64_t* totals) {
     constexpr int SW = map_slot_words<NW>();
     const int K = ix->K;
-    KidxRank& t = ix->ranks[0];
-    uint64_t* tab = t.tab.data();
-    const uint64_t mask = t.slots - 1;
-    const KunitigParams up = Op::ends(pr);
+    uint64_t* tab = ix->ranks[0].tab.data();
+    const KunitigHostTable<NW> t(ix);
     std::vector<uint64_t> starts;
     std::vector<uint32_t> lens;
-    auto find = [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); };
+    auto find = t.find();
     auto zero = [tab](uint64_t slot) { tab[slot * SW + NW] = 0; };
     auto clear = [tab](uint64_t slot, bool fwd, int a) {
         const uint64_t keep = (uint64_t)kedit_keep_mask(fwd, a);
         tab[slot * SW + NW] &= kedit_in_half(fwd) ? keep << 32 | 0xffffffffull : keep | 0xffffffffull << 32;
     };
-    auto node_of = [&](uint64_t start) {
-        const uint64_t* sl = tab + kunitig_start_slot(start) * SW;
-        return kunitig_node<NW>(kidx_record_key<NW>(sl), sl[NW], kunitig_start_slot(start), kunitig_start_fwd(start), K);
-    };
-    uint64_t solid = 0, removed = 0, kmers = 0, kept = 0;
+    uint64_t removed = 0, kmers = 0, kept = 0;
     // 1. the ends, as the unitigs find them: every end side of a solid k-mer is a start
-    for (uint64_t e = 0; e < t.slots; e++) {
-        if (tab[e * SW + NW + 1] == KIDX_EMPTY || !kcor_solid_word(tab[e * SW + NW], pr.min_cov)) continue;
-        solid++;
-        uint32_t reasons[2];
-        const uint32_t ends = kunitig_ends<NW>(kidx_record_key<NW>(tab + e * SW), tab[e * SW + NW], e, K, up, find, reasons);
-        for (int side = 0; side < 2; side++)
-            if (ends >> side & 1) starts.push_back(kunitig_start(e, side == 0, reasons[side]));
-    }
+    const uint64_t solid = kunitig_host_ends<NW>(t, Op::ends(pr), starts);
     // 2. decide: every start over the table as it stands
     for (uint64_t s : starts) {
         const uint32_t left = kunitig_start_reason(s);
         KeditDecision d{0, false, false};
-        if (Op::starts(left)) d = Op::template decide<NW>(node_of(s), left, K, pr, find);
+        if (Op::starts(left)) d = Op::template decide<NW>(t.node_of(s), left, K, pr, find);
         lens.push_back(d.minor ? d.n : 0);
         kept += d.candidate && !d.minor;
     }
     // 3. apply
     for (size_t i = 0; i < starts.size(); i++) {
         if (!lens[i]) continue;
-        Op::template apply<NW>(node_of(starts[i]), lens[i], K, pr, find, zero, clear);
+        Op::template apply<NW>(t.node_of(starts[i]), lens[i], K, pr, find, zero, clear);
         removed++;
         kmers += lens[i];
     }

@@ -36,6 +36,14 @@
 //                              operator's kernels add where a lane's counts come from and what is done with the offsets
 //   the scratch                KidxScratch (kindex.hpp), one each for the trim, the corrector on a cut index and the unitigs:
 //                              kidx_scratch_begin / _end / _free.  kidx_settled is the one way out of an entry point over the ranks
+//   the scratch of ix->uni     for the unitigs by walking, by list ranking and an edit round: laid out once, by kunitig_plan
+//                              (kunitig.hpp: word offsets and the total from keys, slots and the kind), bound by kunitig_bind and
+//                              krank_bind; kunitig_call_begin is what the three drivers begin with (device, plan, the two grids with
+//                              their refusals, kidx_scratch_begin, the leading words and the walk's covered bits zeroed), kunitig_scan
+//                              the scan's two launches of both engines
+//   the finish                 kunitig_finish and kunitig_finish_tail (kunitig.hpp): the eight totals, the go decision, the last
+//                              offsets and the tail's zero words, for kunitig_scan_sums_kernel's thread 0 and both host twins
+//   a published slot's word    kidx_published_word: 0 past the table or where the slot is empty; the ends, number and sweep kernels
 // The index cut over ranks (kindex.hpp; pg_kindex_build_sharded, pg_kindex_query_words):
 //   kidx_count_owners_kernel   a lane per record of a device part, on the device where the part lies: the owners of all n ranks at once
 //                              into an LDS histogram (n <= 256 bins: 1 KB, zeroed and flushed per workgroup), one global atomicAdd per
@@ -72,6 +80,8 @@
 //   krank_number_kernel        a workgroup per 4 096 slots: a solid key takes a node id, one atomicAdd a workgroup
 //   krank_sweep_kernel         a lane per slot: kunitig_side on both sides (the ends kernel's two lookups); an end side becomes an end
 //                              record and a start, an open one a link to its successor
+// Every pass over the nodes is krank.hpp's: its launch-uniform decision (krank_*_pass), its item body (krank_*_item) and what it leaves
+// in the control words (krank_*_done); a kernel adds the grid-stride loop, the host twin a plain one.  No control word is named here
 //   krank_jump_kernel          round j over the oriented nodes, a grid of at most 4 096 workgroups striding them: krank_jump from the
 //                              generation the control words name into the other; a round behind one in which no record became done ends
 //                              after one read a workgroup
@@ -447,18 +457,12 @@ __global__ __launch_bounds__(256) void ktrim_pack_kernel(const uint64_t* __restr
 }
 
 // ---- the unitigs: ends, measure, rings, the scan of the kept starts' counts, write (kunitig.hpp) ----
-// The scratch of one compaction.  ctr: KUNITIG_C_*; starts / lens: `cap` entries, the chains' starts first and the rings' behind them;
-// sums: the scan's, KIDX_COUNTS a block of 256 starts; bits: a covered bit a slot
-enum : int { KUNITIG_C_STARTS = 0, KUNITIG_C_CYCLIC = 1, KUNITIG_C_SOLID = 2, KUNITIG_C_CUT = 3, KUNITIG_C_GO = 4, KUNITIG_CTRS = 8 };
-struct KunitigScratch {
-    unsigned long long* ctr;
-    uint64_t* starts;
-    uint32_t* lens;
-    uint64_t* sums;
-    uint32_t* bits;
-    uint64_t cap;
-};
-
+// The scratch of one compaction is kunitig.hpp's: KunitigScratch, laid out by kunitig_plan
+// the word of the published slot at sl; 0 past the table (inside: the slot is one of the table's) or where the slot is empty
+template <int NW>
+__device__ __forceinline__ uint64_t kidx_published_word(const uint64_t* sl, bool inside) {
+    return inside && sl[NW + 1] != KIDX_EMPTY ? sl[NW] : 0;
+}
 __device__ __forceinline__ uint64_t kunitig_n_starts(const KunitigScratch& s) {
     const uint64_t n = s.ctr[KUNITIG_C_STARTS];
     return n < s.cap ? n : s.cap;
@@ -484,7 +488,7 @@ __global__ __launch_bounds__(256) void kunitig_ends_kernel(const uint64_t* __res
     constexpr int SW = map_slot_words<NW>();
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, mask = slots - 1;
     const uint64_t* sl = tab + e * SW;
-    const uint64_t w = e < slots && sl[NW + 1] != KIDX_EMPTY ? sl[NW] : 0;
+    const uint64_t w = kidx_published_word<NW>(sl, e < slots);
     const bool solid = kcor_solid_word(w, pr.min_cov);
     const uint64_t wave_solid = __ballot(solid);   // (every lane of the wave is here)
     if ((threadIdx.x & 63) == 0 && wave_solid) atomicAdd(s.ctr + KUNITIG_C_SOLID, (unsigned long long)__popcll(wave_solid));
@@ -547,21 +551,10 @@ __global__ __launch_bounds__(256) void kunitig_scan_sums_kernel(KunitigScratch s
                                                                 uint64_t* __restrict__ kmer_base_out, uint64_t* __restrict__ totals) {
     const KidxCounts all = kidx_scan_block_sums(s.sums, (kunitig_n_starts(s) + 255) / 256);
     if (threadIdx.x != 0) return;
-    const uint64_t unitigs = all.c[0], words = all.c[1], kmers = all.c[2];
-    const bool overflow = packed_out && (unitigs > cap_unitigs || words + (uint64_t)tail > cap_words), go = packed_out && !overflow;
-    totals[KUNITIG_T_UNITIGS] = unitigs;
-    totals[KUNITIG_T_WORDS] = words + (uint64_t)tail;
-    totals[KUNITIG_T_BASES] = kmers + unitigs * (uint64_t)(K - 1);
-    totals[KUNITIG_T_COVERED] = kmers;
-    totals[KUNITIG_T_SOLID] = s.ctr[KUNITIG_C_SOLID];
-    totals[KUNITIG_T_CYCLIC] = s.ctr[KUNITIG_C_CYCLIC];
-    totals[KUNITIG_T_CUT] = s.ctr[KUNITIG_C_CUT];
-    totals[KUNITIG_T_OVERFLOW] = overflow ? 1 : 0;
+    const bool go = kunitig_finish(all, K, tail, s.ctr[KUNITIG_C_SOLID], s.ctr[KUNITIG_C_CYCLIC], s.ctr[KUNITIG_C_CUT], cap_unitigs, cap_words,
+                                   packed_out != nullptr, totals);
     s.ctr[KUNITIG_C_GO] = go ? 1 : 0;
-    if (!go) return;
-    if (word_off_out) word_off_out[unitigs] = words;
-    if (kmer_base_out) kmer_base_out[unitigs] = kmers;
-    for (int q = 0; q < tail; q++) packed_out[words + q] = 0;
+    if (go) kunitig_finish_tail(all, tail, packed_out, word_off_out, kmer_base_out);
 }
 
 // a lane per start: the scan inside the workgroup again, and a kept start writes its offsets, walks once more into its row, and reports
@@ -612,9 +605,7 @@ __global__ __launch_bounds__(256) void krank_number_kernel(const uint64_t* __res
 #pragma unroll
     for (int k = 0; k < KRANK_NUMBER_EACH; k++) {
         const uint64_t e = base + (uint64_t)k * 256;
-        const uint64_t* sl = tab + e * SW;
-        const uint64_t w = e < slots && sl[NW + 1] != KIDX_EMPTY ? sl[NW] : 0;
-        mine |= kcor_solid_word(w, min_cov) ? 1u << k : 0u;
+        mine |= kcor_solid_word(kidx_published_word<NW>(tab + e * SW, e < slots), min_cov) ? 1u << k : 0u;
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t upto = (uint32_t)__popc(mine);         // the inclusive scan of the lanes' counts over the workgroup (every lane is here)
@@ -646,82 +637,64 @@ __global__ __launch_bounds__(256) void krank_number_kernel(const uint64_t* __res
 template <int NW>
 __global__ __launch_bounds__(256) void krank_sweep_kernel(const uint64_t* __restrict__ tab, uint64_t slots, int K, KunitigParams pr, KunitigScratch s, KrankView v,
                                                           uint32_t* ctl) {
-    constexpr int SW = map_slot_words<NW>();
     const uint64_t e = krank_lane(), mask = slots - 1;
-    const uint64_t* sl = tab + e * SW;
-    const uint64_t w = e < slots && sl[NW + 1] != KIDX_EMPTY ? sl[NW] : 0;
+    const uint64_t* sl = tab + e * map_slot_words<NW>();
+    const uint64_t w = kidx_published_word<NW>(sl, e < slots);
     bool open = false;
     if (kcor_solid_word(w, pr.min_cov))
-        open = krank_sweep<NW>(v, sl, e, K, pr, [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); },
+        open = krank_sweep<NW>(v, sl, e, K, pr,
+                               [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); },
                                [&s](uint64_t start) { kunitig_append(s, start, 0); });
-    if (open) ctl[KRANK_GO] = 1;                   // (every writer writes the same)
+    krank_sweep_done(ctl, open);
 }
 
-// round j: every record jumps from the generation the control words name into the other; a round behind one in which nothing became
-// done passes the generation on and ends
+// The passes over the nodes are krank.hpp's, each a launch-uniform decision, an item body under a grid-stride loop, and what the pass
+// leaves behind in the control words.  Round j: a round behind one in which nothing became done passes the generation on and ends
 __global__ __launch_bounds__(256) void krank_jump_kernel(KunitigScratch s, KrankView v, uint32_t* ctl, int j) {
-    const uint32_t g = ctl[KRANK_GEN + j];
+    const KrankPass p = krank_jump_pass(ctl, j);
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-    if (!ctl[KRANK_GO + j]) {                      // (uniform over the launch)
-        if (first) ctl[KRANK_GEN + j + 1] = g;
+    bool any = false;
+    if (!p.go) {                                   // (uniform over the launch)
+        krank_jump_done(p, ctl, j, any, first);
         return;
     }
-    const KrankRec* src = v.rec + (uint64_t)g * v.n2;
-    KrankRec* dst = v.rec + (uint64_t)(g ^ 1u) * v.n2;
-    bool any = false;
-    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) {
-        bool became;
-        dst[x] = krank_jump(src[x], src, became);
-        any = any || became;
-    }
-    if (any) ctl[KRANK_GO + j + 1] = 1;
-    if (first) ctl[KRANK_GEN + j + 1] = g ^ 1u;
+    const KrankRec* src = krank_cur(v, p);
+    KrankRec* dst = krank_other(v, p);
+    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) krank_jump_item(src, dst, x, any);
+    krank_jump_done(p, ctl, j, any, first);
 }
 
 // the rings: a record the R rounds did not finish opens its window in the free generation
 __global__ __launch_bounds__(256) void krank_ring_init_kernel(KunitigScratch s, KrankView v, uint32_t* ctl, int R) {
-    const uint32_t g = ctl[KRANK_GEN + R];
-    const KrankRec* fin = v.rec + (uint64_t)g * v.n2;
-    KrankRec* spare = v.rec + (uint64_t)(g ^ 1u) * v.n2;
+    const KrankPass p = krank_ring_init_pass(ctl, R);
+    const KrankRec* fin = krank_cur(v, p);
+    KrankRec* spare = krank_other(v, p);
     bool any = false;
-    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) {
-        if (krank_done(fin[x])) continue;
-        krank_min_store(spare + x, 0, KrankMin{v.succ0[x], (uint32_t)x});
-        any = true;
-    }
-    if (any) ctl[KRANK_RING] = 1;
+    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) krank_ring_init_item(fin, spare, v, x, any);
+    krank_ring_init_done(ctl, any);
 }
 
 // round r of the rings' windows; ends at once when there is no ring
 template <int NW>
 __global__ __launch_bounds__(256) void krank_min_kernel(const uint64_t* __restrict__ tab, KunitigScratch s, KrankView v, const uint32_t* ctl, int R, int r) {
-    if (!ctl[KRANK_RING]) return;                  // (uniform over the launch)
-    const uint32_t g = ctl[KRANK_GEN + R];
-    const KrankRec* fin = v.rec + (uint64_t)g * v.n2;
-    KrankRec* spare = v.rec + (uint64_t)(g ^ 1u) * v.n2;
-    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) {
-        if (krank_done(fin[x])) continue;
-        krank_min_store(spare + x, (r & 1) ^ 1, krank_min_jump<NW>(krank_min_load(spare + x, r & 1), spare, r & 1, tab, v));
-    }
+    const KrankPass p = krank_ring_pass(ctl, R);
+    if (!p.go) return;                             // (uniform over the launch)
+    const KrankRec* fin = krank_cur(v, p);
+    KrankRec* spare = krank_other(v, p);
+    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) krank_min_item<NW>(fin, spare, v, tab, r, x);
 }
 
 // the rings become chains from their least members, which are appended to the start list, and the rounds may run again
 template <int NW>
 __global__ __launch_bounds__(256) void krank_ring_cut_kernel(const uint64_t* __restrict__ tab, KunitigScratch s, KrankView v, uint32_t* ctl, int R) {
-    if (!ctl[KRANK_RING]) return;                  // (uniform over the launch)
-    const uint32_t g = ctl[KRANK_GEN + R];
-    KrankRec* fin = v.rec + (uint64_t)g * v.n2;
-    const KrankRec* spare = v.rec + (uint64_t)(g ^ 1u) * v.n2;
-    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride()) {
-        if (krank_done(fin[x])) continue;
-        const uint32_t best = krank_min_load(spare + x, R & 1).best;
-        fin[x] = krank_ring_cut((uint32_t)x, best, v.succ0[x], [tab, &v](uint32_t y) { return kidx_coverage(krank_slot<NW>(tab, v, y)[NW]); });
-        if (best == (uint32_t)x && krank_fwd(best)) {
-            kunitig_append(s, kunitig_start(v.slot_of[x >> 1], true, KUNITIG_CYCLE), 0);
-            atomicAdd(s.ctr + KUNITIG_C_CYCLIC, 1ull);
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) ctl[KRANK_GO + R] = 1;
+    const KrankPass p = krank_ring_pass(ctl, R);
+    if (!p.go) return;                             // (uniform over the launch)
+    KrankRec* fin = krank_cur(v, p);
+    const KrankRec* spare = krank_other(v, p);
+    for (uint64_t x = krank_lane(), n = krank_n(s); x < n; x += krank_stride())
+        krank_ring_cut_item<NW>(fin, spare, v, tab, R, x, [&s](uint64_t start) { kunitig_append(s, start, 0); },
+                                [&s] { atomicAdd(s.ctr + KUNITIG_C_CYCLIC, 1ull); });
+    krank_ring_cut_done(ctl, R, blockIdx.x == 0 && threadIdx.x == 0);
 }
 
 // a lane per start: its length for the scan from its record
@@ -729,7 +702,7 @@ template <int NW>
 __global__ __launch_bounds__(256) void krank_measure_kernel(const uint64_t* __restrict__ tab, int K, KunitigScratch s, KrankView v, const uint32_t* ctl, int R) {
     const uint64_t i = krank_lane();
     if (i >= kunitig_n_starts(s)) return;
-    s.lens[i] = krank_measure<NW>(s.starts[i], tab, v, v.rec + (uint64_t)ctl[KRANK_GEN + 2 * R] * v.n2, K);
+    s.lens[i] = krank_measure<NW>(s.starts[i], tab, v, krank_cur(v, krank_final_pass(ctl, R)), K);
 }
 
 // the rows' words zeroed where the scan said go: the emit pass ORs into them
@@ -748,9 +721,9 @@ __global__ __launch_bounds__(256) void krank_place_kernel(const uint64_t* __rest
     const uint64_t i = krank_lane();
     const KidxCounts own = kunitig_lane_counts(s, n_starts, K, i), before = kidx_scan_before(own, s.sums);
     if (i >= n_starts) return;                     // (no barrier follows)
-    const uint32_t g = ctl[KRANK_GEN + 2 * R];
-    krank_place<NW>(s.starts[i], (uint32_t)own.c[2], before.c[0], before.c[1], before.c[2], tab, v, v.rec + (uint64_t)g * v.n2,
-                    v.rec + (uint64_t)(g ^ 1u) * v.n2, K, word_off_out, kmer_base_out, report);
+    const KrankPass f = krank_final_pass(ctl, R);
+    krank_place<NW>(s.starts[i], (uint32_t)own.c[2], before.c[0], before.c[1], before.c[2], tab, v, krank_cur(v, f), krank_other(v, f), K, word_off_out, kmer_base_out,
+                    report);
 }
 
 // every node into its row: krank_emit with a 64-bit atomicOr
@@ -758,17 +731,14 @@ template <int NW>
 __global__ __launch_bounds__(256) void krank_emit_kernel(const uint64_t* __restrict__ tab, int K, KunitigScratch s, KrankView v, const uint32_t* ctl, int R,
                                                          uint64_t* packed_out) {
     if (!s.ctr[KUNITIG_C_GO]) return;              // (uniform over the launch)
-    const uint32_t g = ctl[KRANK_GEN + 2 * R];
-    const KrankRec *fin = v.rec + (uint64_t)g * v.n2, *place = v.rec + (uint64_t)(g ^ 1u) * v.n2;
+    const KrankPass f = krank_final_pass(ctl, R);
     for (uint64_t node = krank_lane(), n = s.ctr[KUNITIG_C_SOLID]; node < n; node += krank_stride())
-        krank_emit<NW>((uint32_t)node, tab, v, fin, place, K,
+        krank_emit<NW>((uint32_t)node, tab, v, krank_cur(v, f), krank_other(v, f), K,
                        [packed_out](uint64_t at, uint64_t bits) { atomicOr((unsigned long long*)packed_out + at, (unsigned long long)bits); });
 }
 
 // ---- the operators that edit the graph: ends (the unitigs' kernel), decide, apply, the totals (kedit.hpp; ktip.hpp, kbubble.hpp) ----
-// A round's counters lie behind the unitigs' in the same scratch: unitigs removed, k-mers removed, candidates kept
-enum : int { KEDIT_C_REMOVED = 5, KEDIT_C_KMERS = 6, KEDIT_C_KEPT = 7 };
-static_assert(KEDIT_C_KEPT < KUNITIG_CTRS && KEDIT_C_REMOVED > KUNITIG_C_GO, "a round's counters lie in the scratch, behind the unitigs'");
+// A round's counters lie behind the unitigs' in the same scratch (kunitig.hpp: KEDIT_C_*)
 
 // the table as an operator reaches it: the lookup, a k-mer's word zeroed with a plain store, and a junction's counter taken out with an
 // atomicAnd on the 32-bit half that holds it: another lane may clear another counter of that half
@@ -1396,46 +1366,58 @@ int ktrim_device_times(::pg_kindex* ix, double out[4]) {
 }
 
 // ---- the unitigs ----
-// Six launches on the caller's stream and no host wait: ends, measure, rings, the scan's two, write (count mode: without the last).  The
-// start list holds 2 * keys entries: a stored k-mer has two sides, a chain's start is an end side, and a ring's least member has none
+// What a call on the scratch of ix->uni begins with, whatever its kind: the device, the plan (kunitig.hpp: kunitig_plan), the grids over
+// the slots and over the start list with their refusals, the scratch taken on the stream and bound, its leading words zeroed -- and the
+// walk's covered bits.  The caller ends with kidx_scratch_end
+struct KunitigCall {
+    KunitigPlan plan;
+    KunitigScratch s;
+    dim3 slot_grid, start_grid;
+};
+int kunitig_call_begin(::pg_kindex* ix, KunitigKind kind, hipStream_t st, KunitigCall& c) {
+    const KidxRank& t = ix->ranks[0];
+    if (int rc = kidx_set_device(ix->device)) return rc;
+    c.plan = kunitig_plan(t.keys, t.slots, kind);
+    if (int rc = kidx_launch_blocks(t.slots, 256, "table too large", &c.slot_grid)) return rc;
+    if (int rc = kidx_launch_blocks(c.plan.cap, 256, "too many starts", &c.start_grid)) return rc;
+    if (int rc = kidx_scratch_begin(ix->uni, c.plan.total, st)) return rc;
+    c.s = kunitig_bind(ix->uni.d, c.plan);
+    KIDX_HIP(hipMemsetAsync(ix->uni.d, 0, c.plan.zero * sizeof(uint64_t), st));
+    if (c.s.bits) KIDX_HIP(hipMemsetAsync(c.s.bits, 0, (t.slots + 63) / 64 * sizeof(uint64_t), st));
+    return PG_OK;
+}
+// the scan over the start list's lengths and the finish, for both engines: two launches
+int kunitig_scan(const ::pg_kindex* ix, const KunitigCall& c, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out, uint64_t* d_word_off_out,
+                 uint64_t* d_kmer_base_out, uint64_t* d_totals, hipStream_t st) {
+    hipLaunchKernelGGL(kunitig_block_sums_kernel, c.start_grid, dim3(256), 0, st, c.s, ix->K);
+    hipLaunchKernelGGL(kunitig_scan_sums_kernel, dim3(1), dim3(256), 0, st, c.s, ix->K, ix->nw + 1, cap_unitigs, cap_words, d_packed_out, d_word_off_out,
+                       d_kmer_base_out, d_totals);
+    KIDX_HIP(hipGetLastError());
+    return PG_OK;
+}
+
+// Six launches on the caller's stream and no host wait: ends, measure, rings, the scan's two, write (count mode: without the last)
 int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out,
                            uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_report, uint64_t* d_totals, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const KidxRank& t = ix->ranks[0];
-    if (int rc = kidx_set_device(ix->device)) return rc;
-    const uint64_t cap = std::max<uint64_t>(2 * t.keys, 1);
-    dim3 slot_grid, start_grid;
-    if (int rc = kidx_launch_blocks(t.slots, 256, "table too large", &slot_grid)) return rc;
-    if (int rc = kidx_launch_blocks(cap, 256, "too many starts", &start_grid)) return rc;
-    // Scratch, in words: the counters, the starts, the lengths (two a word), the block sums, the covered bits (64 a word)
-    const uint64_t w_lens = (cap + 1) / 2, w_sums = (uint64_t)start_grid.x * KIDX_COUNTS, w_bits = (t.slots + 63) / 64;
-    if (int rc = kidx_scratch_begin(ix->uni, KUNITIG_CTRS + cap + w_lens + w_sums + w_bits, st)) return rc;
-    KunitigScratch s;
-    s.ctr = (unsigned long long*)ix->uni.d;
-    s.starts = ix->uni.d + KUNITIG_CTRS;
-    s.lens = (uint32_t*)(s.starts + cap);
-    s.sums = s.starts + cap + w_lens;
-    s.bits = (uint32_t*)(s.sums + w_sums);
-    s.cap = cap;
-    KIDX_HIP(hipMemsetAsync(s.ctr, 0, KUNITIG_CTRS * sizeof(uint64_t), st));
-    KIDX_HIP(hipMemsetAsync(s.bits, 0, w_bits * sizeof(uint64_t), st));
+    KunitigCall c;
+    if (int rc = kunitig_call_begin(ix, KUNITIG_KIND_WALK, st, c)) return rc;
+    const KunitigScratch& s = c.s;
     const dim3 block(256);
-    const int K = ix->K, tail = ix->nw + 1;
+    const int K = ix->K;
     const uint64_t mask = t.slots - 1;
     if (int rc = kidx_launch(ix, [&](auto nw) {
             constexpr int NW = decltype(nw)::value;
-            hipLaunchKernelGGL((kunitig_ends_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, pr, s);
-            hipLaunchKernelGGL((kunitig_measure_kernel<NW>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
-            hipLaunchKernelGGL((kunitig_rings_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, pr, s);
+            hipLaunchKernelGGL((kunitig_ends_kernel<NW>), c.slot_grid, block, 0, st, t.d_tab, t.slots, K, pr, s);
+            hipLaunchKernelGGL((kunitig_measure_kernel<NW>), c.start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
+            hipLaunchKernelGGL((kunitig_rings_kernel<NW>), c.slot_grid, block, 0, st, t.d_tab, t.slots, K, pr, s);
         }))
         return rc;
-    hipLaunchKernelGGL(kunitig_block_sums_kernel, start_grid, block, 0, st, s, K);
-    hipLaunchKernelGGL(kunitig_scan_sums_kernel, dim3(1), block, 0, st, s, K, tail, cap_unitigs, cap_words, d_packed_out, d_word_off_out, d_kmer_base_out,
-                       d_totals);
-    KIDX_HIP(hipGetLastError());
+    if (int rc = kunitig_scan(ix, c, cap_unitigs, cap_words, d_packed_out, d_word_off_out, d_kmer_base_out, d_totals, st)) return rc;
     if (d_packed_out)
         if (int rc = kidx_launch(ix, [&](auto nw) {
-                hipLaunchKernelGGL((kunitig_write_kernel<decltype(nw)::value>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s, d_packed_out,
+                hipLaunchKernelGGL((kunitig_write_kernel<decltype(nw)::value>), c.start_grid, block, 0, st, t.d_tab, mask, K, pr, s, d_packed_out,
                                    d_word_off_out, d_kmer_base_out, d_report);
             }))
             return rc;
@@ -1444,63 +1426,38 @@ int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t ca
 
 // The unitigs by list ranking (krank.hpp): no host wait and no guard.  R = krank_rounds(keys) is all the host knows, so
 // it launches 3 R rounds -- the chains', the rings' windows, the rings as chains -- and the device ends the ones with nothing to do:
-// 3 R + 7 launches in count mode, 3 more in full mode.  The scratch is the unitigs' with the ranking's arrays behind it
+// 3 R + 7 launches in count mode, 3 more in full mode.  The scratch is the unitigs' with the ranking's arrays in it
 int kunitig_device_unitigs_ranked(::pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out,
                                   uint64_t* d_word_off_out, uint64_t* d_kmer_base_out, uint64_t* d_report, uint64_t* d_totals, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const KidxRank& t = ix->ranks[0];
-    if (int rc = kidx_set_device(ix->device)) return rc;
-    const uint64_t cap = std::max<uint64_t>(2 * t.keys, 2), words_bound = std::max<uint64_t>(std::min(cap_words, krank_words_bound(t.keys, ix->K)), 1);
-    dim3 slot_grid, start_grid, node_grid, word_grid;
-    if (int rc = kidx_launch_blocks(t.slots, 256, "table too large", &slot_grid)) return rc;
-    if (int rc = kidx_launch_blocks(cap, 256, "too many starts", &start_grid)) return rc;
-    const dim3 number_grid((slot_grid.x + KRANK_NUMBER_EACH - 1) / KRANK_NUMBER_EACH);
-    node_grid = dim3(std::min(start_grid.x, KRANK_BLOCKS));
-    word_grid = dim3((unsigned)std::min<uint64_t>((words_bound + 255) / 256, KRANK_BLOCKS));
-    // Scratch, in words: the counters, the control words (two a word), the records (two generations of `cap`, two words each), the
-    // starts, the lengths (two a word), the block sums, succ0 and slot_of and node_of (two a word)
-    const uint64_t w_ctl = KRANK_CTL / 2, w_rec = 4 * cap, w_lens = (cap + 1) / 2, w_sums = (uint64_t)start_grid.x * KIDX_COUNTS, w_succ = cap / 2,
-                   w_slot_of = (t.keys + 2) / 2, w_node_of = (t.slots + 1) / 2;
-    static_assert((KUNITIG_CTRS + KRANK_CTL / 2) % 2 == 0, "the records are 16-byte aligned");
-    if (int rc = kidx_scratch_begin(ix->uni, KUNITIG_CTRS + w_ctl + w_rec + cap + w_lens + w_sums + w_succ + w_slot_of + w_node_of, st)) return rc;
-    KunitigScratch s;
-    s.ctr = (unsigned long long*)ix->uni.d;
-    uint32_t* ctl = (uint32_t*)(ix->uni.d + KUNITIG_CTRS);
-    KrankView v;
-    v.rec = (KrankRec*)(ix->uni.d + KUNITIG_CTRS + w_ctl);
-    s.starts = ix->uni.d + KUNITIG_CTRS + w_ctl + w_rec;
-    s.lens = (uint32_t*)(s.starts + cap);
-    s.sums = s.starts + cap + w_lens;
-    s.bits = nullptr;
-    s.cap = cap;
-    v.succ0 = (uint32_t*)(s.sums + w_sums);
-    v.slot_of = (uint32_t*)(s.sums + w_sums + w_succ);
-    v.node_of = (uint32_t*)(s.sums + w_sums + w_succ + w_slot_of);
-    v.n2 = cap;
-    KIDX_HIP(hipMemsetAsync(ix->uni.d, 0, (KUNITIG_CTRS + w_ctl) * sizeof(uint64_t), st));
-    const dim3 block(256);
+    KunitigCall c;
+    if (int rc = kunitig_call_begin(ix, KUNITIG_KIND_RANK, st, c)) return rc;
+    const KunitigScratch& s = c.s;
+    const KrankView v = krank_bind(ix->uni.d, c.plan);
+    uint32_t* ctl = kunitig_at<uint32_t>(ix->uni.d, c.plan.ctl);
+    const uint64_t words_bound = std::max<uint64_t>(std::min(cap_words, krank_words_bound(t.keys, ix->K)), 1);
+    const dim3 block(256), number_grid((c.slot_grid.x + KRANK_NUMBER_EACH - 1) / KRANK_NUMBER_EACH), node_grid(std::min(c.start_grid.x, KRANK_BLOCKS)),
+        word_grid((unsigned)std::min<uint64_t>((words_bound + 255) / 256, KRANK_BLOCKS));
     const int K = ix->K, tail = ix->nw + 1, R = krank_rounds(t.keys);
     if (int rc = kidx_launch(ix, [&](auto nw) {
             constexpr int NW = decltype(nw)::value;
             hipLaunchKernelGGL((krank_number_kernel<NW>), number_grid, block, 0, st, t.d_tab, t.slots, pr.min_cov, s, v);
-            hipLaunchKernelGGL((krank_sweep_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, pr, s, v, ctl);
+            hipLaunchKernelGGL((krank_sweep_kernel<NW>), c.slot_grid, block, 0, st, t.d_tab, t.slots, K, pr, s, v, ctl);
             for (int j = 0; j < R; j++) hipLaunchKernelGGL(krank_jump_kernel, node_grid, block, 0, st, s, v, ctl, j);
             hipLaunchKernelGGL(krank_ring_init_kernel, node_grid, block, 0, st, s, v, ctl, R);
             for (int r = 0; r < R; r++) hipLaunchKernelGGL((krank_min_kernel<NW>), node_grid, block, 0, st, t.d_tab, s, v, ctl, R, r);
             hipLaunchKernelGGL((krank_ring_cut_kernel<NW>), node_grid, block, 0, st, t.d_tab, s, v, ctl, R);
             for (int j = R; j < 2 * R; j++) hipLaunchKernelGGL(krank_jump_kernel, node_grid, block, 0, st, s, v, ctl, j);
-            hipLaunchKernelGGL((krank_measure_kernel<NW>), start_grid, block, 0, st, t.d_tab, K, s, v, ctl, R);
+            hipLaunchKernelGGL((krank_measure_kernel<NW>), c.start_grid, block, 0, st, t.d_tab, K, s, v, ctl, R);
         }))
         return rc;
-    hipLaunchKernelGGL(kunitig_block_sums_kernel, start_grid, block, 0, st, s, K);
-    hipLaunchKernelGGL(kunitig_scan_sums_kernel, dim3(1), block, 0, st, s, K, tail, cap_unitigs, cap_words, d_packed_out, d_word_off_out, d_kmer_base_out,
-                       d_totals);
-    KIDX_HIP(hipGetLastError());
+    if (int rc = kunitig_scan(ix, c, cap_unitigs, cap_words, d_packed_out, d_word_off_out, d_kmer_base_out, d_totals, st)) return rc;
     if (d_packed_out)
         if (int rc = kidx_launch(ix, [&](auto nw) {
                 constexpr int NW = decltype(nw)::value;
                 hipLaunchKernelGGL(krank_zero_kernel, word_grid, block, 0, st, s, d_totals, tail, d_packed_out);
-                hipLaunchKernelGGL((krank_place_kernel<NW>), start_grid, block, 0, st, t.d_tab, K, s, v, ctl, R, d_word_off_out, d_kmer_base_out, d_report);
+                hipLaunchKernelGGL((krank_place_kernel<NW>), c.start_grid, block, 0, st, t.d_tab, K, s, v, ctl, R, d_word_off_out, d_kmer_base_out, d_report);
                 hipLaunchKernelGGL((krank_emit_kernel<NW>), node_grid, block, 0, st, t.d_tab, K, s, v, ctl, R, d_packed_out);
             }))
             return rc;
@@ -1515,28 +1472,17 @@ template <class Op>
 int kedit_device_round(::pg_kindex* ix, const typename Op::Params& pr, uint64_t* d_totals, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const KidxRank& t = ix->ranks[0];
-    if (int rc = kidx_set_device(ix->device)) return rc;
-    const uint64_t cap = std::max<uint64_t>(2 * t.keys, 1);
-    dim3 slot_grid, start_grid;
-    if (int rc = kidx_launch_blocks(t.slots, 256, "table too large", &slot_grid)) return rc;
-    if (int rc = kidx_launch_blocks(cap, 256, "too many starts", &start_grid)) return rc;
-    if (int rc = kidx_scratch_begin(ix->uni, KUNITIG_CTRS + cap + (cap + 1) / 2, st)) return rc;
-    KunitigScratch s;
-    s.ctr = (unsigned long long*)ix->uni.d;
-    s.starts = ix->uni.d + KUNITIG_CTRS;
-    s.lens = (uint32_t*)(s.starts + cap);
-    s.sums = nullptr;
-    s.bits = nullptr;
-    s.cap = cap;
-    KIDX_HIP(hipMemsetAsync(s.ctr, 0, KUNITIG_CTRS * sizeof(uint64_t), st));
+    KunitigCall c;
+    if (int rc = kunitig_call_begin(ix, KUNITIG_KIND_EDIT, st, c)) return rc;
+    const KunitigScratch& s = c.s;
     const dim3 block(256);
     const int K = ix->K;
     const uint64_t mask = t.slots - 1;
     if (int rc = kidx_launch(ix, [&](auto nw) {
             constexpr int NW = decltype(nw)::value;
-            hipLaunchKernelGGL((kunitig_ends_kernel<NW>), slot_grid, block, 0, st, t.d_tab, t.slots, K, Op::ends(pr), s);
-            hipLaunchKernelGGL((kedit_decide_kernel<NW, Op>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
-            hipLaunchKernelGGL((kedit_apply_kernel<NW, Op>), start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
+            hipLaunchKernelGGL((kunitig_ends_kernel<NW>), c.slot_grid, block, 0, st, t.d_tab, t.slots, K, Op::ends(pr), s);
+            hipLaunchKernelGGL((kedit_decide_kernel<NW, Op>), c.start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
+            hipLaunchKernelGGL((kedit_apply_kernel<NW, Op>), c.start_grid, block, 0, st, t.d_tab, mask, K, pr, s);
         }))
         return rc;
     hipLaunchKernelGGL(kedit_totals_kernel, dim3(1), dim3(64), 0, st, s, d_totals);

@@ -18,7 +18,10 @@
 // one 2^r steps before its end becomes done in round r), so the next round has nothing to do and says so to the one after it.
 // Every round reads one generation of the records and writes the other.
 //
-// The passes, in order (kindex_kernels.hip: krank_*_kernel; kunitig_rank_host.cpp runs the same bodies one after the other):
+// The passes, in order (kindex_kernels.hip: krank_*_kernel; kunitig_rank_host.cpp runs the same bodies one after the other).  A pass
+// over the nodes is here whole: krank_*_pass is its decision, uniform over the launch, from the control words; krank_*_item its body
+// for one node; krank_*_done what it leaves in the control words.  A kernel is the decision, a grid-stride loop over the body, and done;
+// the twin the same with a plain loop:
 //   number    a solid slot takes a node id: node_of a slot, slot_of a node
 //   sweep     krank_sweep, a slot: both sides through kunitig_side; an end side becomes an end record and a start of the start list
 //             (kunitig_start, as kunitig_ends_kernel appends it), an open one a link to its successor with the successor's coverage; the
@@ -39,7 +42,7 @@
 //             flip(A).  The one with a place record that is kept names the row; the node ORs its last base in at position rank + K - 1,
 //             the node of rank 0 all K of its bases.  The rows were zeroed by a pass before.  No lane walks a chain
 //
-// Scratch (decided on the host from keys and slots, before the solid count is known): 100 bytes a key -- records 2 generations x 2
+// Scratch (kunitig.hpp: kunitig_plan, decided on the host from keys and slots, before the solid count is known): 100 bytes a key -- records 2 generations x 2
 // oriented nodes x 16, succ0 2 x 4, slot_of 4, the start list 2 x 8, the length list 2 x 4 -- and 4 bytes a slot for node_of; the block
 // sums and the control words are small change.  The other layout, node arrays indexed by slot, needs no node_of and no numbering pass
 // but 72 bytes a slot; a table is at most half full, so that is more than twice the bytes (19.3 GB against 10.7 GB on the 95.9 M-key,
@@ -80,16 +83,23 @@ PG_HD int krank_rounds(uint64_t keys) {
     return r;
 }
 
-// The scratch of the ranking behind the unitigs' (kindex_kernels.hip: KunitigScratch; the host twin's vectors): rec = two generations
-// of n2 records, generation g at rec + g * n2; n2 = 2 * keys
+// The scratch of the ranking behind the unitigs' (kunitig.hpp: kunitig_plan of KUNITIG_KIND_RANK; the host twin's vectors): rec = two
+// generations of n2 records, generation g at rec + g * n2; n2 = the plan's cap
 struct KrankView {
     KrankRec* rec;
     uint32_t *succ0, *node_of, *slot_of;
     uint64_t n2;
 };
 // The control words (32-bit, zeroed before a call).  Round j of 0 .. 2 R - 1 (the chains' rounds, then the rings' chains') runs when
-// GO + j is set and reads generation GEN + j; it sets GO + j + 1 when a record became done and writes GEN + j + 1.  RING: there is a ring
+// GO + j is set and reads generation GEN + j; it sets GO + j + 1 when a record became done and writes GEN + j + 1.  RING: there is a ring.
+// Nothing outside this file reads or writes one: every pass below comes with its launch-uniform decision (krank_*_pass) and what it
+// leaves for the passes behind it (krank_*_done)
 enum : int { KRANK_GO = 0, KRANK_GEN = 64, KRANK_RING = 128, KRANK_CTL = 192 };
+static_assert(KRANK_CTL == 2 * KUNITIG_PLAN_CTL, "the plan's control words");
+inline KrankView krank_bind(uint64_t* base, const KunitigPlan& p) {
+    return KrankView{kunitig_at<KrankRec>(base, p.rec), kunitig_at<uint32_t>(base, p.succ0), kunitig_at<uint32_t>(base, p.node_of),
+                     kunitig_at<uint32_t>(base, p.slot_of), p.cap};
+}
 
 template <int NW>
 PG_HD const uint64_t* krank_slot(const uint64_t* tab, const KrankView& v, uint32_t x) {
@@ -103,7 +113,7 @@ PG_HD Kmer<NW> krank_kmer(const uint64_t* tab, const KrankView& v, uint32_t x, i
 }
 
 // sweep: the solid key of slot e (node_of is complete) writes its two records of generation 0.  append(start) puts an end side into
-// the start list.  Returns whether a side is open
+// the start list.  Returns whether a side is open, which krank_sweep_done takes: an open side raises the first round's go flag
 template <int NW, typename Find, typename Append>
 PG_HD bool krank_sweep(const KrankView& v, const uint64_t* sl, uint64_t e, int K, const KunitigParams& pr, Find find, Append append) {
     const Kmer<NW> filter = kmer_filter<NW>(K), c = kidx_record_key<NW>(sl);
@@ -123,6 +133,18 @@ PG_HD bool krank_sweep(const KrankView& v, const uint64_t* sl, uint64_t e, int K
     }
     return open;
 }
+PG_HD void krank_sweep_done(uint32_t* ctl, bool open) {
+    if (open) ctl[KRANK_GO] = 1;                   // (every writer writes the same)
+}
+
+// A pass over the oriented nodes as every lane of its launch sees it (the twin: its one loop): whether it runs, and which generation
+// of the records the control words name: krank_cur is that one, krank_other the one that leaves free
+struct KrankPass {
+    bool go;
+    uint32_t g;
+};
+PG_HD KrankRec* krank_cur(const KrankView& v, const KrankPass& p) { return v.rec + (uint64_t)p.g * v.n2; }
+PG_HD KrankRec* krank_other(const KrankView& v, const KrankPass& p) { return v.rec + (uint64_t)(p.g ^ 1u) * v.n2; }
 
 // a round's step of one record: src = the generation read.  became: the record was not done and is now
 PG_HD KrankRec krank_jump(const KrankRec& own, const KrankRec* src, bool& became) {
@@ -131,6 +153,19 @@ PG_HD KrankRec krank_jump(const KrankRec& own, const KrankRec* src, bool& became
     const KrankRec q = src[own.ptr];
     became = krank_done(q);
     return KrankRec{q.ptr, own.dist + q.dist, own.cov + q.cov};
+}
+// Round j: every record jumps from the generation the control words name into the other; a round behind one in which nothing became
+// done does not run.  any: a record of the caller's became done.  `first` is true for one caller of the launch, which passes the
+// generation on
+PG_HD KrankPass krank_jump_pass(const uint32_t* ctl, int j) { return KrankPass{ctl[KRANK_GO + j] != 0, ctl[KRANK_GEN + j]}; }
+PG_HD void krank_jump_item(const KrankRec* src, KrankRec* dst, uint64_t x, bool& any) {
+    bool became;
+    dst[x] = krank_jump(src[x], src, became);
+    any = any || became;
+}
+PG_HD void krank_jump_done(const KrankPass& p, uint32_t* ctl, int j, bool any, bool first) {
+    if (any) ctl[KRANK_GO + j + 1] = 1;
+    if (first) ctl[KRANK_GEN + j + 1] = p.go ? p.g ^ 1u : p.g;
 }
 
 // A ring member's two window generations lie in its record of the generation the chains' rounds left free: generation 0 in (ptr, dist),
@@ -165,6 +200,45 @@ PG_HD KrankRec krank_ring_cut(uint32_t x, uint32_t best, uint32_t succ, Cov cov_
     const bool end = krank_fwd(best) ? succ == best : x == best;
     return end ? krank_end(x, KUNITIG_CYCLE) : krank_link(succ, cov_of(succ));
 }
+// The rings' passes, behind the chains' R rounds: fin = krank_cur, the generation those left, in which what is not done lies on a
+// ring; spare = krank_other, the windows.  The init always runs and says whether there is a ring; the windows' rounds and the cut run when there is one
+PG_HD KrankPass krank_ring_init_pass(const uint32_t* ctl, int R) { return KrankPass{true, ctl[KRANK_GEN + R]}; }
+PG_HD KrankPass krank_ring_pass(const uint32_t* ctl, int R) {
+    if (!ctl[KRANK_RING]) return KrankPass{false, 0};
+    return KrankPass{true, ctl[KRANK_GEN + R]};
+}
+// init: a record the rounds did not finish opens its window
+PG_HD void krank_ring_init_item(const KrankRec* fin, KrankRec* spare, const KrankView& v, uint64_t x, bool& any) {
+    if (krank_done(fin[x])) return;
+    krank_min_store(spare + x, 0, KrankMin{v.succ0[x], (uint32_t)x});
+    any = true;
+}
+PG_HD void krank_ring_init_done(uint32_t* ctl, bool any) {
+    if (any) ctl[KRANK_RING] = 1;
+}
+// round r of the windows
+template <int NW>
+PG_HD void krank_min_item(const KrankRec* fin, KrankRec* spare, const KrankView& v, const uint64_t* tab, int r, uint64_t x) {
+    if (krank_done(fin[x])) return;
+    krank_min_store(spare + x, (r & 1) ^ 1, krank_min_jump<NW>(krank_min_load(spare + x, r & 1), spare, r & 1, tab, v));
+}
+// the cut: the rings become chains from their least members, each of which is appended to the start list (append(start)) and counted
+// (ring()); then the rounds may run again
+template <int NW, typename Append, typename Ring>
+PG_HD void krank_ring_cut_item(KrankRec* fin, const KrankRec* spare, const KrankView& v, const uint64_t* tab, int R, uint64_t x, Append append, Ring ring) {
+    if (krank_done(fin[x])) return;
+    const uint32_t best = krank_min_load(spare + x, R & 1).best;
+    fin[x] = krank_ring_cut((uint32_t)x, best, v.succ0[x], [tab, &v](uint32_t y) { return kidx_coverage(krank_slot<NW>(tab, v, y)[NW]); });
+    if (best == (uint32_t)x && krank_fwd(best)) {
+        append(kunitig_start(v.slot_of[x >> 1], true, KUNITIG_CYCLE));
+        ring();
+    }
+}
+PG_HD void krank_ring_cut_done(uint32_t* ctl, int R, bool first) {
+    if (first) ctl[KRANK_GO + R] = 1;
+}
+// What all 2 R rounds left, for measure, place and emit: krank_cur is the final generation (fin), krank_other holds the place records
+PG_HD KrankPass krank_final_pass(const uint32_t* ctl, int R) { return KrankPass{true, ctl[KRANK_GEN + 2 * R]}; }
 
 // measure: the length of the start `start` for the scan, 0 for the end of a chain that is not emitted.  fin = the final generation
 template <int NW>

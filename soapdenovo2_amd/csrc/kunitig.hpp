@@ -36,6 +36,9 @@
 // that measures (row == null) or writes through the walk's base writer (KwalkText); both take the lookup as a function of the canonical
 // k-mer that also returns the slot, for the covered bit a slot.  Reason and length are kept with selects (DESIGN.md §11 on what stores
 // under branches inside such a loop became).
+// Behind the rule, what the two unitig engines and the edit rounds state once: the finish of a compaction (kunitig_finish,
+// kunitig_finish_tail) and the scratch of ix->uni (KunitigScratch, kunitig_plan, kunitig_bind) -- plain host code a program built
+// without the device engine can call.
 #pragma once
 #include "kwalk.hpp"
 
@@ -183,6 +186,93 @@ PG_HD uint32_t kunitig_ends(const Kmer<NW>& c, uint64_t w, uint64_t slot, int K,
 
 // what a start of n k-mers (0: the copy that is not emitted) adds to the scan: kept, words, k-mers
 PG_HD KidxCounts kunitig_counts(uint32_t n, int K) { return KidxCounts{{n ? 1ull : 0ull, n ? kunitig_row_words(n, K) : 0ull, n, 0}}; }
+
+// The finish of a compaction, for both engines, their kernels and their host twins.  kunitig_finish: the eight totals from the scan's
+// sums (kept, words, k-mers) and the counts, and the go decision: full mode, and the unitigs and their words with the tail fit the
+// capacities.  kunitig_finish_tail, where the decision was go: the batch's last offsets and the tail's zero words
+PG_HD bool kunitig_finish(const KidxCounts& all, int K, int tail, uint64_t solid, uint64_t cyclic, uint64_t cut, uint64_t cap_unitigs,
+                          uint64_t cap_words, bool full, uint64_t* totals) {
+    const uint64_t unitigs = all.c[0], words = all.c[1], kmers = all.c[2];
+    const bool overflow = full && (unitigs > cap_unitigs || words + (uint64_t)tail > cap_words);
+    totals[KUNITIG_T_UNITIGS] = unitigs;
+    totals[KUNITIG_T_WORDS] = words + (uint64_t)tail;
+    totals[KUNITIG_T_BASES] = kmers + unitigs * (uint64_t)(K - 1);
+    totals[KUNITIG_T_COVERED] = kmers;
+    totals[KUNITIG_T_SOLID] = solid;
+    totals[KUNITIG_T_CYCLIC] = cyclic;
+    totals[KUNITIG_T_CUT] = cut;
+    totals[KUNITIG_T_OVERFLOW] = overflow ? 1 : 0;
+    return full && !overflow;
+}
+PG_HD void kunitig_finish_tail(const KidxCounts& all, int tail, uint64_t* packed_out, uint64_t* word_off_out, uint64_t* kmer_base_out) {
+    if (word_off_out) word_off_out[all.c[0]] = all.c[1];
+    if (kmer_base_out) kmer_base_out[all.c[0]] = all.c[2];
+    for (int q = 0; q < tail; q++) packed_out[all.c[1] + q] = 0;
+}
+
+// ---- the scratch of ix->uni, for the three operators that use it: the unitigs by walking, by list ranking, and an edit round ----
+// The counters at its head: the unitigs' and, behind them, an edit round's (unitigs removed, k-mers removed, candidates kept)
+enum : int {
+    KUNITIG_C_STARTS = 0, KUNITIG_C_CYCLIC = 1, KUNITIG_C_SOLID = 2, KUNITIG_C_CUT = 3, KUNITIG_C_GO = 4,
+    KEDIT_C_REMOVED = 5, KEDIT_C_KMERS = 6, KEDIT_C_KEPT = 7, KUNITIG_CTRS = 8
+};
+// ctr: KUNITIG_C_*; starts / lens: `cap` entries, the chains' starts first and the rings' behind them; sums: the scan's, KIDX_COUNTS a
+// block of 256 starts; bits: a covered bit a slot.  An array the operator does not have is null
+struct KunitigScratch {
+    unsigned long long* ctr;
+    uint64_t* starts;
+    uint32_t* lens;
+    uint64_t* sums;
+    uint32_t* bits;
+    uint64_t cap;
+};
+
+// The plan: where every array lies, in 64-bit words from the scratch's base, decided on the host from keys and slots before anything is
+// counted.  cap = the start list's entries: 2 * keys hold every start -- a stored k-mer has two sides, a chain's start is an end side,
+// and a ring's least member has none --, and the ranked engine's two oriented nodes a key, of which it wants two at least.  The first
+// `zero` words (the counters, the ranked engine's control words) are zeroed before a call, and the walk's covered bits.  The ranked
+// engine's arrays are krank.hpp's: the control words (KUNITIG_PLAN_CTL words of two), the records (two generations of cap, two words
+// each), succ0, slot_of and node_of (32-bit, two a word).  An array a kind does not have: KUNITIG_ABSENT
+enum KunitigKind : int { KUNITIG_KIND_WALK = 0, KUNITIG_KIND_RANK = 1, KUNITIG_KIND_EDIT = 2 };
+constexpr uint64_t KUNITIG_ABSENT = ~0ull, KUNITIG_PLAN_CTL = 96;
+static_assert(KUNITIG_CTRS % 2 == 0 && (KUNITIG_CTRS + KUNITIG_PLAN_CTL) % 2 == 0, "the records are 16-byte aligned, whatever the kind");
+struct KunitigPlan {
+    uint64_t cap, start_blocks, zero, total;
+    uint64_t ctr, ctl, rec, starts, lens, sums, bits, succ0, slot_of, node_of;
+};
+inline KunitigPlan kunitig_plan(uint64_t keys, uint64_t slots, KunitigKind kind) {
+    const bool rank = kind == KUNITIG_KIND_RANK;
+    const uint64_t least = rank ? 2 : 1;
+    KunitigPlan p;
+    p.cap = 2 * keys > least ? 2 * keys : least;
+    p.start_blocks = (p.cap + 255) / 256;
+    uint64_t at = 0;
+    auto take = [&at](bool has, uint64_t words) {
+        const uint64_t off = has ? at : KUNITIG_ABSENT;
+        at += has ? words : 0;
+        return off;
+    };
+    p.ctr = take(true, KUNITIG_CTRS);
+    p.ctl = take(rank, KUNITIG_PLAN_CTL);
+    p.zero = at;
+    p.rec = take(rank, 4 * p.cap);
+    p.starts = take(true, p.cap);
+    p.lens = take(true, (p.cap + 1) / 2);
+    p.sums = take(kind != KUNITIG_KIND_EDIT, p.start_blocks * KIDX_COUNTS);
+    p.bits = take(kind == KUNITIG_KIND_WALK, (slots + 63) / 64);
+    p.succ0 = take(rank, p.cap / 2);
+    p.slot_of = take(rank, (keys + 2) / 2);
+    p.node_of = take(rank, (slots + 1) / 2);
+    p.total = at;
+    return p;
+}
+// the array at word `off` of the scratch at `base`, null when the plan has none
+template <typename T>
+inline T* kunitig_at(uint64_t* base, uint64_t off) { return off == KUNITIG_ABSENT ? nullptr : (T*)(base + off); }
+inline KunitigScratch kunitig_bind(uint64_t* base, const KunitigPlan& p) {
+    return KunitigScratch{kunitig_at<unsigned long long>(base, p.ctr), kunitig_at<uint64_t>(base, p.starts), kunitig_at<uint32_t>(base, p.lens),
+                          kunitig_at<uint64_t>(base, p.sums), kunitig_at<uint32_t>(base, p.bits), p.cap};
+}
 
 // The caller's side of the device engine (kindex_kernels.hip), asynchronous on `stream`: count mode when d_packed_out is null
 int kunitig_device_unitigs(::pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* d_packed_out,

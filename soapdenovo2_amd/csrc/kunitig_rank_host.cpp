@@ -7,8 +7,8 @@
 #include <vector>
 
 #include "../../include/soapdenovo2_amd.h"
-#include "kindex.hpp"
 #include "krank.hpp"
+#include "kunitig_host.hpp"
 
 void pg_set_error(const std::string& s);
 
@@ -18,103 +18,63 @@ namespace {
 template <int NW>
 void krank_host_unitigs(const pg_kindex* ix, const KunitigParams& pr, uint64_t cap_unitigs, uint64_t cap_words, uint64_t* packed_out,
                         uint64_t* word_off_out, uint64_t* kmer_base_out, uint64_t* report, uint64_t* totals) {
-    constexpr int SW = map_slot_words<NW>();
-    const int K = ix->K, R = krank_rounds(ix->ranks[0].keys);
-    const KidxRank& t = ix->ranks[0];
-    const uint64_t* tab = t.tab.data();
-    const uint64_t mask = t.slots - 1, n2 = 2 * t.keys > 2 ? 2 * t.keys : 2;
+    const KunitigHostTable<NW> t(ix);
+    const uint64_t* tab = t.tab;
+    const uint64_t keys = ix->ranks[0].keys, n2 = kunitig_plan(keys, t.slots, KUNITIG_KIND_RANK).cap;
+    const int K = ix->K, tail = ix->nw + 1, R = krank_rounds(keys);
     std::vector<KrankRec> rec((size_t)(2 * n2));
-    std::vector<uint32_t> succ0((size_t)n2), node_of((size_t)t.slots), slot_of((size_t)(t.keys + 1)), ctl(KRANK_CTL, 0u), lens;
+    std::vector<uint32_t> succ0((size_t)n2), node_of((size_t)t.slots), slot_of((size_t)(keys + 1)), ctl_words(KRANK_CTL, 0u), lens;
     std::vector<uint64_t> starts;
+    uint32_t* ctl = ctl_words.data();
     const KrankView v{rec.data(), succ0.data(), node_of.data(), slot_of.data(), n2};
-    auto find = [tab, mask](const Kmer<NW>& ck, uint64_t& slot) { return kunitig_probe<NW>(tab, mask, ck, slot); };
-    auto solid_at = [&](uint64_t e) { return tab[e * SW + NW + 1] != KIDX_EMPTY && kcor_solid_word(tab[e * SW + NW], pr.min_cov); };
     auto append = [&starts](uint64_t start) { starts.push_back(start); };
     // number, sweep
     uint32_t solid = 0;
     for (uint64_t e = 0; e < t.slots; e++)
-        if (solid_at(e)) {
+        if (t.solid_at(e, pr.min_cov)) {
             node_of[(size_t)e] = solid;
             slot_of[solid++] = (uint32_t)e;
         }
     for (uint64_t e = 0; e < t.slots; e++)
-        if (solid_at(e) && krank_sweep<NW>(v, tab + e * SW, e, K, pr, find, append)) ctl[KRANK_GO] = 1;
+        if (t.solid_at(e, pr.min_cov)) krank_sweep_done(ctl, krank_sweep<NW>(v, t.slot(e), e, K, pr, t.find(), append));
     const uint64_t n = 2 * (uint64_t)solid;
     // round j, as krank_jump_kernel runs it
     auto round = [&](int j) {
-        const uint32_t g = ctl[KRANK_GEN + j];
-        if (!ctl[KRANK_GO + j]) { ctl[KRANK_GEN + j + 1] = g; return; }
-        const KrankRec* src = v.rec + (uint64_t)g * n2;
-        KrankRec* dst = v.rec + (uint64_t)(g ^ 1u) * n2;
-        for (uint64_t x = 0; x < n; x++) {
-            bool became;
-            dst[x] = krank_jump(src[x], src, became);
-            if (became) ctl[KRANK_GO + j + 1] = 1;
-        }
-        ctl[KRANK_GEN + j + 1] = g ^ 1u;
+        const KrankPass p = krank_jump_pass(ctl, j);
+        bool any = false;
+        for (uint64_t x = 0; p.go && x < n; x++) krank_jump_item(krank_cur(v, p), krank_other(v, p), x, any);
+        krank_jump_done(p, ctl, j, any, true);
     };
     for (int j = 0; j < R; j++) round(j);
     // the rings: windows, the cut, the rounds again
     uint64_t cyclic = 0;
     {
-        const uint32_t g = ctl[KRANK_GEN + R];
-        KrankRec *fin = v.rec + (uint64_t)g * n2, *spare = v.rec + (uint64_t)(g ^ 1u) * n2;
-        for (uint64_t x = 0; x < n; x++)
-            if (!krank_done(fin[x])) {
-                krank_min_store(spare + x, 0, KrankMin{succ0[(size_t)x], (uint32_t)x});
-                ctl[KRANK_RING] = 1;
-            }
-        for (int r = 0; r < R && ctl[KRANK_RING]; r++)
-            for (uint64_t x = 0; x < n; x++)
-                if (!krank_done(fin[x]))
-                    krank_min_store(spare + x, (r & 1) ^ 1, krank_min_jump<NW>(krank_min_load(spare + x, r & 1), spare, r & 1, tab, v));
-        if (ctl[KRANK_RING]) {
-            for (uint64_t x = 0; x < n; x++) {
-                if (krank_done(fin[x])) continue;
-                const uint32_t best = krank_min_load(spare + x, R & 1).best;
-                fin[x] = krank_ring_cut((uint32_t)x, best, succ0[(size_t)x], [tab, &v](uint32_t y) { return kidx_coverage(krank_slot<NW>(tab, v, y)[NW]); });
-                if (best == (uint32_t)x && krank_fwd(best)) {
-                    starts.push_back(kunitig_start(slot_of[(size_t)(x >> 1)], true, KUNITIG_CYCLE));
-                    cyclic++;
-                }
-            }
-            ctl[KRANK_GO + R] = 1;
-        }
+        const KrankPass p = krank_ring_init_pass(ctl, R);
+        bool any = false;
+        for (uint64_t x = 0; x < n; x++) krank_ring_init_item(krank_cur(v, p), krank_other(v, p), v, x, any);
+        krank_ring_init_done(ctl, any);
+    }
+    for (int r = 0; r < R; r++) {
+        const KrankPass p = krank_ring_pass(ctl, R);
+        for (uint64_t x = 0; p.go && x < n; x++) krank_min_item<NW>(krank_cur(v, p), krank_other(v, p), v, tab, r, x);
+    }
+    if (const KrankPass p = krank_ring_pass(ctl, R); p.go) {
+        for (uint64_t x = 0; x < n; x++) krank_ring_cut_item<NW>(krank_cur(v, p), krank_other(v, p), v, tab, R, x, append, [&cyclic] { cyclic++; });
+        krank_ring_cut_done(ctl, R, true);
     }
     for (int j = R; j < 2 * R; j++) round(j);
-    const uint32_t g = ctl[KRANK_GEN + 2 * R];
-    const KrankRec* fin = v.rec + (uint64_t)g * n2;
-    KrankRec* place = v.rec + (uint64_t)(g ^ 1u) * n2;
+    const KrankPass f = krank_final_pass(ctl, R);
+    const KrankRec* fin = krank_cur(v, f);
+    KrankRec* place = krank_other(v, f);
     // measure, the scan and the decision
-    KidxCounts total{{0, 0, 0, 0}};
-    for (uint64_t s : starts) {
-        lens.push_back(krank_measure<NW>(s, tab, v, fin, K));
-        for (int i = 0; i < KIDX_COUNTS; i++) total.c[i] += kunitig_counts(lens.back(), K).c[i];
-    }
-    const uint64_t unitigs = total.c[0], words = total.c[1], kmers = total.c[2];
-    const uint64_t tail = (uint64_t)ix->nw + 1;
-    const bool overflow = packed_out && (unitigs > cap_unitigs || words + tail > cap_words);
-    totals[KUNITIG_T_UNITIGS] = unitigs;
-    totals[KUNITIG_T_WORDS] = words + tail;
-    totals[KUNITIG_T_BASES] = kmers + unitigs * (uint64_t)(K - 1);
-    totals[KUNITIG_T_COVERED] = kmers;
-    totals[KUNITIG_T_SOLID] = solid;
-    totals[KUNITIG_T_CYCLIC] = cyclic;
-    totals[KUNITIG_T_CUT] = 0;
-    totals[KUNITIG_T_OVERFLOW] = overflow ? 1 : 0;
-    if (!packed_out || overflow) return;
+    for (uint64_t s : starts) lens.push_back(krank_measure<NW>(s, tab, v, fin, K));
+    const KidxCounts all = kunitig_host_sums(lens, K);
+    if (!kunitig_finish(all, K, tail, solid, cyclic, 0, cap_unitigs, cap_words, packed_out != nullptr, totals)) return;
     // zero, place, emit
-    for (uint64_t q = 0; q < words + tail; q++) packed_out[q] = 0;
-    uint64_t u = 0, at = 0, base = 0;
-    for (size_t i = 0; i < starts.size(); i++) {
+    for (uint64_t q = 0; q < all.c[1]; q++) packed_out[q] = 0;
+    kunitig_host_scan(lens, K, tail, packed_out, word_off_out, kmer_base_out, [&](size_t i, uint64_t u, uint64_t at, uint64_t base) {
         krank_place<NW>(starts[i], lens[i], u, at, base, tab, v, fin, place, K, word_off_out, kmer_base_out, report);
-        if (!lens[i]) continue;
-        at += kunitig_row_words(lens[i], K);
-        base += lens[i];
-        u++;
-    }
-    if (word_off_out) word_off_out[u] = at;
-    if (kmer_base_out) kmer_base_out[u] = base;
+    });
     for (uint32_t node = 0; node < solid; node++)
         krank_emit<NW>(node, tab, v, fin, place, K, [packed_out](uint64_t w, uint64_t bits) { packed_out[w] |= bits; });
 }

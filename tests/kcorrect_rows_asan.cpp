@@ -4,40 +4,11 @@
 // one table and one cut over 3 ranks, a ragged and a uniform batch of reads with substitutions -- the batch's first read with one at base
 // 0, its last read with one at its last base -- whose words lie on the heap with exactly NW + 1 words of tail (ones, like every pad
 // bit), packed_out on the heap at exactly n_words.  The cut index's rounds must give the single table's words and reports, in place too.
-// The device engine is not linked: its entry points are stubs that fail (kindex_engine_stubs.hpp, and the one below).
+// The device engine is not linked: its entry points are stubs that fail (kindex_engine_stubs.hpp).
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <set>
-#include <string>
-#include <vector>
-
-#include "kindex_engine_stubs.hpp"
-#include "kcorrect_rows.hpp"
-
-namespace pg {
-int kcor_device_correct_rows(::pg_kindex*, const KidxBatch&, const KcorParams&, uint64_t*, uint64_t*, void*, uint64_t*) { return no_device(); }
-}  // namespace pg
-
-#define CHECK(cond)                                                                             \
-    do {                                                                                        \
-        if (!(cond)) { fprintf(stderr, "line %d: %s failed: %s\n", __LINE__, #cond, pg_last_error()); exit(1); }   \
-    } while (0)
 
 static uint64_t g_rng = 88172645463325252ull;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17; return (uint32_t)(g_rng >> 32); }
-
-// bases packed as pg_pack_read packs them (first base in the most significant bits, 32 a word) into words whose other bits are ones
-static void pack(const std::vector<uint8_t>& b, uint64_t* w) {
-    const size_t nw = (b.size() + 31) / 32;
-    for (size_t q = 0; q < nw; q++) w[q] = ~0ull;
-    for (size_t i = 0; i < b.size(); i++) {
-        const int sh = 62 - 2 * (int)(i % 32);
-        w[i / 32] = (w[i / 32] & ~(3ull << sh)) | (uint64_t)b[i] << sh;
-    }
-}
+#include "khost_program.hpp"
 
 // one batch through both indexes: two buffers and in place, reports and words equal, something fixed, the tail untouched
 static void both(pg_kindex* one, pg_kindex* cutix, int NW, const uint64_t* packed, uint64_t n_words, const uint64_t* word_off, const uint64_t* kmer_base,
@@ -75,7 +46,7 @@ static void flavour(int K) {
     for (auto& b : g) b = (uint8_t)(rnd() & 3);
     // the genome's distinct canonical k-mers as records at coverage 20
     std::vector<uint64_t> gw((G + 31) / 32 + NW + 1, 0);
-    pack(g, gw.data());
+    pack(g, gw.data(), true);
     std::set<std::vector<uint64_t>> seen;
     std::vector<uint64_t> rec;
     pg::map_roll<NW>(gw.data(), 0, G - K + 1, K, [&](const pg::Kmer<NW>& ck, bool, int) {
@@ -120,7 +91,7 @@ static void flavour(int K) {
     kmer_base[n_seqs] = n_kmers;
     n_words += NW + 1;
     uint64_t* packed = new uint64_t[n_words];
-    for (uint64_t r = 0; r < n_seqs; r++) pack(reads[r], packed + word_off[r]);
+    for (uint64_t r = 0; r < n_seqs; r++) pack(reads[r], packed + word_off[r], true);
     for (int q = 0; q < NW + 1; q++) packed[n_words - 1 - q] = ~0ull;
     both(one, cutix, NW, packed, n_words, word_off, kmer_base, n_seqs, 0, n_kmers);
     delete[] packed;
@@ -137,7 +108,7 @@ static void flavour(int K) {
         if (r == 0) rd[0] ^= 2;
         else if (r == m - 1) rd[L - 1] ^= 1;
         else if (r % 3 == 1) rd[rnd() % L] ^= 2;
-        pack(rd, u + r * wpr);
+        pack(rd, u + r * wpr, true);
     }
     both(one, cutix, NW, u, u_words, nullptr, nullptr, m, L, u_kmers);
     delete[] u;

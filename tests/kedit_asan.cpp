@@ -12,116 +12,12 @@
 //   a path read five times over, a copy that differs in eight bases read twice -- arms of K + 7 k-mers -- and a copy with another base
 //   inside that window read once: round 1 pops the inner bubble's weak arm and keeps the outer one's, round 2 pops that, round 3 nothing.
 // A removed k-mer reads 0 through pg_kindex_query and its neighbours on the path as before; then the refusals, with nothing written.
-// The device engine is not linked: its entry points are stubs that fail (kunitig_engine_stubs.hpp, and the round's below).
+// The device engine is not linked: its entry points are stubs that fail (kindex_engine_stubs.hpp).
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <map>
-#include <vector>
-
-#include "kunitig_engine_stubs.hpp"
-#include "kbubble.hpp"
-
-namespace pg {
-template <class Op>
-int kedit_device_round(::pg_kindex*, const typename Op::Params&, uint64_t*, void*) { return no_device(); }
-template int kedit_device_round<KtipOp>(::pg_kindex*, const KtipParams&, uint64_t*, void*);
-template int kedit_device_round<KbubbleOp>(::pg_kindex*, const KbubbleParams&, uint64_t*, void*);
-}  // namespace pg
-
-#define CHECK(cond)                                                                             \
-    do {                                                                                        \
-        if (!(cond)) { fprintf(stderr, "line %d: %s failed: %s\n", __LINE__, #cond, pg_last_error()); exit(1); }   \
-    } while (0)
-
-typedef std::vector<uint8_t> Seq;
 
 static const uint64_t SEED = 88172645463325252ull;     // every operator's designs start from it
 static uint64_t g_rng = SEED;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17; return (uint32_t)(g_rng >> 32); }
-
-static Seq random_seq(size_t n) {
-    Seq s(n);
-    for (auto& b : s) b = (uint8_t)(rnd() & 3);
-    return s;
-}
-static Seq cut(const Seq& s, size_t from, size_t to) { return Seq(s.begin() + from, s.begin() + to); }
-static Seq joined(Seq a, const Seq& b) {
-    a.insert(a.end(), b.begin(), b.end());
-    return a;
-}
-// the packed words of a sequence, pad bits zero, and `extra` zero words behind them
-static std::vector<uint64_t> pack(const Seq& b, size_t extra) {
-    std::vector<uint64_t> w((b.size() + 31) / 32 + extra, 0);
-    for (size_t i = 0; i < b.size(); i++) w[i / 32] |= (uint64_t)b[i] << (62 - 2 * (int)(i % 32));
-    return w;
-}
-
-typedef std::map<std::vector<uint64_t>, uint64_t> Counts;
-
-// every k-mer of the read src counted `passes` times over with its neighbours, as pass 1 counts them
-template <int NW>
-static void count_into(Counts& cnt, const Seq& src, int K, int passes) {
-    const std::vector<uint64_t> w = pack(src, NW + 1);
-    const pg::Kmer<NW> filter = pg::kmer_filter<NW>(K);
-    for (int pass = 0; pass < passes; pass++)
-        for (int j = 0; j + K <= (int)src.size(); j++) {
-            pg::Occurrence occ;
-            const pg::Kmer<NW> ck = pg::canonical_occurrence<NW>(w.data(), j, (int)src.size(), K, filter, occ);
-            const std::vector<uint64_t> key(ck.w, ck.w + NW);
-            auto it = cnt.find(key);
-            if (it == cnt.end()) cnt[key] = pg::node_first(occ.left, occ.right);
-            else it->second = pg::node_update(it->second, occ.left, occ.right);
-        }
-}
-
-template <int NW>
-static std::vector<uint64_t> records(const Counts& cnt) {
-    const int RW = NW + 2;
-    std::vector<uint64_t> all(cnt.size() * RW);
-    uint64_t i = 0;
-    for (const auto& kv : cnt) {
-        memcpy(all.data() + i * RW, kv.first.data(), NW * sizeof(uint64_t));
-        all[i * RW + NW] = kv.second;
-        all[i * RW + NW + 1] = i;
-        i++;
-    }
-    return all;
-}
-
-template <int NW>
-static pg_kindex* build(const Counts& cnt, int K) {
-    const std::vector<uint64_t> all = records<NW>(cnt);
-    pg_kindex* ix = pg_kindex_build(-1, K, NW == 4, all.data(), cnt.size(), nullptr);
-    CHECK(ix);
-    return ix;
-}
-
-// the same records in an index cut over two ranks, which every operator refuses
-template <int NW>
-static pg_kindex* build_cut(const Counts& cnt, int K) {
-    const uint64_t n = cnt.size();
-    const std::vector<uint64_t> all = records<NW>(cnt);
-    const uint64_t* parts[1] = {all.data()};
-    const int devices[2] = {-1, -1}, part_device[1] = {-1};
-    pg_kindex* ix = pg_kindex_build_sharded(devices, 2, K, NW == 4, parts, &n, part_device, 1, nullptr);
-    CHECK(ix);
-    return ix;
-}
-
-// the cnt words of a read's k-mers, into a heap buffer of exactly that many
-template <int NW>
-static std::vector<uint64_t> query(pg_kindex* ix, const Seq& read, int K) {
-    const std::vector<uint64_t> w = pack(read, NW + 1);
-    const uint64_t nk = read.size() - K + 1;
-    uint64_t* out = new uint64_t[nk];
-    CHECK(pg_kindex_query(ix, w.data(), nullptr, nullptr, 1, (uint32_t)read.size(), nk, 0, out, nullptr, nullptr) == PG_OK);
-    std::vector<uint64_t> v(out, out + nk);
-    delete[] out;
-    return v;
-}
+#include "khost_program.hpp"
 
 // one round at thresholds 1, 1 (the bubbles' at max_diff 0) into a heap buffer of exactly the totals
 static void round(bool bubbles, pg_kindex* ix, uint32_t max, uint64_t removed, uint64_t kmers, uint64_t solid, uint64_t kept) {

@@ -5,23 +5,9 @@
 // last sequence -- the reach read_kmer is allowed.  Every answer and summary word of the two indexes must agree, and some k-mers must be
 // present and some absent.  The device engine is not linked: its entry points are stubs that fail (kindex_engine_stubs.hpp).
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <set>
-#include <string>
-#include <vector>
-
-#include "kindex_engine_stubs.hpp"
-
-#define CHECK(cond)                                                                             \
-    do {                                                                                        \
-        if (!(cond)) { fprintf(stderr, "line %d: %s failed: %s\n", __LINE__, #cond, pg_last_error()); exit(1); }   \
-    } while (0)
 
 static uint64_t g_rng = 88172645463325252ull;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17; return (uint32_t)(g_rng >> 32); }
+#include "khost_program.hpp"
 
 // bases [at, at + len) of g packed as pg_pack_read packs them: first base in the most significant bits, 32 a word
 static void pack(const std::vector<uint8_t>& g, size_t at, size_t len, uint64_t* w) {

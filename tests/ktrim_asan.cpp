@@ -6,33 +6,9 @@
 // n_seqs + 1, out_totals 4.  The two indexes must agree word for word, and the output is checked against a base-by-base repack of the
 // spans.  The device engine is not linked: its entry points are stubs that fail (kindex_engine_stubs.hpp).
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <set>
-#include <string>
-#include <vector>
-
-#include "kindex_engine_stubs.hpp"
-
-#define CHECK(cond)                                                                             \
-    do {                                                                                        \
-        if (!(cond)) { fprintf(stderr, "line %d: %s failed: %s\n", __LINE__, #cond, pg_last_error()); exit(1); }   \
-    } while (0)
 
 static uint64_t g_rng = 88172645463325252ull;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17; return (uint32_t)(g_rng >> 32); }
-
-// bases packed as pg_pack_read packs them (first base in the most significant bits, 32 a word) into words whose other bits are `fill`
-static void pack(const std::vector<uint8_t>& b, uint64_t* w, bool ones) {
-    const size_t nw = (b.size() + 31) / 32;
-    for (size_t q = 0; q < nw; q++) w[q] = ones ? ~0ull : 0;
-    for (size_t i = 0; i < b.size(); i++) {
-        const int sh = 62 - 2 * (int)(i % 32);
-        w[i / 32] = (w[i / 32] & ~(3ull << sh)) | (uint64_t)b[i] << sh;
-    }
-}
+#include "khost_program.hpp"
 
 struct Out {
     uint64_t n_seqs, n_words;

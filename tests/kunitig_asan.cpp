@@ -5,73 +5,11 @@
 // packed_out totals[1] words, word_off_out and kmer_base_out totals[0] + 1, out_report 2 totals[0] -- so that a word written past any of
 // them is caught.  The unitigs are checked against the construction: the genome or its reverse complement, the ring once round from its
 // least k-mer, every lone k-mer in its canonical orientation.  Then the capacities one short, each nullable output null, a guard that
-// cuts, and the refusals.  The device engine is not linked: its entry points are stubs that fail (kunitig_engine_stubs.hpp).
+// cuts, and the refusals.  The device engine is not linked: its entry points are stubs that fail (kindex_engine_stubs.hpp).
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <map>
-#include <set>
-#include <vector>
-
-#include "kunitig_engine_stubs.hpp"
-
-#define CHECK(cond)                                                                             \
-    do {                                                                                        \
-        if (!(cond)) { fprintf(stderr, "line %d: %s failed: %s\n", __LINE__, #cond, pg_last_error()); exit(1); }   \
-    } while (0)
-
-typedef std::vector<uint8_t> Seq;
 
 static uint64_t g_rng = 88172645463325252ull;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17; return (uint32_t)(g_rng >> 32); }
-
-static Seq random_seq(size_t n) {
-    Seq s(n);
-    for (auto& b : s) b = (uint8_t)(rnd() & 3);
-    return s;
-}
-static Seq revcomp(const Seq& s) {
-    Seq r(s.rbegin(), s.rend());
-    for (auto& b : r) b ^= 2;
-    return r;
-}
-// the packed words of a sequence, pad bits zero, and `extra` zero words behind them
-static std::vector<uint64_t> pack(const Seq& b, size_t extra) {
-    std::vector<uint64_t> w((b.size() + 31) / 32 + extra, 0);
-    for (size_t i = 0; i < b.size(); i++) w[i / 32] |= (uint64_t)b[i] << (62 - 2 * (int)(i % 32));
-    return w;
-}
-static Seq unpack(const uint64_t* w, size_t n) {
-    Seq s(n);
-    for (size_t i = 0; i < n; i++) s[i] = (uint8_t)(w[i / 32] >> (62 - 2 * (int)(i % 32)) & 3);
-    return s;
-}
-// of a text and its reverse complement, the one whose first K bases are not greater
-static Seq oriented(const Seq& t, size_t K) {
-    const Seq r = revcomp(t);
-    return std::lexicographical_compare(r.begin(), r.begin() + K, t.begin(), t.begin() + K) ? r : t;
-}
-
-typedef std::map<std::vector<uint64_t>, uint64_t> Counts;
-
-// k-mers [j0, j1) of src (len bases) counted `passes` times over with their neighbours, as pass 1 counts them
-template <int NW>
-static void count_into(Counts& cnt, const Seq& src, int j0, int j1, int K, int passes) {
-    const std::vector<uint64_t> w = pack(src, NW + 1);
-    const pg::Kmer<NW> filter = pg::kmer_filter<NW>(K);
-    for (int pass = 0; pass < passes; pass++)
-        for (int j = j0; j < j1; j++) {
-            pg::Occurrence occ;
-            const pg::Kmer<NW> ck = pg::canonical_occurrence<NW>(w.data(), j, (int)src.size(), K, filter, occ);
-            const std::vector<uint64_t> key(ck.w, ck.w + NW);
-            auto it = cnt.find(key);
-            if (it == cnt.end()) cnt[key] = pg::node_first(occ.left, occ.right);
-            else it->second = pg::node_update(it->second, occ.left, occ.right);
-        }
-}
+#include "khost_program.hpp"
 
 struct Result {
     uint64_t totals[8];
@@ -128,7 +66,7 @@ static Result run(pg_kindex* ix, int K, int NW, uint32_t min_cov, uint32_t min_a
 
 template <int NW>
 static void flavour(int K) {
-    const int G = 3000, C = 700, RW = NW + 2, LONE = 5;
+    const int G = 3000, C = 700, LONE = 5;
     const Seq g = random_seq(G), c = random_seq(C);
     Counts cnt;
     count_into<NW>(cnt, g, 0, G - K + 1, K, 2);
@@ -143,21 +81,8 @@ static void flavour(int K) {
     }
     const uint64_t n = cnt.size();
     CHECK(n == (uint64_t)(G - K + 1 + C + LONE));                              // the k-mers are distinct
-    uint64_t* all = new uint64_t[n * RW];
-    uint64_t i = 0;
-    for (const auto& kv : cnt) {
-        memcpy(all + i * RW, kv.first.data(), NW * sizeof(uint64_t));
-        all[i * RW + NW] = kv.second;
-        all[i * RW + NW + 1] = i;
-        i++;
-    }
-    pg_kindex* one = pg_kindex_build(-1, K, NW == 4, all, n, nullptr);
-    const uint64_t* parts[1] = {all};
-    const int devices[2] = {-1, -1}, part_device[1] = {-1};
-    pg_kindex* cutix = pg_kindex_build_sharded(devices, 2, K, NW == 4, parts, &n, part_device, 1, nullptr);
-    pg_kindex* none = pg_kindex_build(-1, K, NW == 4, nullptr, 0, nullptr);
-    CHECK(one && cutix && none);
-    delete[] all;
+    pg_kindex *one = build<NW>(cnt, K), *cutix = build_cut<NW>(cnt, K), *none = pg_kindex_build(-1, K, NW == 4, nullptr, 0, nullptr);
+    CHECK(none);
     // the ring as the rule emits it: from its least canonical k-mer, as that k-mer reads, once round
     Seq ring;
     for (const Seq& strand : {c, revcomp(c)}) {

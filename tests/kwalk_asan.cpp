@@ -4,35 +4,11 @@
 // batch of stretches of the genome whose words lie on the heap with exactly NW + 1 words of tail (ones, like every pad bit), and the two
 // output buffers on the heap at exactly the sizes the header states: 2 n_seqs rows of pg_packed_words(max_ext) words and 4 n_seqs report
 // words.  Every walk is checked base by base against the genome's flanks: the k-mers are distinct, so a walk ends at the genome's end or
-// at max_ext.  The device engine is not linked: its entry points are stubs that fail (kwalk_engine_stubs.hpp).
+// at max_ext.  The device engine is not linked: its entry points are stubs that fail (kindex_engine_stubs.hpp).
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <map>
-#include <vector>
-
-#include "kwalk_engine_stubs.hpp"
-
-#define CHECK(cond)                                                                             \
-    do {                                                                                        \
-        if (!(cond)) { fprintf(stderr, "line %d: %s failed: %s\n", __LINE__, #cond, pg_last_error()); exit(1); }   \
-    } while (0)
 
 static uint64_t g_rng = 88172645463325252ull;
-static uint32_t rnd() { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17; return (uint32_t)(g_rng >> 32); }
-
-// bases packed as pg_pack_read packs them (first base in the most significant bits, 32 a word) into words whose other bits are `fill`
-static void pack(const std::vector<uint8_t>& b, uint64_t* w, bool ones) {
-    const size_t nw = (b.size() + 31) / 32;
-    for (size_t q = 0; q < nw; q++) w[q] = ones ? ~0ull : 0;
-    for (size_t i = 0; i < b.size(); i++) {
-        const int sh = 62 - 2 * (int)(i % 32);
-        w[i / 32] = (w[i / 32] & ~(3ull << sh)) | (uint64_t)b[i] << sh;
-    }
-}
+#include "khost_program.hpp"
 
 // walk v of a sequence that is bases [at, at + len) of g: its row and its report against the genome's flank
 static void check_walk(const std::vector<uint8_t>& g, int K, size_t at, size_t len, bool second, uint32_t max_ext, const uint64_t* row, const uint64_t* rep) {
@@ -53,39 +29,13 @@ static void check_walk(const std::vector<uint8_t>& g, int K, size_t at, size_t l
 
 template <int NW>
 static void flavour(int K) {
-    const int G = 3000, RW = NW + 2;
-    std::vector<uint8_t> g(G);
-    for (auto& b : g) b = (uint8_t)(rnd() & 3);
+    const int G = 3000;
+    const Seq g = random_seq(G);
     // the genome read twice: every canonical k-mer with its neighbours, counted as pass 1 counts them
-    std::vector<uint64_t> gw((G + 31) / 32 + NW + 1, 0);
-    pack(g, gw.data(), false);
-    const pg::Kmer<NW> filter = pg::kmer_filter<NW>(K);
-    std::map<std::vector<uint64_t>, uint64_t> cnt;
-    for (int pass = 0; pass < 2; pass++)
-        for (int j = 0; j + K <= G; j++) {
-            pg::Occurrence occ;
-            const pg::Kmer<NW> ck = pg::canonical_occurrence<NW>(gw.data(), j, G, K, filter, occ);
-            const std::vector<uint64_t> key(ck.w, ck.w + NW);
-            auto it = cnt.find(key);
-            if (it == cnt.end()) cnt[key] = pg::node_first(occ.left, occ.right);
-            else it->second = pg::node_update(it->second, occ.left, occ.right);
-        }
-    const uint64_t n = cnt.size();
-    CHECK(n == (uint64_t)(G - K + 1));                                        // the k-mers are distinct
-    uint64_t* all = new uint64_t[n * RW];
-    uint64_t i = 0;
-    for (const auto& kv : cnt) {
-        memcpy(all + i * RW, kv.first.data(), NW * sizeof(uint64_t));
-        all[i * RW + NW] = kv.second;
-        all[i * RW + NW + 1] = i;
-        i++;
-    }
-    pg_kindex* one = pg_kindex_build(-1, K, NW == 4, all, n, nullptr);
-    const uint64_t* parts[1] = {all};
-    const int devices[2] = {-1, -1}, part_device[1] = {-1};
-    pg_kindex* cutix = pg_kindex_build_sharded(devices, 2, K, NW == 4, parts, &n, part_device, 1, nullptr);
-    CHECK(one && cutix);
-    delete[] all;
+    Counts cnt;
+    count_into<NW>(cnt, g, K, 2);
+    CHECK(cnt.size() == (size_t)(G - K + 1));                                 // the k-mers are distinct
+    pg_kindex *one = build<NW>(cnt, K), *cutix = build_cut<NW>(cnt, K);
     // a ragged batch: stretches of many lengths, some without a k-mer, the last one a multiple of 32 bases that ends one word before the tail
     const int lens[] = {K - 1, K, K + 1, 64, 65, 2 * K + 1, 0, 1000, 33, 97, 4 * K, 32 * 7};
     const uint64_t n_seqs = sizeof lens / sizeof lens[0];

@@ -4,13 +4,11 @@ each also against what its construction dictates: the totals and the word of eve
 refusal, KmerIndex.drop_weak_arcs and KmerIndex.simplify(ops=...), and, with the bulges', under -fsanitize=address,undefined in a
 stand-alone program (tests/kedit_ops_asan.cpp).  tests/test_gpu_karc.py runs the same through the kernels.  All comparisons are of
 integers and exact."""
-import os
-import subprocess
 
 import pytest
 
 import karc_cases as G
-from conftest import ROOT
+from host_program import build_and_run
 
 
 @pytest.mark.parametrize("flavour", G.FLAVOURS, ids=G.flavour_id)
@@ -33,12 +31,4 @@ def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     """tests/kedit_ops_asan.cpp, the arcs' and the bulges' designs in one program over the one host twin: both flavours, two designs an
     operator, each checked against the construction -- compiled with the host twin's sources and -fsanitize=address,undefined, and run.
     Nothing loaded into Python is sanitised."""
-    exe = str(tmp_path / "kedit_ops_asan")
-    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kedit_ops_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           os.path.join(csrc, "kunitig_host.cpp"), os.path.join(csrc, "kedit_ops_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "karc host twin: ok" in ran.stdout and "kbulge host twin: ok" in ran.stdout, ran.stdout + ran.stderr
+    build_and_run(tmp_path, "kedit_ops_asan", ["kindex_host.cpp", "kunitig_host.cpp", "kedit_ops_host.cpp"], ["karc host twin: ok", "kbulge host twin: ok"])

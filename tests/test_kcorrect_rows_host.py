@@ -3,7 +3,6 @@ csrc/kcorrect_rows.hpp with the kernels' own steps, over the rows of the twin's 
 (tests/kcorrect_model.py), the single-table twin (pg_kindex_correct) and itself at other round capacities.
 tests/test_gpu_kcorrect_rows.py runs the same through the kernels.  All comparisons are of integers and exact."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import kcorrect_cases as E
 import kcorrect_model as C
 import kcorrect_rows_cases as R
 from conftest import oracle_records
+from host_program import build_and_run
 from soapdenovo2_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -139,12 +139,4 @@ def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     """tests/kcorrect_rows_asan.cpp: both flavours, 3 ranks, a ragged and a uniform batch on the heap with exactly nw + 1 words of tail,
     packed_out at exactly n_words, a round capacity of 2, checked against the single-table twin -- compiled with the host twin's sources
     and -fsanitize=address,undefined, and run.  Nothing loaded into Python is sanitised."""
-    exe = str(tmp_path / "kcorrect_rows_asan")
-    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kcorrect_rows_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           os.path.join(csrc, "kcorrect_rows_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "kcorrect rows host twin: ok" in ran.stdout, ran.stdout + ran.stderr
+    build_and_run(tmp_path, "kcorrect_rows_asan", ["kindex_host.cpp", "kcorrect_rows_host.cpp"], ["kcorrect rows host twin: ok"])

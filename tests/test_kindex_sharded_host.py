@@ -3,8 +3,6 @@ serial tables, csrc/kindex_host.cpp) against the independent model (tests/kindex
 cases of tests/kindex_cases.py; the cut against its Python statement (tests/kindex_sharded_cases.py: owner); parts; refusals;
 pg_host_kindex_plan against a restatement of its arithmetic; and the twin under -fsanitize=address,undefined in a stand-alone program.
 tests/test_gpu_kindex_sharded.py runs the same cases through the kernels.  All comparisons are of integers and exact."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,7 +10,7 @@ import pytest
 import kindex_cases as E
 import kindex_model as M
 import kindex_sharded_cases as S
-from conftest import ROOT
+from host_program import build_and_run
 from soapdenovo2_amd import api
 
 
@@ -203,12 +201,4 @@ def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     """tests/kindex_sharded_asan.cpp: 3 ranks, 3 parts, both flavours, batches with exactly NW + 1 words of tail on the heap, against the
     index in one table -- compiled with the host twin's sources and -fsanitize=address,undefined, and run.  Nothing loaded into Python
     is sanitised."""
-    exe = str(tmp_path / "kindex_sharded_asan")
-    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kindex_sharded_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "kindex sharded host twin: ok" in ran.stdout, ran.stdout + ran.stderr
+    build_and_run(tmp_path, "kindex_sharded_asan", ["kindex_host.cpp"], ["kindex sharded host twin: ok"])

@@ -3,13 +3,11 @@ csrc/ktip.hpp) against the independent model (tests/ktip_model.py) on the design
 construction dictates: the totals and the word of every key of the original set after every round --, every refusal, KmerIndex.clip_tips,
 and under -fsanitize=address,undefined in a stand-alone program.  tests/test_gpu_ktip.py runs the same through the kernels.  All
 comparisons are of integers and exact."""
-import os
-import subprocess
 
 import pytest
 
 import ktip_cases as G
-from conftest import ROOT
+from host_program import build_and_run
 
 
 @pytest.mark.parametrize("flavour", G.FLAVOURS, ids=G.flavour_id)
@@ -35,12 +33,4 @@ def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     one-k-mer tips and a tip on a tip, clipped by rounds to the fixed point, then three arms of one bubble and a bubble on an arm, popped
     by rounds to theirs, each checked against the construction -- compiled with the host twin's sources and
     -fsanitize=address,undefined, and run.  Nothing loaded into Python is sanitised."""
-    exe = str(tmp_path / "kedit_asan")
-    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kedit_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           os.path.join(csrc, "kunitig_host.cpp"), os.path.join(csrc, "kedit_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "ktip host twin: ok" in ran.stdout and "kbubble host twin: ok" in ran.stdout, ran.stdout + ran.stderr
+    build_and_run(tmp_path, "kedit_asan", ["kindex_host.cpp", "kunitig_host.cpp", "kedit_host.cpp"], ["ktip host twin: ok", "kbubble host twin: ok"])

@@ -2,8 +2,6 @@
 the rule the kernels share in csrc/ktrim.hpp) against the independent model (tests/ktrim_model.py) on the designed cases of
 tests/ktrim_cases.py, on the simulated read set of the corrector's tests counted by the oracle, and under -fsanitize=address,undefined
 in a stand-alone program.  tests/test_gpu_ktrim.py runs the same through the kernels.  All comparisons are of integers and exact."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,7 +9,8 @@ import pytest
 import kcorrect_cases as C
 import kindex_model as M
 import ktrim_cases as E
-from conftest import ROOT, oracle_records
+from conftest import oracle_records
+from host_program import build_and_run
 from soapdenovo2_amd import api
 
 
@@ -118,12 +117,4 @@ def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     """tests/ktrim_asan.cpp: both flavours, one table and 3 ranks, a ragged and a uniform batch with exactly nw + 1 words of tail, every
     output buffer on the heap at exactly the capacity the header states -- compiled with the host twin's sources and
     -fsanitize=address,undefined, and run.  Nothing loaded into Python is sanitised."""
-    exe = str(tmp_path / "ktrim_asan")
-    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "ktrim_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           os.path.join(csrc, "ktrim_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "ktrim host twin: ok" in ran.stdout, ran.stdout + ran.stderr
+    build_and_run(tmp_path, "ktrim_asan", ["kindex_host.cpp", "ktrim_host.cpp"], ["ktrim host twin: ok"])

@@ -3,13 +3,11 @@ csrc/kunitig.hpp) against the independent model (tests/kunitig_model.py) on the 
 against the unitigs its construction dictates --, on tables of random counter words, on a noisy read set, at the capacities' edges, every
 refusal, the api's methods with the round trip into the query and the walk, and under -fsanitize=address,undefined in a stand-alone
 program.  tests/test_gpu_kunitig.py runs the same through the kernels.  All comparisons are of integers and exact."""
-import os
-import subprocess
 
 import pytest
 
 import kunitig_cases as G
-from conftest import ROOT
+from host_program import build_and_run
 
 
 @pytest.mark.parametrize("flavour", G.FLAVOURS, ids=G.flavour_id)
@@ -61,12 +59,4 @@ def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     """tests/kunitig_asan.cpp: both flavours, a linear genome, a ring and isolated k-mers in one index, the output buffers on the heap at
     exactly the sizes the count call states -- compiled with the host twin's sources and -fsanitize=address,undefined, and run.  Nothing
     loaded into Python is sanitised."""
-    exe = str(tmp_path / "kunitig_asan")
-    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kunitig_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           os.path.join(csrc, "kunitig_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "kunitig host twin: ok" in ran.stdout, ran.stdout + ran.stderr
+    build_and_run(tmp_path, "kunitig_asan", ["kindex_host.cpp", "kunitig_host.cpp"], ["kunitig host twin: ok"])

@@ -3,13 +3,11 @@ csrc/krank.hpp that the kernels run, one after the other) on a device = -1 index
 at its default guard and against what each construction dictates (tests/kunitig_ranked_cases.py), and under
 -fsanitize=address,undefined in a stand-alone program.  tests/test_gpu_kunitig_ranked.py runs the same through the kernels.  All
 comparisons are of integers and exact."""
-import os
-import subprocess
 
 import pytest
 
 import kunitig_ranked_cases as R
-from conftest import ROOT
+from host_program import build_and_run
 
 
 @pytest.mark.parametrize("flavour", R.FLAVOURS, ids=R.flavour_id)
@@ -93,12 +91,4 @@ def test_walk_rank_edit_round_rank_on_one_index():
 def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     """tests/kunitig_ranked_asan.cpp: both flavours, a chain, a ring and isolated k-mers in one index, heap outputs at exactly the counted
     sizes -- compiled with the host twin's sources and -fsanitize=address,undefined, and run.  Nothing loaded into Python is sanitised."""
-    exe = str(tmp_path / "kunitig_ranked_asan")
-    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kunitig_ranked_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           os.path.join(csrc, "kunitig_rank_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "kunitig ranked host twin: ok" in ran.stdout, ran.stdout + ran.stderr
+    build_and_run(tmp_path, "kunitig_ranked_asan", ["kindex_host.cpp", "kunitig_rank_host.cpp"], ["kunitig ranked host twin: ok"])

@@ -3,15 +3,13 @@ csrc/kwalk.hpp) against the independent model (tests/kwalk_model.py) on the desi
 the text its construction dictates --, on tables of random counter words, at the batch sizes of the kernel's wave and workgroup edges,
 every refusal, api.extend_seqs, and under -fsanitize=address,undefined in a stand-alone program.  tests/test_gpu_kwalk.py runs the same
 through the kernel.  All comparisons are of integers and exact."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import kwalk_cases as E
 import kwalk_model as W
-from conftest import ROOT
+from host_program import build_and_run
 from soapdenovo2_amd import api
 
 
@@ -65,12 +63,4 @@ def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     """tests/kwalk_asan.cpp: both flavours, a ragged and a uniform batch with exactly nw + 1 words of tail, the output buffers on the heap
     at exactly the stated sizes -- compiled with the host twin's sources and -fsanitize=address,undefined, and run.  Nothing loaded into
     Python is sanitised."""
-    exe = str(tmp_path / "kwalk_asan")
-    csrc = os.path.join(ROOT, "soapdenovo2_amd", "csrc")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
-           "-I/opt/rocm/include", "-I" + csrc, os.path.join(ROOT, "tests", "kwalk_asan.cpp"), os.path.join(csrc, "kindex_host.cpp"),
-           os.path.join(csrc, "kwalk_host.cpp"), "-o", exe]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
-    ran = subprocess.run([exe], capture_output=True, text=True)
-    assert ran.returncode == 0 and "kwalk host twin: ok" in ran.stdout, ran.stdout + ran.stderr
+    build_and_run(tmp_path, "kwalk_asan", ["kindex_host.cpp", "kwalk_host.cpp"], ["kwalk host twin: ok"])
