@@ -853,6 +853,11 @@ int pg_device_emu_layout_growable(int device, const uint64_t *records, uint64_t 
                                   int n_sets, uint64_t *out_set_size, uint64_t *out_rounds, uint64_t *out_nodes,
                                   uint64_t nodes_cap_slots);
 int pg_device_emu_home_slots(int device, const uint64_t *keys, uint64_t n, int mer127, uint64_t size, uint64_t *out);
+/* pg_host_emu_clip_tips with the device stage on the HipBackend: the layout is replayed on the host, the sets are uploaded, the tips are
+ * decided as a run decides them (p2_clip_tips: clip_tips<HipBackend, NW>), and the node words are downloaded and compared with the
+ * sequential scan's.  The same eight numbers. */
+int pg_device_emu_clip_tips(int device, const uint64_t *records, uint64_t n_records, const uint64_t *set_last_put, int K, int mer127,
+                            int n_sets, int cut_single, int a_gb, uint64_t out[8]);
 /* The backend's append primitive (csrc/backend_hip.hpp: be_append_kernel, which has no host twin) with f(i) = flags[i] ?
  * PG_EMU_APPEND_BASE + i : ~0 over i in [0, n) and room for `cap` entries: list_out[0 .. cap) = what the kernel left in the list,
  * which was all ones before (entries in any order; everything behind min(cap, hits) stays all ones), *count_out = the counter

@@ -175,6 +175,7 @@ def lib() -> C.CDLL:
     L.pg_device_emu_layout_growable.argtypes = [C.c_int, u64p, C.c_uint64, u64p, C.c_int, C.c_int, u64p, u64p, u64p, C.c_uint64]
     L.pg_device_emu_home_slots.argtypes = [C.c_int, u64p, C.c_uint64, C.c_int, C.c_uint64, u64p]
     L.pg_device_emu_append.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, u64p, u64p]
+    L.pg_device_emu_clip_tips.argtypes = [C.c_int, u64p, C.c_uint64, u64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u64p]
     # the k-mer index (include/soapdenovo2_amd.h, section 3)
     L.pg_kindex_build.restype = C.c_void_p
     L.pg_kindex_build.argtypes = [C.c_int, C.c_int, C.c_int, u64p, C.c_uint64, C.c_void_p]
@@ -230,7 +231,7 @@ EXPORTED_SYMBOLS = [
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
     "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times", "pg_kindex_correct_rows", "pg_kindex_correct_rows_stats",
     "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_unitigs_ranked", "pg_kindex_clip_tips", "pg_kindex_pop_bubbles", "pg_kindex_drop_weak_arcs", "pg_kindex_pop_bulges",
-    "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append",
+    "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append", "pg_device_emu_clip_tips",
 ]
 
 

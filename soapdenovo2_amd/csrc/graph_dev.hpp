@@ -80,6 +80,10 @@ int p2_tip_walks(P2Device* d, int cut_len, bool thin, std::vector<P2TipWalk>& ou
 // removeSingleTips / removeMinorTips decided on the device (dev_tips.hpp); the counts the reference prints
 struct P2TipTotals { unsigned long long single = 0, minor = 0; int cycles = 0, rounds = 0; std::vector<unsigned long long> per_cycle; };
 int p2_clip_tips(P2Device* d, bool cut_single, P2TipTotals& out);
+// test hook pg_device_emu_clip_tips: the sets replayed from host records (host_graph.cpp), every set's slot array as p2_open takes it --
+// `before` the tips, and `after` the sequential scan with the tips it removed
+struct EmuTipSets { std::vector<std::vector<uint64_t>> before, after; std::vector<uint64_t> size; unsigned long long single = 0, minor = 0; };
+int emu_tip_sets(const uint64_t* records, uint64_t n, const uint64_t* set_last_put, int K, int nw, int P, int cut_single, int a_gb, EmuTipSets& out);
 // the vertices -- live non-linear nodes -- in slot order, nw key words each (what output_vertex prints)
 int p2_list_vertices(P2Device* d, std::vector<uint64_t>& keys);
 int p2_mirror_nodes(P2Device* d, const uint64_t* slots, const uint64_t* ab, uint64_t n);

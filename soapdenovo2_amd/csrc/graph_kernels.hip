@@ -871,6 +871,7 @@ __global__ __launch_bounds__(256) void eb_apply_seg(P2Params p, EbWay way, const
     if (lo >= n_rec || sorted_key[lo] != own) return;
     const EdgeRec& r = recs[order[lo]];
     const uint32_t id = (uint32_t)id_before[lo] + 1, bal = (r.flags >> 6) & 1;
+    if (!bal) return;                                                   // a walk that is its own twin passed this waypoint both ways: eb_apply does all of it
     const uint64_t h = t >> 1;
     const int d = (int)(t & 1);
     const unsigned int vi = way.vis_info[t];
@@ -931,7 +932,28 @@ __global__ __launch_bounds__(256) void eb_apply(P2Params p, const EdgeRec* recs,
     uint64_t* node;
     bool smaller;
     bool handed_over = false;                                       // the rest of the walk belongs to the lanes of eb_apply_seg
-    for (uint32_t b = 0; b < r.length; b++) {
+    if (!bal) {
+        // A walk that is its own twin passes every interior node twice, there and back, and the way out of a node met against its canonical
+        // k-mer is read from word A -- which the tag replaces.  So: the bases first, node by node and past every waypoint, with nothing written;
+        // then the tags over the first half of the walk, which is every interior node once (both passes would write the same: id, twin 1).
+        for (uint32_t b = 0; b < r.length; b++) {
+            if (!sv_step<NW>(sv, cur, slot, node, smaller)) { atomicAdd(errors, 1ULL); return; }
+            seq[b] = "ACTG"[kmer_last<NW>(cur)];
+            if (b + 1 == r.length) break;
+            cur = kmer_next<NW>(cur, linear_out_ab(node[NW], smaller), filter);
+        }
+        if (slot != r.far_slot) { atomicAdd(errors, 1ULL); return; }
+        cur = kmer_next<NW>(first, next_ch, filter);
+        for (uint32_t b = 0; 2 * (b + 1) < r.length; b++) {
+            uint64_t at;
+            if (!sv_step<NW>(sv, cur, at, node, smaller)) { atomicAdd(errors, 1ULL); return; }
+            ab = node[NW];
+            const uint32_t B = ((uint32_t)(ab >> 32) & 0x0FFFFFFFu) | (1u << B_TWIN_SHIFT) | (1u << B_INEDGE_SHIFT);
+            node[NW] = (uint64_t)id | ((uint64_t)B << 32);
+            cur = kmer_next<NW>(cur, linear_out_ab(ab, smaller), filter);
+        }
+    }
+    for (uint32_t b = 0; bal && b < r.length; b++) {
         if (!sv_step<NW>(sv, cur, slot, node, smaller)) { atomicAdd(errors, 1ULL); return; }
         ab = node[NW];
         seq[b] = "ACTG"[kmer_last<NW>(cur)];
@@ -2985,6 +3007,41 @@ extern "C" int pg_device_emu_append(int device, const unsigned char* flags, uint
     (void)pg::arena_free(d_list);
     (void)pg::arena_free(d_flags);
     return rc;
+}
+
+// pg_host_emu_clip_tips on the HipBackend: the layout is replayed on the host (host_graph.cpp: emu_tip_sets), the sets go up as a run without a
+// device layout uploads them (p2_open), the tips are decided by p2_clip_tips -- the product's call of clip_tips<HipBackend, NW> -- and the node
+// words come down to be held against the sequential scan's.  out[] as the host hook's.
+extern "C" int pg_device_emu_clip_tips(int device, const uint64_t* records, uint64_t n_records, const uint64_t* set_last_put, int K, int mer127, int n_sets,
+                                       int cut_single, int a_gb, uint64_t out[8]) {
+    if ((!records && n_records) || !out || n_sets < 1 || n_sets > P2_MAX_SETS) { pg_set_error("pg_device_emu_clip_tips: bad argument"); return PG_EINVAL; }
+    int rc = emu_device(device, "pg_device_emu_clip_tips");
+    if (rc) return rc;
+    pg::ArenaPin pin(device);                                          // (one life of the arena for the call's blocks, not one for every block)
+    const int nw = mer127 ? 4 : 2;
+    EmuTipSets hs;
+    if ((rc = emu_tip_sets(records, n_records, set_last_put, K, nw, n_sets, cut_single, a_gb, hs)) != PG_OK) return rc;
+    P2Sets sets;
+    for (int s = 0; s < n_sets; s++) { sets.nodes[s] = hs.before[s].data(); sets.size[s] = hs.size[s]; }
+    P2Device* d = p2_open(device, K, nw, n_sets, sets, 1);
+    if (!d) return PG_ENODEV;
+    P2TipTotals tot;
+    rc = p2_clip_tips(d, cut_single != 0, tot);
+    uint64_t diff = 0;
+    std::vector<uint64_t> got;
+    for (int s = 0; s < n_sets && rc == PG_OK; s++) {
+        got.assign(hs.after[s].size(), 0);
+        if (hs.size[s] && (rc = p2_download_set(d, s, got.data())) != PG_OK) break;
+        for (uint64_t i = 0; i < hs.size[s]; i++) {
+            const uint64_t at = i * (uint64_t)(nw + 1);
+            if (hs.before[s][at] != P2_EMPTY) diff += got[at + nw] != hs.after[s][at + nw];      // A | B << 32 of an occupied slot
+        }
+    }
+    p2_destroy(d);
+    if (rc) return rc;
+    out[0] = hs.single; out[1] = hs.minor; out[2] = tot.single; out[3] = tot.minor;
+    out[4] = diff; out[5] = (uint64_t)tot.rounds; out[6] = (uint64_t)tot.cycles; out[7] = 0;
+    return PG_OK;
 }
 
 }  // namespace pg

@@ -1117,8 +1117,13 @@ struct ParallelEdgeBuilder {
                 const uintptr_t v = c.inner[cd.inner_off + i];
                 HNode<NW>& n = *(HNode<NW>*)(v & ~(uintptr_t)1);
                 const bool smaller = v & 1;
-                if ((n.B >> B_INEDGE_SHIFT) & 3) return false;               // a linear node can sit on one chain only
                 const uint32_t twin = smaller ? (uint32_t)(bal + 1) : (uint32_t)(1 - bal);
+                // a linear node can sit on one chain only -- which passes it twice, there and back, when the chain is its own reverse
+                // complement (bal 0: a hairpin between one arc of a branch node and itself); both passes write the same tag
+                if ((n.B >> B_INEDGE_SHIFT) & 3) {
+                    if (bal == 0 && n.A == (uint32_t)id && ((n.B >> B_TWIN_SHIFT) & 3) == twin) continue;
+                    return false;
+                }
                 n.A = smaller ? (uint32_t)id : (uint32_t)(id + bal);          // edge id replaces word A
                 n.B = (n.B & 0x0FFFFFFFu) | (twin << B_TWIN_SHIFT) | (1u << B_INEDGE_SHIFT);
             }
@@ -2807,6 +2812,36 @@ extern "C" int pg_host_emu_clip_tips(const uint64_t* records, uint64_t n_records
     if (n_sets < 1 || n_sets > 255) { pg_set_error("n_sets must be 1..255"); return PG_EINVAL; }
     return mer127 ? emu_clip_tips<4>(records, n_records, set_last_put, K, n_sets, cut_single, a_gb, n_threads, out)
                   : emu_clip_tips<2>(records, n_records, set_last_put, K, n_sets, cut_single, a_gb, n_threads, out);
+}
+
+// The host half of pg_device_emu_clip_tips (graph_kernels.hip): the same two copies of the replayed layout -- `before` is what goes up to
+// the device, `after` is what the sequential scan left.
+template <int NW>
+static int emu_tip_sets_nw(const uint64_t* records, uint64_t n, const uint64_t* set_last_put, int K, int P, int cut_single, int a_gb, pg::EmuTipSets& out) {
+    using namespace pg;
+    static_assert(sizeof(HNode<NW>) == (NW + 1) * sizeof(uint64_t), "a slot is NW key words and the counter word");
+    Graph<NW> g;
+    out.before.assign((size_t)P, {}); out.after.assign((size_t)P, {}); out.size.assign((size_t)P, 0);
+    for (int pass = 0; pass < 2; pass++) {
+        const int rc = replay_layout<NW>(g, records, n, set_last_put, K, P, a_gb, 1);
+        if (rc) return rc;
+        if (pass == 1) {
+            if (cut_single) g.remove_single_tips();
+            g.remove_minor_tips();
+            if (g.tip_error) return g.tip_error;
+            out.single = (unsigned long long)g.last_single; out.minor = (unsigned long long)g.last_minor;
+        }
+        for (int s = 0; s < P; s++) {
+            const uint64_t* w = (const uint64_t*)g.sets[s].array.data();
+            out.size[s] = g.sets[s].size;
+            (pass ? out.after : out.before)[s].assign(w, w + g.sets[s].size * (uint64_t)(NW + 1));
+        }
+    }
+    return PG_OK;
+}
+int pg::emu_tip_sets(const uint64_t* records, uint64_t n, const uint64_t* set_last_put, int K, int nw, int P, int cut_single, int a_gb, EmuTipSets& out) {
+    return nw == 4 ? emu_tip_sets_nw<4>(records, n, set_last_put, K, P, cut_single, a_gb, out)
+                   : emu_tip_sets_nw<2>(records, n, set_last_put, K, P, cut_single, a_gb, out);
 }
 
 // Test hook: the layout of growable sets as the device computes it (dev_rehash.hpp on the HostBackend) -- per record its slot,
