@@ -118,6 +118,31 @@ PG_HD uint64_t sv_find(const SetsView& v, const Kmer<NW>& key, uint64_t*& node) 
     return ~0ULL;
 }
 
+// The node word (A | B << 32) of a canonical key, ~0 when the key is absent (no node has every flag of word B set): what pass 2 asks of the sets, once per
+// k-mer of every read.  Not sv_find: the CRC is sliced by four (crc4[4 * 256]), `geo` and `crc4` may lie in LDS, and all NW + 1 words of a slot are loaded at
+// once -- one random 24 / 40-byte probe in flight a lane.  Bounded by the set's size like sv_find: an image without an empty slot ends a probe, it hangs no GPU.
+template <int NW, typename Geo, typename Table4>
+PG_HD uint64_t sv_node_word(const Geo& geo, const Table4& crc4, uint32_t P, uint32_t bias, const Kmer<NW>& key) {
+    const uint32_t s = set_of_crc(kmer_crc32_sliced<NW>(key, crc4), P, bias);
+    const uint64_t size = geo[SV_GEO * s + 1];
+    const uint64_t* base = (const uint64_t*)(uintptr_t)geo[SV_GEO * s + 2];
+    uint64_t hc = home_slot<NW>(key, ModConst{size, geo[SV_GEO * s + 3], (uint32_t)geo[SV_GEO * s + 4]});
+    uint64_t ab = ~0ULL;
+    for (uint64_t step = 0; step < size; step++) {
+        const uint64_t* nd = base + hc * (NW + 1);
+        uint64_t d[NW + 1];
+#pragma unroll
+        for (int i = 0; i <= NW; i++) d[i] = sv_word(nd + i);
+        if (d[0] == SV_EMPTY) break;
+        bool eq = true;
+#pragma unroll
+        for (int i = 0; i < NW; i++) eq = eq && d[i] == key.w[i];
+        if (eq) { ab = d[NW]; break; }
+        if (++hc == size) hc = 0;
+    }
+    return ab;
+}
+
 // one step of a walk: the node of the walk-oriented k-mer `word`
 template <int NW>
 PG_HD bool sv_step(const SetsView& v, const Kmer<NW>& word, uint64_t& slot, uint64_t*& node, bool& smaller) {

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "kmer.hpp"
+#include "p2_walk.hpp"
 #include "env.hpp"
 #include "host_graph.hpp"
 #include "graph_dev.hpp"
@@ -1577,22 +1578,29 @@ struct ReadThreader {
     Graph<NW>& g;
     explicit ReadThreader(Graph<NW>& g_) : g(g_) {}
 
-    struct Item { uint32_t id; bool kplus; bool smaller; Kmer<NW> plus; };
     struct Probe { Kmer<NW> key; uint64_t home; int set; bool smaller; };
     std::vector<Probe> probes;
+
+    // what p2_walk_step sends out: (K+1)-mers to the patch map, pairs to `out`, the items to `ids` (for recordPathBin)
+    struct Sink {
+        Graph<NW>& g;
+        std::vector<std::pair<uint32_t, uint32_t>>& out;
+        std::vector<uint32_t>& ids;
+        uint32_t kplus(const Kmer<NW>& plus, bool smaller) const {
+            auto f = g.patch.find(plus);
+            return f == g.patch.end() ? 0u : (smaller ? f->second.id : f->second.id + f->second.twin - 1);
+        }
+        void pair(uint32_t from, uint32_t to, int) const { out.emplace_back(from, to); }
+        void item(int i, uint32_t id) const { if ((size_t)i >= ids.size()) ids.resize((size_t)i + 1); ids[i] = id; }
+    };
 
     // appends the read's pairs (from, to) to `out`; returns false when the read yielded no usable item at all
     // (the reference's "read(s) deleted" counter, prlRead2path.c:722-725)
     // With `path` set (-R, prlRead2path.c:478-543 recordPathBin) the read's edge walk is also appended to *path as
     // <count:u8><count x u32 edge id> and every id on it to *marks, when its first three entries are resolved.
-    bool thread_read(const uint8_t* codes, int len, std::vector<Item>& items, std::vector<std::pair<uint32_t, uint32_t>>& out,
+    bool thread_read(const uint8_t* codes, int len, std::vector<uint32_t>& ids, std::vector<std::pair<uint32_t, uint32_t>>& out,
                      std::vector<uint8_t>* path = nullptr, std::vector<uint32_t>* marks = nullptr) {
         const int K = g.K;
-        items.clear();
-        unsigned retain = 0;
-        bool is_prev = false;
-        Kmer<NW> prev_k;
-        for (int i = 0; i < NW; i++) prev_k.w[i] = 0;
         // stage 1: every canonical k-mer of the read, its set and home slot; the slots are prefetched so that the
         // probes of stage 2 overlap their cache misses (chopKmer4read + searchKmer, prlRead2path.c:159-330)
         const int nk = len - K + 1;
@@ -1616,64 +1624,30 @@ struct ReadThreader {
                 g.sets[pr.set].prefetch(pr.home);
             }
         }
-        for (int j = 0; j < nk; j++) {
+        // stage 2: parse1read over the nodes (p2_walk.hpp)
+        P2Walk<NW> w;
+        Sink sink{g, out, ids};
+        for (int j = 0; j < nk && !w.stop; j++) {
             const Probe& pr = probes[j];
-            const bool smaller = pr.smaller;
             const HNode<NW>* node = g.sets[pr.set].find_from(pr.key, pr.home);
             if (!node) { fprintf(stderr, "SearchKmer: kmer is not found.\n"); exit(1); }
-            const uint32_t B = node->B;
-            const bool linear = B & B_LINEAR, in_edge = (B >> B_INEDGE_SHIFT) & 3;
-            if ((B & B_DELETED) || (linear && !in_edge)) {
-                if (retain < 2) { retain = 0; items.clear(); continue; }      // is_prev / prev_k keep their stale values
-                break;
-            }
-            if (linear) {
-                const uint32_t twin = (B >> B_TWIN_SHIFT) & 3;
-                const uint32_t e = smaller ? node->A : node->A + twin - 1;
-                if (retain == 0 || is_prev) { retain++; items.push_back(Item{e, false, false, Kmer<NW>()}); is_prev = false; }
-                else if (e != items.back().id) { retain++; items.push_back(Item{e, false, false, Kmer<NW>()}); }
-            } else {
-                const Kmer<NW> cur = smaller ? pr.key : kmer_rc<NW>(pr.key, K);   // the node's k-mer in read orientation (prlRead2path.c:680-687)
-                if (is_prev) {
-                    retain++;
-                    const Kmer<NW> plus = kmer_plus<NW>(prev_k, kmer_last<NW>(cur));
-                    const Kmer<NW> bal_plus = rc_plus<NW>(plus, K);
-                    Item it;
-                    it.kplus = true;
-                    it.smaller = kmer_less<NW>(plus, bal_plus);
-                    it.plus = it.smaller ? plus : bal_plus;
-                    it.id = 0;
-                    items.push_back(it);
-                }
-                is_prev = true;
-                prev_k = cur;
-            }
+            p2_walk_step<NW>(w, pr.key, pr.smaller, (uint64_t)node->A | (uint64_t)node->B << 32, K, sink);
         }
-        if (retain < 2) return retain >= 1;
-        for (Item& it : items) {
-            if (!it.kplus) continue;
-            auto f = g.patch.find(it.plus);
-            it.id = f == g.patch.end() ? 0u : (it.smaller ? f->second.id : f->second.id + f->second.twin - 1);
-        }
-        for (size_t i = 0; i + 1 < items.size(); i++) {
-            if (items[i].id == 0 || items[i + 1].id == 0) break;
-            out.emplace_back(items[i].id, items[i + 1].id);
-        }
-        if (path && items.size() >= 3 && items[0].id && items[1].id && items[2].id) {
+        const P2WalkEnd end = p2_walk_end<NW>(w);
+        if (path && end.walk) {
             // the reference counts with an unsigned char that also indexes its staging buffer, so a walk longer than
             // 255 entries wraps around and overwrites the front (prlRead2path.c:481, 529)
             uint32_t buf[256];
             uint8_t counter = 0;
-            for (const Item& it : items) {
-                if (it.id == 0) break;
-                buf[counter++] = it.id;
-                marks->push_back(it.id);
+            for (int i = 0; i < end.walk; i++) {
+                buf[counter++] = ids[i];
+                marks->push_back(ids[i]);
             }
             path->push_back(counter);
             const uint8_t* b = reinterpret_cast<const uint8_t*>(buf);
             path->insert(path->end(), b, b + 4 * (size_t)counter);
         }
-        return true;
+        return !end.deleted;
     }
 };
 
@@ -1744,7 +1718,7 @@ struct GraphHandle : GraphHandleBase {
     double t_thread = 0, t_fold = 0;
     struct Scratch {
         std::unique_ptr<ReadThreader<NW>> rt;
-        std::vector<typename ReadThreader<NW>::Item> items;
+        std::vector<uint32_t> items;
         std::vector<std::pair<uint32_t, uint32_t>> pairs, sorted;
         std::vector<uint32_t> marks;
         std::vector<uint8_t> unpacked, path;

@@ -29,6 +29,13 @@ def test_prearc_matches_reference(golden, tmp_path, name):
         assert na > 0 or D > 0                                             # (-d leaves an error-free 40 kb genome as a single chain)
 
 
+def test_parse1read_step_against_a_two_phase_model(tmp_path):
+    """csrc/p2_walk.hpp, the state machine the device kernels and the host twin share, in a stand-alone program under the sanitizers
+    (tests/p2_walk_asan.cpp): designed node sequences and random ones against a model in the reference's own shape."""
+    from host_program import build_and_run
+    build_and_run(tmp_path, "p2_walk_asan", [], ["designed cases ok", "p2_walk ok"])
+
+
 def test_prearc_on_reader_corner_cases(golden, tmp_path):
     """Ragged reads, truncated reads, mate files: pass 2 sees exactly the reads pass 1 saw."""
     from soapdenovo2_amd import synth
