@@ -172,9 +172,10 @@ __device__ __forceinline__ uint32_t fastdiv1(uint32_t i, uint32_t d, uint32_t in
 // instructions per read, profiles/r01_pmc_sq_bench20M_engine2.json; this form measures 1.65x faster,
 // profiles/r02_k1k2_rewrite_ab.json.)
 //   load  the tile's reads as dword strings (hi dword of every 64-bit word first)
-//   A     thread = (read, 16 positions): m-mer values from two dwords, compile-time funnel shifts
-//   B     thread = (read, S k-mers): window minima with w + S reads (suffix / core / prefix), partition ids, run-start bits; one LDS
-//         atomic reserves the segment's places in the tile's item list, every start bit becomes an item (read, first k-mer | partition id)
+//   A     thread = (read, 16 positions): m-mer values from two dwords, compile-time funnel shifts (the reverse complements too: two rc_dword a chunk)
+//   B     thread = (read, S k-mers): window minima with w + S reads (suffix / core / prefix), partition ids, run-start bits; a prefix sum over
+//         the wave and one LDS atomic a wave reserve the segments' places in the tile's item list, every start bit becomes an item
+//         (read, first k-mer | partition id)
 //   E     one lane per item: the run ends at the read's next start bit; slot in the partition's stream (or the owner's send region),
 //         record from the dword string
 // A read's row holds its dword string, its m-mer values and its start bits; the partition ids of its k-mers stay in phase B's registers
@@ -191,6 +192,7 @@ struct SegArg { int R, np, npad, wsd, nseg, nca, icap; uint32_t inv_R, inv_wpr; 
 
 // W: the window length (m-mers a k-mer) at compile time, with 16-mers (0: whatever the geometry says) -- the loops of phase B
 // unroll into loads with immediate offsets, phase A loses its shifts by 32 - 2m.
+__device__ __forceinline__ unsigned int wave_inclusive_sum(unsigned int x);
 template <int NW, bool ROUTE, int S, int W = 0, bool RAGGED = false>
 #if defined(PG_MEASURE) && defined(PG_K1_WAVES)
 __attribute__((amdgpu_waves_per_eu(PG_K1_WAVES, PG_K1_WAVES)))          // (the A/B of the register budget: make MEASURE=1 XDEF=PG_K1_WAVES=8)
@@ -260,22 +262,36 @@ __global__ __launch_bounds__(BLOCK) void skm_scatter_seg_kernel(ReadsArg a, E2De
     for (;;) {
         const bool whole = turn_seg < 0;
         const int ntask = whole ? R * nseg : min(gsz, nr - turn_r);
-        for (int t = threadIdx.x; t < ntask; t += BLOCK) {
-            int seg, r;
-            if (whole) { seg = (int)fastdiv1(t, R, sa.inv_R); r = t - seg * R; }
-            else { seg = turn_seg; r = turn_r + t; }
-            if (r >= nr) continue;
+        // Every lane of a wave goes round this loop as often as the others (idle ones with no start bits): the places in the item list are handed out
+        // by a prefix sum of the lanes' start-bit counts over the WHOLE wave and one atomic a wave on its total.  (A per-lane count added to the one
+        // counter, as it was, the compiler turns into a serial loop over the wave's active lanes, nine instructions a lane: 3.2 ms of K1's 48 at
+        // 150 bp, K = 63, profiles/k1_valu_diet_ab.json.)
+        for (int tb = 0; tb < ntask; tb += BLOCK) {
+            const int t = tb + (int)threadIdx.x;
+            int seg = 0, r = nr;
+            if (t < ntask) {
+                if (whole) { seg = (int)fastdiv1(t, R, sa.inv_R); r = t - seg * R; }
+                else { seg = turn_seg; r = turn_r + t; }
+            }
             const int j0 = seg * S;
-            const int kpr_r = RAGGED ? rlen[r] - e.g.K + 1 : kpr, np_r = RAGGED ? rlen[r] - m + 1 : np;
-            const int cnt = min(S, kpr_r - j0);
-            if (RAGGED && cnt <= 0) { smask[r * mpad + seg] = 0; continue; }       // behind the read's last k-mer
             uint32_t pid[S];
-            const uint32_t mk = tile_segment<S, W>(v0 + r * npad, np_r, j0, cnt, w, e.g.nmax, e.g.part_mul, pid);
-            smask[r * mpad + seg] = mk;
-            if (mk) {
-                const unsigned int n = (unsigned int)__popc(mk), at = atomicAdd(&n_items, n);
-                if (at + n > (unsigned int)icap) overflow = 1;    // (turn 0 only) nothing is stored, the list is forgotten below
-                else tile_put_items<S>(mk, pid, r, j0, at, ikey, ipid);
+            uint32_t mk = 0;
+            if (r < nr) {
+                const int kpr_r = RAGGED ? rlen[r] - e.g.K + 1 : kpr, np_r = RAGGED ? rlen[r] - m + 1 : np;
+                const int cnt = min(S, kpr_r - j0);
+                if (!RAGGED || cnt > 0) mk = tile_segment<S, W>(v0 + r * npad, np_r, j0, cnt, w, e.g.nmax, e.g.part_mul, pid);     // (cnt <= 0: behind the read's last k-mer)
+                smask[r * mpad + seg] = mk;
+            }
+            const unsigned int n = (unsigned int)__popc(mk), incl = wave_inclusive_sum(n);
+            const unsigned int wave_n = (unsigned int)__builtin_amdgcn_readlane((int)incl, 63);
+            if (wave_n) {                                         // (wave-uniform)
+                unsigned int base = 0;
+                if ((threadIdx.x & 63) == 63) base = atomicAdd(&n_items, wave_n);
+                const unsigned int at = (unsigned int)__builtin_amdgcn_readlane((int)base, 63) + incl - n;
+                if (mk) {
+                    if (at + n > (unsigned int)icap) overflow = 1;    // (turn 0 only) nothing is stored, the list is forgotten below
+                    else tile_put_items<S>(mk, pid, r, j0, at, ikey, ipid);
+                }
             }
         }
         __syncthreads();
