@@ -23,7 +23,7 @@ else
 O       := o
 LIBNAME := libsoapdenovo2_amd.so
 endif
-HOSTOBJ := $(CSRC)/host_graph.$(O) $(CSRC)/host_reads.$(O) $(CSRC)/call_pregraph.$(O) $(CSRC)/host_skm.$(O) $(CSRC)/host_emu.$(O) $(CSRC)/host_plan.$(O) $(CSRC)/arena.$(O) $(CSRC)/call_map.$(O) $(CSRC)/map_host.$(O) $(CSRC)/map_plan.$(O) $(CSRC)/kindex_host.$(O) $(CSRC)/kindex_plan.$(O) $(CSRC)/ktrim_host.$(O) $(CSRC)/kcorrect_rows_host.$(O) $(CSRC)/kwalk_host.$(O) $(CSRC)/kunitig_host.$(O) $(CSRC)/kunitig_rank_host.$(O) $(CSRC)/kedit_host.$(O) $(CSRC)/kedit_ops_host.$(O)
+HOSTOBJ := $(CSRC)/host_graph.$(O) $(CSRC)/host_reads.$(O) $(CSRC)/call_pregraph.$(O) $(CSRC)/host_skm.$(O) $(CSRC)/host_emu.$(O) $(CSRC)/host_plan.$(O) $(CSRC)/arena.$(O) $(CSRC)/call_map.$(O) $(CSRC)/map_host.$(O) $(CSRC)/map_plan.$(O) $(CSRC)/kindex_host.$(O) $(CSRC)/kindex_plan.$(O) $(CSRC)/ktrim_host.$(O) $(CSRC)/kcorrect_rows_host.$(O) $(CSRC)/kwalk_host.$(O) $(CSRC)/kunitig_host.$(O) $(CSRC)/kunitig_rank_host.$(O) $(CSRC)/kedit_host.$(O) $(CSRC)/kedit_ops_host.$(O) $(CSRC)/kisolated_host.$(O)
 DEVOBJ  := $(CSRC)/pregraph_kernels.$(O) $(CSRC)/partition_kernels.$(O) $(CSRC)/graph_kernels.$(O) $(CSRC)/sort_records.$(O) $(CSRC)/exchange.$(O) $(CSRC)/map_kernels.$(O) $(CSRC)/kindex_kernels.$(O)
 HDRS    := $(wildcard $(CSRC)/*.hpp) include/soapdenovo2_amd.h
 

@@ -598,7 +598,8 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       PG_EINVAL: a threshold or max_tip out of range, out_totals null; PG_ESTATE: an index cut over ranks (a walk
  *                       chases its lookups in one table); nothing is written then and the index is untouched.  Device memory of the
  *                       index's device, asynchronous on `stream`, no host wait; the scratch is pg_kindex_unitigs'.  Host memory for a
- *                       host-twin index.  Not done: a cut index, isolated short unitigs; bubbles are pg_kindex_pop_bubbles'.
+ *                       host-twin index.  Not done: a cut index; isolated short unitigs are pg_kindex_drop_isolated's, bubbles
+ *                       pg_kindex_pop_bubbles'.
  *   pg_kindex_pop_bubbles        one round of bubble popping on the graph of the index (csrc/kbubble.hpp).  Solid, the arc sets, the side
  *                       test, the end reasons, min_cov (1..255) and min_arc (1..63) are pg_kindex_unitigs'.  A branch is a linear
  *                       unitig P = x0 -> .. -> x(n-1) whose two sides both have reason 6 branch in, with n <= max_len (1 .. 2^16
@@ -651,6 +652,24 @@ int pg_sort_records_ws(uint64_t *d_records, uint64_t n_records, int mer127, void
  *                       out_totals[4], always written: [0] arms popped, [1] k-mers removed, [2] solid k-mers before the round,
  *                       [3] arms kept.  Call rounds until out_totals[0] == 0.  PG_EINVAL, PG_ESTATE, the memory and the stream are
  *                       pg_kindex_pop_bubbles'.  Not done: a cut index, a comparison of the arms' bases, a choice among tied paths.
+ *   pg_kindex_drop_isolated      one round that drops the short isolated unitigs from the graph of the index (csrc/kisolated.hpp).
+ *                       Solid, the arc sets, the side test, the end reasons, linear unitigs, min_cov (1..255) and min_arc (1..63)
+ *                       are pg_kindex_unitigs'; free is pg_kindex_clip_tips': reason 3 dead end or 5 weak next.  An island is a linear
+ *                       unitig x0 -> .. -> x(n-1) whose two sides are both free, with n <= max_len (1 .. 2^16 k-mers).  It is
+ *                       removed iff cov <= max_cov n in 64-bit integers, cov the sum of its k-mers' coverage bytes and max_cov
+ *                       1 .. 255: the byte saturates at 255, so max_cov = 255 removes every island within max_len, and a smaller
+ *                       bound keeps a short fragment of high coverage.  A tip, the path before a fork, a chain with a hairpin side,
+ *                       a ring and a chain longer than max_len are no islands, and nothing of them is written.  An island is a
+ *                       start from both of its ends; it is decided once, from the end its unitig is emitted from.  The round decides
+ *                       over the index as it stood when it began, then applies: the cnt word of every k-mer of every removed
+ *                       island becomes 0 (pg_kindex_clip_tips' tombstone).  Nothing else is written: an island has no junction; use
+ *                       the index at the same or higher thresholds.  out_totals[4], always written: [0] islands removed, [1] k-mers
+ *                       removed, [2] solid k-mers before the round, [3] islands kept: within max_len, above max_cov.  Call rounds
+ *                       until out_totals[0] == 0.  PG_EINVAL: a threshold, max_len or max_cov out of range, out_totals null;
+ *                       PG_ESTATE: an index cut over ranks; nothing is written then and the index is untouched.  Device memory of
+ *                       the index's device, asynchronous on `stream`, no host wait; the scratch is pg_kindex_unitigs'.  Host memory
+ *                       for a host-twin index.  Not done: a cut index, isolated short rings, chains with a hairpin side, any choice
+ *                       of max_len or max_cov.
  *   pg_kindex_correct_rows       pg_kindex_correct on any index, by rounds over merged rows (csrc/kcorrect_rows.hpp).  The batch, its
  *                       tail, n_words and n_kmers are pg_kindex_query_words' and pg_kindex_trim's; packed_out, out_report, in-place
  *                       use, the report word, the rule and the argument errors are pg_kindex_correct's, and so is the result, bit for
@@ -703,6 +722,8 @@ int pg_kindex_pop_bubbles(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uin
 int pg_kindex_drop_weak_arcs(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint64_t *out_totals, void *stream);
 int pg_kindex_pop_bulges(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_len, uint32_t max_diff, uint64_t *out_totals,
                          void *stream);
+int pg_kindex_drop_isolated(pg_kindex *ix, uint32_t min_cov, uint32_t min_arc, uint32_t max_len, uint32_t max_cov, uint64_t *out_totals,
+                            void *stream);
 int pg_kindex_info(const pg_kindex *ix, uint64_t out[4]);
 void pg_kindex_destroy(pg_kindex *ix);
 uint64_t pg_host_kindex_bytes(uint64_t n_records, int mer127);   /* the table a build of n_records will cut; no GPU touched */

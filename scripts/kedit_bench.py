@@ -17,12 +17,16 @@ each.  --runs runs after one warm-up run.  No rate is asserted anywhere.
     --op all       the four operators in the order of KmerIndex.simplify(ops=("arcs", "tips", "bubbles", "bulges")): per-call times and
                    totals, every operator's first and first empty round as a ratio of the count call, then the unitigs, N50 and longest
                    unitig of the simplified index with its count call and full call timed.  Writes profiles/kedit_ops.json.
+    --op isolated  KmerIndex.simplify(ops=SIMPLIFY_OPS), not timed, and then pg_kindex_drop_isolated round by round: the
+                   first, removing round and the first empty one beside the count call, the islands and k-mers removed, and the unitig
+                   count, N50 and longest unitig before and after the rounds, by unitigs(engine="rank") in the last run.  Writes
+                   profiles/kisolated.json.
 
 Every setting is measured by a child process of its own under a time limit (--limit seconds; the parent does not touch the GPU), and the
 first child that fails or runs out of time ends the script: nothing more is started on the card after it.  Needs a GPU; nothing falls back.
 
-    python scripts/kedit_bench.py --op tips|bubbles|arcs|bulges|all [--reads 10000000] [--setting 3:2] [--max-tip 62] [--max-len 62] [--max-diff 0]
-                                  [--runs 3] [--limit 900] [--out profiles/NAME.json]
+    python scripts/kedit_bench.py --op tips|bubbles|arcs|bulges|all|isolated [--reads 10000000] [--setting 3:2] [--max-tip 62] [--max-len 62]
+                                  [--max-diff 0] [--max-cov 255] [--runs 3] [--limit 900] [--out profiles/NAME.json]
 """
 import argparse
 import json
@@ -48,6 +52,9 @@ NOT_MEASURED = {
 for _op in ("arcs", "bulges", "all"):
     NOT_MEASURED[_op] = ["the 127-mer build (K > 63: slots of 48 bytes, four-word keys)", "max_diff > 0 on reads with insertions and deletions",
                          REPEATS, "the idle share of lanes in the decide passes (no counters were collected and no estimate made)", ONE_CARD]
+NOT_MEASURED["isolated"] = ["the 127-mer build (K > 63: slots of 48 bytes, four-word keys)", "a max_cov below 255 (every island within max_len goes)", REPEATS,
+                            "the idle share of lanes in the decide pass (a start that is not free ends at once, a free one walks up to max_len k-mers: no "
+                            "counters were collected and no estimate made)", ONE_CARD]
 GENERIC_SUMMARY = ("calls_needed", "median_unitigs_count_call_seconds", "first_round_over_count_call", "median_all_calls_seconds", "unitigs", "n50_bases",
                    "longest_bases", "unitigs_count_call_after_seconds", "unitigs_full_call_after_seconds")
 # the calls of one cycle, in order; the summary fields printed at the end
@@ -57,7 +64,13 @@ OPS = {"tips": (("tips",), ("rounds_needed", "median_unitigs_count_call_seconds"
                                          "median_first_empty_bubble_round_seconds", "popping_round_over_count_call", "empty_round_over_count_call",
                                          "median_all_calls_seconds")),
        "arcs": (("arcs",), GENERIC_SUMMARY), "bulges": (("bulges",), GENERIC_SUMMARY), "all": (("arcs", "tips", "bubbles", "bulges"), GENERIC_SUMMARY)}
-DEFAULT_OUT = {"tips": "ktip.json", "bubbles": "kbubble.json", "arcs": "karc.json", "bulges": "kbulge.json", "all": "kedit_ops.json"}
+OPS["isolated"] = (("isolated",), ("rounds_needed", "median_unitigs_count_call_seconds", "median_first_round_seconds", "first_round_over_count_call",
+                                   "median_first_empty_round_seconds", "empty_round_over_count_call", "islands_removed", "kmers_removed", "unitigs_before",
+                                   "n50_bases_before", "unitigs_after", "n50_bases_after"))
+DEFAULT_OUT = {"tips": "ktip.json", "bubbles": "kbubble.json", "arcs": "karc.json", "bulges": "kbulge.json", "all": "kedit_ops.json", "isolated": "kisolated.json"}
+# what --op isolated records its figures against; nothing is asserted
+EXPECTED_ISOLATED = {"round_over_count_call": "0.68 to 0.75, the tips' empty round in profiles/kedit_ops.json: the same starts and the same walk",
+                     "unitigs_after": "1: the 15 353 fragments of DESIGN.md section 17 go and the genome's unitig is left"}
 
 
 def n50(lens):
@@ -65,6 +78,52 @@ def n50(lens):
     if not len(lens):
         return 0
     return int(lens[np.searchsorted(np.cumsum(lens), lens.sum() / 2.0)])
+
+
+def isolated_runs(a, kc, timed, new, min_cov, min_arc):
+    """--op isolated, one setting, over the counted reads: the result object."""
+    from soapdenovo2_amd import api
+    L_ = api.lib()
+
+    def ranked(ix):
+        u = ix.unitigs(min_cov, min_arc, engine="rank")
+        f = api.unitig_fields(u.report)
+        return {"totals": {k: int(v) for k, v in zip(api.UNITIG_TOTALS_FIELDS, u.totals)}, "n50_bases": n50(f["len"]),
+                "longest_bases": int(f["len"].max()) if len(f["len"]) else 0}
+
+    runs, before, after, info, simplify_calls = [], None, None, None, None
+    for i in range(a.runs + 1):                                        # (run 0 warms every path up)
+        ix = kc.index()
+        info = ix.info()
+        totals = new(8)
+        yard = timed(lambda: L_.pg_kindex_unitigs(ix.h, min_cov, min_arc, a.max_kmers, 0, 0, None, None, None, None, ix._ptr(totals), ix._stream()))
+        simplify_calls = [(name, [int(v) for v in t]) for name, t in ix.simplify(min_cov, min_arc, a.max_tip, a.max_len, a.max_diff, ops=api.SIMPLIFY_OPS)]
+        if i == a.runs:
+            before = ranked(ix)
+        calls, t4 = [], new(4)
+        while not calls or calls[-1]["islands"]:
+            sec = timed(lambda: L_.pg_kindex_drop_isolated(ix.h, min_cov, min_arc, a.max_len, a.max_cov, ix._ptr(t4), ix._stream()))
+            calls.append(dict(api.isolated_fields(t4), seconds=sec))
+            assert len(calls) <= 64
+        if i == a.runs:
+            after = ranked(ix)
+        ix.close()
+        print(f"[{a.child}] run {i}: count call {yard:.4f} s, {len(simplify_calls)} simplify calls, {len(calls)} rounds " +
+              " ".join(f"i{c['seconds']:.4f}" for c in calls), flush=True)
+        if i:
+            runs.append({"unitigs_count_call_seconds": yard, "rounds": calls})
+    yard = float(np.median([r["unitigs_count_call_seconds"] for r in runs]))
+    first = float(np.median([r["rounds"][0]["seconds"] for r in runs]))
+    empty = float(np.median([[c for c in r["rounds"] if not c["islands"]][0]["seconds"] for r in runs]))
+    return {"min_cov": min_cov, "min_arc": min_arc, "max_tip": a.max_tip, "max_len": a.max_len, "max_diff": a.max_diff, "max_cov": a.max_cov,
+            "max_kmers": a.max_kmers, "index": info, "simplify_calls": simplify_calls, "runs": runs, "rounds_needed": len(runs[0]["rounds"]),
+            "median_unitigs_count_call_seconds": yard, "median_first_round_seconds": first, "first_round_over_count_call": first / yard,
+            "median_first_empty_round_seconds": empty, "empty_round_over_count_call": empty / yard,
+            "first_round": {k: v for k, v in runs[0]["rounds"][0].items() if k != "seconds"},
+            "islands_removed": sum(c["islands"] for c in runs[0]["rounds"]), "kmers_removed": sum(c["kmers"] for c in runs[0]["rounds"]),
+            "unitigs_before_rounds": before, "unitigs_after_rounds": after, "unitigs_before": before["totals"]["unitigs"],
+            "n50_bases_before": before["n50_bases"], "unitigs_after": after["totals"]["unitigs"], "n50_bases_after": after["n50_bases"],
+            "expected_not_asserted": EXPECTED_ISOLATED}
 
 
 def child(a):
@@ -124,6 +183,11 @@ def child(a):
         sec = timed(lambda: L_.pg_kindex_pop_bubbles(ix.h, min_cov, min_arc, a.max_len, a.max_diff, ix._ptr(t4), ix._stream()))
         return dict(api.bubble_fields(t4), call="bubbles", removed=int(api.bubble_fields(t4)["branches"]), seconds=sec)
 
+    if a.op == "isolated":
+        res = isolated_runs(a, kc, timed, new, min_cov, min_arc)
+        kc.close()
+        json.dump(res, open(a.child_out, "w"))
+        return
     names = OPS[a.op][0]
     runs, built, tips_only, last, info = [], None, None, None, None
     for i in range(a.runs + 1):                                        # (run 0 warms every path up)
@@ -204,10 +268,11 @@ def main():
     ap.add_argument("--max-tip", type=int, default=62)
     ap.add_argument("--max-len", type=int, default=62)
     ap.add_argument("--max-diff", type=int, default=0)
+    ap.add_argument("--max-cov", type=int, default=255, help="--op isolated: pg_kindex_drop_isolated's coverage bound")
     ap.add_argument("--max-kmers", type=int, default=1 << 24)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--limit", type=int, default=900, help="seconds a setting's child process may take")
-    ap.add_argument("--out", default=None, help="default: profiles/ktip.json, kbubble.json, karc.json, kbulge.json, kedit_ops.json by --op")
+    ap.add_argument("--out", default=None, help="default: profiles/ktip.json, kbubble.json, karc.json, kbulge.json, kedit_ops.json, kisolated.json by --op")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child-out", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -218,6 +283,10 @@ def main():
     if a.op == "tips":
         what = (f"pg_kindex_clip_tips with max_tip {a.max_tip} round by round to the fixed point at each min_cov:min_arc, beside the "
                 f"unitigs' count call (max_kmers {a.max_kmers}) on the index as built; the unitigs before the clipping and after it")
+    elif a.op == "isolated":
+        what = (f"KmerIndex.simplify(ops=SIMPLIFY_OPS) with max_tip {a.max_tip}, max_len {a.max_len}, max_diff {a.max_diff}, not timed, then "
+                f"pg_kindex_drop_isolated (max_len {a.max_len}, max_cov {a.max_cov}) round by round to the fixed point at each min_cov:min_arc, beside "
+                f"the unitigs' count call (max_kmers {a.max_kmers}) on the index as built; the unitigs before and after the rounds by the ranked engine")
     elif a.op in ("arcs", "bulges", "all"):
         entries = {"arcs": "pg_kindex_drop_weak_arcs", "tips": f"pg_kindex_clip_tips (max_tip {a.max_tip})",
                    "bubbles": f"pg_kindex_pop_bubbles (max_len {a.max_len}, max_diff {a.max_diff})",

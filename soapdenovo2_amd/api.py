@@ -195,6 +195,7 @@ def lib() -> C.CDLL:
     L.pg_kindex_pop_bubbles.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
     L.pg_kindex_drop_weak_arcs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
     L.pg_kindex_pop_bulges.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
+    L.pg_kindex_drop_isolated.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u64p, C.c_void_p]
     L.pg_kindex_info.argtypes = [C.c_void_p, u64p]
     L.pg_kindex_destroy.argtypes = [C.c_void_p]
     L.pg_kindex_destroy.restype = None
@@ -231,6 +232,7 @@ EXPORTED_SYMBOLS = [
     "pg_kindex_build_sharded", "pg_kindex_from_ctx_sharded", "pg_kindex_query_words", "pg_kindex_ranks", "pg_kindex_rank_info", "pg_kindex_query_times",
     "pg_host_kindex_plan", "pg_kindex_trim", "pg_kindex_trim_times", "pg_kindex_correct_rows", "pg_kindex_correct_rows_stats",
     "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_unitigs_ranked", "pg_kindex_clip_tips", "pg_kindex_pop_bubbles", "pg_kindex_drop_weak_arcs", "pg_kindex_pop_bulges",
+    "pg_kindex_drop_isolated",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append", "pg_device_emu_clip_tips",
 ]
 
@@ -994,6 +996,18 @@ def bulge_fields(totals) -> dict:
     return _edit_fields(BULGE_TOTALS_FIELDS, totals)
 
 
+# The islands (pg_kindex_drop_isolated).  ISOLATED_MAX_BOUND is the most max_len the entry takes; its default is 2 K, as for the siblings.
+ISOLATED_MAX_BOUND = 1 << 16
+ISOLATED_TOTALS_FIELDS = ["islands", "kmers", "solid", "kept"]
+CLEAN_OPS = SIMPLIFY_OPS + ("isolated",)                       # every operator simplify knows: SIMPLIFY_OPS and, behind them, the islands
+
+
+def isolated_fields(totals) -> dict:
+    """A round's totals (pg_kindex_drop_isolated) by name: `islands` removed, `kmers` removed, `solid` k-mers before the round, and the
+    islands `kept`: those within max_len whose coverage is above max_cov a k-mer.  Takes a numpy array or a torch tensor of 4 words."""
+    return _edit_fields(ISOLATED_TOTALS_FIELDS, totals)
+
+
 def host_kindex_bytes(n_records: int, mer127: bool = False) -> int:
     """pg_host_kindex_bytes: the table an index of n_records k-mers cuts (no GPU)."""
     return int(lib().pg_host_kindex_bytes(n_records, 1 if mer127 else 0))
@@ -1357,20 +1371,33 @@ class KmerIndex:
         max_len = 2 * self.K if max_len is None else max_len
         return self._edit_rounds("pg_kindex_pop_bulges", (min_cov, min_arc, max_len, max_diff), max_rounds)
 
+    def drop_isolated(self, min_cov: int, min_arc: int, max_len=None, max_cov: int = 255, max_rounds: int = 64) -> list:
+        """Short isolated unitigs dropped from the index's graph, in place (pg_kindex_drop_isolated): an island is a chain of at most
+        max_len k-mers (default 2 K) that is free -- a dead end or a weak successor -- on both sides, and it is removed when the sum
+        of its k-mers' coverage is at most max_cov a k-mer (1 to 255; the default, 255, is where the coverage saturates: every island
+        within max_len).  A removed k-mer reads as absent from then on, to every operator; the records the index came from are not
+        touched.  Rings, chains with a hairpin end and tips are not islands.  Rounds are called until one removes nothing or
+        max_rounds is reached.  Returns the rounds' totals, a list of numpy arrays of ISOLATED_TOTALS_FIELDS (isolated_fields names
+        them).  The library chooses neither bound for the caller.  An index cut over ranks is refused."""
+        max_len = 2 * self.K if max_len is None else max_len
+        return self._edit_rounds("pg_kindex_drop_isolated", (min_cov, min_arc, max_len, max_cov), max_rounds)
+
     def simplify(self, min_cov: int, min_arc: int, max_tip=None, max_len=None, max_diff: int = 0, max_rounds: int = 64,
-                 ops=("tips", "bubbles")) -> list:
+                 ops=("tips", "bubbles"), max_cov: int = 255) -> list:
         """Every operator named in ops to its fixed point, in the order given, and all of them again -- a tip on a branch hides a
         bubble, a popped bubble can leave a tip, a removed k-mer leaves its neighbours' arcs dangling -- until a whole cycle removes
-        nothing or max_rounds rounds were called in all.  ops: names of SIMPLIFY_OPS -- "arcs" (drop_weak_arcs), "tips" (clip_tips),
-        "bubbles" (pop_bubbles), "bulges" (pop_bulges); the default is the tips and the bubbles, SIMPLIFY_OPS itself the full set; a
-        name that is none of them raises ValueError.  Returns the rounds in call order, a list of (name, totals)."""
+        nothing or max_rounds rounds were called in all.  ops: names of CLEAN_OPS -- "arcs" (drop_weak_arcs), "tips" (clip_tips),
+        "bubbles" (pop_bubbles), "bulges" (pop_bulges), "isolated" (drop_isolated, with max_len and max_cov); the default is the tips
+        and the bubbles, SIMPLIFY_OPS the four that edit the connected graph, CLEAN_OPS those and the islands behind them; a name
+        that is none of them raises ValueError.  Returns the rounds in call order, a list of (name, totals)."""
         ops = tuple(ops)
         for name in ops:
-            if name not in SIMPLIFY_OPS:
-                raise ValueError("KmerIndex.simplify: ops holds %r; the operators are %s" % (name, ", ".join(SIMPLIFY_OPS)))
+            if name not in CLEAN_OPS:
+                raise ValueError("KmerIndex.simplify: ops holds %r; the operators are %s" % (name, ", ".join(CLEAN_OPS)))
         run = {"arcs": lambda left: self.drop_weak_arcs(min_cov, min_arc, left), "tips": lambda left: self.clip_tips(min_cov, min_arc, max_tip, left),
                "bubbles": lambda left: self.pop_bubbles(min_cov, min_arc, max_len, max_diff, left),
-               "bulges": lambda left: self.pop_bulges(min_cov, min_arc, max_len, max_diff, left)}
+               "bulges": lambda left: self.pop_bulges(min_cov, min_arc, max_len, max_diff, left),
+               "isolated": lambda left: self.drop_isolated(min_cov, min_arc, max_len, max_cov, left)}
         out = []
         while len(out) < max_rounds:
             removed = 0

@@ -1,5 +1,5 @@
-// kedit.hpp -- what the operators that write to the table of the k-mer index share (DESIGN.md §15, §16, §16.1, §17): the tips (ktip.hpp),
-// the bubbles (kbubble.hpp), the arcs (karc.hpp) and the bulges (kbulge.hpp).  A ROUND of such an operator is the unitigs' ends sweep (kunitig.hpp: the start list), a decide pass that
+// kedit.hpp -- what the operators that write to the table of the k-mer index share (DESIGN.md §15, §16, §16.1, §17, §20): the tips (ktip.hpp),
+// the bubbles (kbubble.hpp), the arcs (karc.hpp), the bulges (kbulge.hpp) and the islands (kisolated.hpp).  A ROUND of such an operator is the unitigs' ends sweep (kunitig.hpp: the start list), a decide pass that
 // only reads -- every start over the index as it stood when the round began --, an apply pass that writes, and four totals.  The round
 // exists once for the device (kindex_kernels.hip: kedit_decide_kernel, kedit_apply_kernel, kedit_device_round) and once for the host
 // (kedit_host.hpp: kedit_host_round); the operator is a stateless struct Op, and this is all of it that either sees:
@@ -16,7 +16,7 @@
 namespace pg {
 
 constexpr int KEDIT_TOTALS = 4;
-// out_totals: unitigs removed (tips clipped, branches popped), k-mers removed, solid k-mers before the round, candidates kept
+// out_totals: unitigs removed (tips clipped, branches popped, islands dropped), k-mers removed, solid k-mers before the round, candidates kept
 enum : int { KEDIT_T_REMOVED = 0, KEDIT_T_KMERS = 1, KEDIT_T_SOLID = 2, KEDIT_T_KEPT = 3 };
 
 // What the decide pass says of a start: n k-mers walked; candidate: the operator's rule names it; minor: a candidate that is removed

@@ -1,8 +1,8 @@
 // kedit_host.hpp -- what the C ABI entries of the operators that edit the graph of the k-mer index share on the host (kedit_host.cpp: the
-// tips and the bubbles; kedit_ops_host.cpp: the arcs and the bulges): the round's host twin (a device = -1 index in one table) -- the
-// operator's rule (kedit.hpp) over host memory, the kernels' passes one after the other: ends, decide over every start, then apply: the
-// snapshot rule, not a sequential sweep, every lookup kunitig_probe --, the refusals every entry makes, and the dispatch between the twin
-// and the device engine.  What the CPU tests run, and the kernels' yardstick.
+// tips and the bubbles; kedit_ops_host.cpp: the arcs and the bulges; kisolated_host.cpp: the islands): the round's host twin (a
+// device = -1 index in one table) -- the operator's rule (kedit.hpp) over host memory, the kernels' passes one after the other: ends,
+// decide over every start, then apply: the snapshot rule, not a sequential sweep, every lookup kunitig_probe --, the refusals every
+// entry makes, and the dispatch between the twin and the device engine.  What the CPU tests run, and the kernels' yardstick.
 #pragma once
 #include <string>
 #include <vector>

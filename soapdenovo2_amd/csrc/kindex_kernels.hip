@@ -109,6 +109,8 @@
 // up-to-four targets of that side's arcs; apply looks them up again and takes the dangling ones out of the start's own word
 // The bulges (kbulge.hpp: KbulgeOp; pg_kindex_pop_bulges): the bubbles' start, branch and apply; in place of the siblings one
 // walk from the fork along the strictly strongest arcs to the join
+// The islands (kisolated.hpp: KisolatedOp; pg_kindex_drop_isolated): the tips' start and walk; a chain that is free at its far
+// end too is decided by the copy the unitigs emit, on its coverage sum; apply zeroes its k-mers and writes no junction
 // The corrector on an index cut over ranks (kcorrect_rows.hpp; pg_kindex_correct_rows): rounds of plan, query, decide on the
 // caller's stream, every query kidx_query_ranks, and the host reads the round's trial count back once a round
 //   kcor_rows_begin_kernel     a lane per read over its row of the read as given: weak count, anchor, first weak k-mer behind it, the
@@ -138,6 +140,7 @@
 #include "kcorrect_rows.hpp"
 #include "kedit.hpp"
 #include "kindex.hpp"
+#include "kisolated.hpp"
 #include "krank.hpp"
 #include "ktip.hpp"
 #include "ktrim.hpp"
@@ -1493,6 +1496,7 @@ template int kedit_device_round<KtipOp>(::pg_kindex*, const KtipParams&, uint64_
 template int kedit_device_round<KbubbleOp>(::pg_kindex*, const KbubbleParams&, uint64_t*, void*);
 template int kedit_device_round<KarcOp>(::pg_kindex*, const KarcParams&, uint64_t*, void*);
 template int kedit_device_round<KbulgeOp>(::pg_kindex*, const KbubbleParams&, uint64_t*, void*);
+template int kedit_device_round<KisolatedOp>(::pg_kindex*, const KisolatedParams&, uint64_t*, void*);
 
 // ---- the corrector on an index cut over ranks ----
 namespace {
