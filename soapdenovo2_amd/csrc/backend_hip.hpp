@@ -1,8 +1,6 @@
 // backend_hip.hpp -- the backend the product runs the device graph stages on (see backend.hpp): one HIP device, one stream.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include <string.h>
 #include <time.h>
@@ -12,6 +10,7 @@
 
 #include "backend.hpp"
 #include "arena.hpp"
+#include "dev_scratch.hpp"
 #include "../../include/soapdenovo2_amd.h"
 
 namespace pg {
@@ -65,8 +64,7 @@ struct HipBackend {
     static constexpr bool on_device = true;
     int error = 0;
     std::string error_text;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
+    DevArr<unsigned char> tmp;                    // the sorts' and scans' temporary, grow-only
     void* pinned = nullptr;                       // 256 bytes of page-locked host memory: the fixed points read a counter or two per round
     double t_readback = 0;                        // seconds spent in small read-backs (copy + wait), for the verbose lines
     unsigned long long n_readback = 0;
@@ -188,7 +186,7 @@ struct HipBackend {
     }
     HipBackend(const HipBackend&) = delete;
     HipBackend& operator=(const HipBackend&) = delete;
-    ~HipBackend() { if (tmp) (void)pg::arena_free(tmp); if (pinned) (void)hipHostFree(pinned); }
+    ~HipBackend() { if (pinned) (void)hipHostFree(pinned); }
 
     bool ok(hipError_t e, const char* what) {
         if (e == hipSuccess) return true;
@@ -235,40 +233,17 @@ struct HipBackend {
         tick_end(-1, stream, ev);
         ok(hipGetLastError(), "launch");
     }
-    bool scratch(size_t bytes) {
-        if (bytes <= tmp_bytes) return true;
-        if (tmp) (void)pg::arena_free(tmp);
-        tmp = nullptr; tmp_bytes = 0;
-        if (!ok(pg::arena_malloc(&tmp, bytes), "hipMalloc (scratch)")) return false;
-        tmp_bytes = bytes;
-        return true;
-    }
+    bool scratch(size_t bytes) { return ok(tmp.reserve(bytes, 0), "hipMalloc (scratch)"); }
     template <typename KT, typename V> void sort_pairs(const KT* kin, KT* kout, const V* vin, V* vout, uint64_t n, int bits) {
         static_assert(sizeof(KT) == 8, "64-bit keys");
         if (!n || error) return;
-        size_t need = 0;
-        if (!ok((rocprim::radix_sort_pairs<rocprim::default_config, const KT*, KT*, const V*, V*, size_t>(
-                    nullptr, need, kin, kout, vin, vout, (size_t)n, 0u, (unsigned)bits, stream)), "radix sort (size)")) return;
-        if (!scratch(need)) return;
+        if (!scratch(dev_sort_pairs_bytes(kin, kout, vin, vout, (size_t)n, (unsigned)bits, stream))) return;
         hipEvent_t ev; tick_begin(-1, stream, ev);
-        ok((rocprim::radix_sort_pairs<rocprim::default_config, const KT*, KT*, const V*, V*, size_t>(
-               tmp, need, kin, kout, vin, vout, (size_t)n, 0u, (unsigned)bits, stream)), "radix sort");
+        ok(dev_sort_pairs(tmp, kin, kout, vin, vout, (size_t)n, (unsigned)bits, stream), "radix sort");
         tick_end(-1, stream, ev);
     }
-    void inclusive_max(const long long* in, long long* out, uint64_t n) {
-        if (!n || error) return;
-        size_t need = 0;
-        if (!ok(rocprim::inclusive_scan(nullptr, need, in, out, (size_t)n, BeMaxLL(), stream), "scan (size)")) return;
-        if (!scratch(need)) return;
-        ok(rocprim::inclusive_scan(tmp, need, in, out, (size_t)n, BeMaxLL(), stream), "scan");
-    }
-    void exclusive_sum(const unsigned long long* in, unsigned long long* out, uint64_t n) {
-        if (!n || error) return;
-        size_t need = 0;
-        if (!ok(rocprim::exclusive_scan(nullptr, need, in, out, 0ULL, (size_t)n, rocprim::plus<unsigned long long>(), stream), "sum (size)")) return;
-        if (!scratch(need)) return;
-        ok(rocprim::exclusive_scan(tmp, need, in, out, 0ULL, (size_t)n, rocprim::plus<unsigned long long>(), stream), "sum");
-    }
+    void inclusive_max(const long long* in, long long* out, uint64_t n) { if (n && !error) ok(dev_inclusive_scan(tmp, in, out, (size_t)n, BeMaxLL(), stream), "scan"); }
+    void exclusive_sum(const unsigned long long* in, unsigned long long* out, uint64_t n) { if (n && !error) ok(dev_exclusive_sum(tmp, in, out, (size_t)n, stream), "sum"); }
 };
 
 }  // namespace pg

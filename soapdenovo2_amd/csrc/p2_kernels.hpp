@@ -453,15 +453,15 @@ static int p2_make_look(P2Device* d) {
     for (int s = 0; s < d->P; s++) if (d->set_dev[s] != d->device) return PG_OK;
     const bool verbose = pg::env_user("PG_HOST_VERBOSE") != nullptr;
     const double t0 = p2_now();
-    unsigned long long* d_n = nullptr;
-    P2_HIP(pg::arena_malloc((void**)&d_n, sizeof(unsigned long long)));
-    P2_HIP(hipMemsetAsync(d_n, 0, sizeof(unsigned long long), d->stream));
+    DevArr<unsigned long long> d_n;
+    P2_HIP(d_n.alloc(1));
+    P2_HIP(hipMemsetAsync(d_n.p, 0, sizeof(unsigned long long), d->stream));
     for (int s = 0; s < d->P; s++)
-        hipLaunchKernelGGL(p2_look_count, dim3((unsigned)std::min<uint64_t>((d->set_sizes[s] + 255) / 256, 1u << 15)), dim3(256), 0, d->stream, d->set_ptr[s], d->nw + 1, d->set_sizes[s], d_n);
+        hipLaunchKernelGGL(p2_look_count, dim3((unsigned)std::min<uint64_t>((d->set_sizes[s] + 255) / 256, 1u << 15)), dim3(256), 0, d->stream, d->set_ptr[s], d->nw + 1, d->set_sizes[s], d_n.p);
     unsigned long long n_keys = 0;
-    P2_HIP(hipMemcpyAsync(&n_keys, d_n, sizeof n_keys, hipMemcpyDeviceToHost, d->stream));
+    P2_HIP(hipMemcpyAsync(&n_keys, d_n.p, sizeof n_keys, hipMemcpyDeviceToHost, d->stream));
     P2_HIP(hipStreamSynchronize(d->stream));
-    pg::arena_free(d_n);
+    d_n.reset();
     const int ES = d->nw == 2 ? 4 : 8, EPB = d->nw == 2 ? 2 : 1;
     size_t free_b = 0, total_b = 0;
     P2_HIP(pg::arena_mem_info(&free_b, &total_b));
@@ -497,19 +497,16 @@ static void p2_drop_look(P2Device* d) {
     for (P2Lane& ln : d->lanes) ln.prm.look = nullptr;
 }
 // ---- routed pass 2: one round = the batches that wait on the lanes (one each at most), all lanes working at once ---------------------------
-template <typename T>
-static int p2r_grow(P2Lane::Buf<T>& b, size_t need) {
-    if (need <= b.cap && b.p) return PG_OK;
-    if (b.p) P2_HIP(pg::arena_free(b.p));
-    b.p = nullptr;
-    b.cap = need + need / 4 + 64;
-    P2_HIP(pg::arena_malloc((void**)&b.p, b.cap * sizeof(T)));
-    return PG_OK;
+// a lane's index rows of a batch (word offsets, lengths): room for n_reads, a quarter more when they grow -- both rows go before either comes again
+static hipError_t p2_reserve_read_rows(P2Lane& ln, size_t n_reads) {
+    if (n_reads > ln.d_off.n) { ln.d_off.reset(); ln.d_lens.reset(); }
+    const hipError_t e = ln.d_off.reserve(n_reads, n_reads / 4);
+    return e == hipSuccess ? ln.d_lens.reserve(n_reads, n_reads / 4) : e;
 }
 // -R: the walks of a lane's batch (its rows of the staging matrix, their lengths) on their way to the caller, behind the kernel that writes them
 static int p2_download_walks(const P2Device* d, P2Lane& ln, uint64_t n_reads, uint32_t* walks_out, uint16_t* walk_len_out) {
-    P2_HIP(hipMemcpyAsync(walks_out, ln.d_stage, n_reads * (size_t)d->max_nk * sizeof(uint32_t), hipMemcpyDeviceToHost, ln.stream));
-    P2_HIP(hipMemcpyAsync(walk_len_out, ln.d_walk_len, n_reads * sizeof(uint16_t), hipMemcpyDeviceToHost, ln.stream));
+    P2_HIP(hipMemcpyAsync(walks_out, ln.d_stage.p, n_reads * (size_t)d->max_nk * sizeof(uint32_t), hipMemcpyDeviceToHost, ln.stream));
+    P2_HIP(hipMemcpyAsync(walk_len_out, ln.d_walk_len.p, n_reads * sizeof(uint16_t), hipMemcpyDeviceToHost, ln.stream));
     return PG_OK;
 }
 // the next lane in turn among those on `device`
@@ -540,22 +537,20 @@ static int p2_route_round(P2Device* d) {
         P2_HIP(hipSetDevice(ln.device));
         const uint32_t nblocks = (uint32_t)((b.n_reads + 255) / 256);
         const size_t nh = (size_t)N * nblocks + 1;
-        int rc = p2r_grow(ln.hist_in, nh);
-        if (!rc) rc = p2r_grow(ln.hist, nh);
-        if (!rc) rc = p2r_grow(ln.where, (size_t)N * nblocks * 256);
-        if (!rc) rc = p2r_grow(ln.ans, (size_t)b.q);
-        if (!rc) rc = p2r_grow(ln.send, (size_t)b.q * nw);
-        if (rc) return rc;
+        const size_t nwh = (size_t)N * nblocks * 256, nq = (size_t)b.q, nk = nq * nw;      // (the lane's buffers of the rounds grow by a quarter more than asked)
+        P2_HIP(ln.hist_in.reserve(nh, nh / 4 + 64));
+        P2_HIP(ln.hist.reserve(nh, nh / 4 + 64));
+        P2_HIP(ln.where.reserve(nwh, nwh / 4 + 64));
+        P2_HIP(ln.ans.reserve(nq, nq / 4 + 64));
+        P2_HIP(ln.send.reserve(nk, nk / 4 + 64));
         P2Route ro{N, nblocks, ln.d_owner_of_set, ln.hist_in.p, ln.send.p, ln.where.p};
         const dim3 grid(nblocks), block(256);
         P2_HIP(hipMemsetAsync(ln.hist_in.p + (nh - 1), 0, sizeof(uint32_t), ln.stream));
         P2_LAUNCH_NW(nw, (p2_route_hist<NW>), grid, block, 0, ln.stream, ln.prm, ro, b.d_words, b.d_off, b.d_lens, b.n_reads, b.uniform_len);
         P2_HIP(hipGetLastError());
-        size_t need = 0;
-        P2_HIP(rocprim::exclusive_scan(nullptr, need, ln.hist_in.p, ln.hist.p, 0u, nh, rocprim::plus<uint32_t>(), ln.stream));
-        rc = p2r_grow(ln.scan_tmp, need);
-        if (rc) return rc;
-        P2_HIP(rocprim::exclusive_scan((void*)ln.scan_tmp.p, need, ln.hist_in.p, ln.hist.p, 0u, nh, rocprim::plus<uint32_t>(), ln.stream));
+        const size_t need = dev_exclusive_sum_bytes(ln.hist_in.p, ln.hist.p, nh, ln.stream);
+        P2_HIP(ln.scan_tmp.reserve(need, need / 4 + 64));
+        P2_HIP(dev_exclusive_sum(ln.scan_tmp, ln.hist_in.p, ln.hist.p, nh, ln.stream));
         ro.hist = ln.hist.p;
         P2_LAUNCH_NW(nw, (p2_route_scatter<NW>), grid, block, 0, ln.stream, ln.prm, ro, b.d_words, b.d_off, b.d_lens, b.n_reads, b.uniform_len);
         P2_HIP(hipGetLastError());
@@ -578,9 +573,9 @@ static int p2_route_round(P2Device* d) {
         P2Lane& ow = d->lanes[o];
         if (!recv_total[o]) continue;
         P2_HIP(hipSetDevice(ow.device));
-        int rc = p2r_grow(ow.rans, (size_t)recv_total[o]);
-        if (!rc) rc = p2r_grow(ow.rkeys, (size_t)recv_total[o] * nw);
-        if (rc) return rc;
+        const size_t na = (size_t)recv_total[o], nk = na * nw;
+        P2_HIP(ow.rans.reserve(na, na / 4 + 64));
+        P2_HIP(ow.rkeys.reserve(nk, nk / 4 + 64));
         for (int l = 0; l < N; l++) {
             const uint64_t c = cnt[(size_t)l * N + o];
             if (!c) continue;
@@ -608,8 +603,8 @@ static int p2_route_round(P2Device* d) {
             if (c) P2_HIP(p2r_copy(ln.ans.p + ln.h_starts[o], ln.device, d->lanes[o].rans.p + recv_off[(size_t)o * N + l], d->lanes[o].device, c * sizeof(uint64_t), ln.stream));
         }
         P2Params p = ln.prm;
-        p.stage = d->reps ? ln.d_stage : nullptr;
-        p.walk_len = d->reps ? ln.d_walk_len : nullptr;
+        p.stage = d->reps ? ln.d_stage.p : nullptr;
+        p.walk_len = d->reps ? ln.d_walk_len.p : nullptr;
         const uint32_t nblocks = (uint32_t)((b.n_reads + 255) / 256);
         const dim3 grid(nblocks), block(256);
         const P2Route ro{N, nblocks, ln.d_owner_of_set, nullptr, nullptr, ln.where.p};
@@ -628,8 +623,8 @@ static int p2_batch_ready(P2Device* d, P2Lane& ln, const uint64_t* d_words, cons
                           uint32_t* walks_out, uint16_t* walk_len_out, bool round_now) {
     if (!d->route) {
         P2Params p = ln.prm;
-        p.stage = d->reps && !uniform_len ? ln.d_stage : nullptr;
-        p.walk_len = d->reps && !uniform_len ? ln.d_walk_len : nullptr;
+        p.stage = d->reps && !uniform_len ? ln.d_stage.p : nullptr;
+        p.walk_len = d->reps && !uniform_len ? ln.d_walk_len.p : nullptr;
         const dim3 grid((unsigned)((n_reads + 255) / 256));
         p2_launch_thread_kernel(d->nw, grid, ln.stream, p, d_words, d_off, d_lens, n_reads, d->ordinal, uniform_len);
         P2_HIP(hipGetLastError());
@@ -656,35 +651,24 @@ int p2_add_packed(P2Device* d, const uint64_t* words, const uint64_t* word_off, 
     P2Lane& ln = d->lanes[d->next_lane++ % d->lanes.size()];
     if (d->route && ln.pend.have) { const int rc = p2_route_round(d); if (rc) return rc; }      // (its buffers still hold a batch that waits for its round)
     P2_HIP(hipSetDevice(ln.device));
-    if (n_words + 8 > ln.cap_words || n_reads > ln.cap_reads || (d->reps && n_reads > ln.cap_stage_reads)) P2_HIP(hipStreamSynchronize(ln.stream));   // nobody reads the buffers that go
-    if (n_words + 8 > ln.cap_words) {
-        pg::arena_free(ln.d_words);
-        ln.cap_words = (n_words + 8) * 5 / 4;
-        P2_HIP(pg::arena_malloc((void**)&ln.d_words, ln.cap_words * sizeof(uint64_t)));
-    }
-    if (n_reads > ln.cap_reads) {
-        pg::arena_free(ln.d_off); pg::arena_free(ln.d_lens);
-        ln.cap_reads = n_reads * 5 / 4;
-        P2_HIP(pg::arena_malloc((void**)&ln.d_off, ln.cap_reads * sizeof(uint64_t)));
-        P2_HIP(pg::arena_malloc((void**)&ln.d_lens, ln.cap_reads * sizeof(int32_t)));
-    }
-    if (d->reps && n_reads > ln.cap_stage_reads) {
-        pg::arena_free(ln.d_stage); pg::arena_free(ln.d_walk_len);
-        ln.cap_stage_reads = n_reads;
-        P2_HIP(pg::arena_malloc((void**)&ln.d_stage, ln.cap_stage_reads * (size_t)d->max_nk * sizeof(uint32_t)));
-        P2_HIP(pg::arena_malloc((void**)&ln.d_walk_len, ln.cap_stage_reads * sizeof(uint16_t)));
-    }
+    const size_t nwp = n_words + 8, nst = d->reps ? (size_t)n_reads : 0;
+    if (nwp > ln.d_words.n || n_reads > ln.d_off.n || nst > ln.d_walk_len.n) P2_HIP(hipStreamSynchronize(ln.stream));   // nobody reads the buffers that go
+    // (words and index rows grow by a quarter more than asked, the -R rows to the batch; a pair of rows goes before either comes again)
+    P2_HIP(ln.d_words.reserve(nwp, nwp / 4));
+    P2_HIP(p2_reserve_read_rows(ln, n_reads));
+    if (nst > ln.d_walk_len.n) { ln.d_stage.reset(); ln.d_walk_len.reset(); }
+    if (d->reps) { P2_HIP(ln.d_stage.reserve(nst * (size_t)d->max_nk, 0)); P2_HIP(ln.d_walk_len.reserve(nst, 0)); }
     // (the copies are ordered behind the lane's previous batch by its stream: that batch read the same buffers)
-    P2_HIP(hipMemcpyAsync(ln.d_words, words, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ln.stream));
-    P2_HIP(hipMemsetAsync(ln.d_words + n_words, 0, 8 * sizeof(uint64_t), ln.stream));      // readable padding for the window loads
-    P2_HIP(hipMemcpyAsync(ln.d_off, word_off, n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, ln.stream));
-    P2_HIP(hipMemcpyAsync(ln.d_lens, lens, n_reads * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
+    P2_HIP(hipMemcpyAsync(ln.d_words.p, words, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ln.stream));
+    P2_HIP(hipMemsetAsync(ln.d_words.p + n_words, 0, 8 * sizeof(uint64_t), ln.stream));      // readable padding for the window loads
+    P2_HIP(hipMemcpyAsync(ln.d_off.p, word_off, n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, ln.stream));
+    P2_HIP(hipMemcpyAsync(ln.d_lens.p, lens, n_reads * sizeof(int32_t), hipMemcpyHostToDevice, ln.stream));
     uint64_t q = 0;
     if (d->route)                                                     // the lookups the batch asks for (prlRead2path.c:1103: reads shorter than K + 1 have none)
         for (uint64_t r = 0; r < n_reads; r++) if (lens[r] >= d->K + 1) q += (uint64_t)(lens[r] - d->K + 1);
     P2_HIP(hipEventRecord(ln.copied, ln.stream));
     // (-R: the walks come back with the call, so a routed batch does not wait for the other lanes' batches)
-    { const int rc = p2_batch_ready(d, ln, ln.d_words, ln.d_off, ln.d_lens, n_reads, q, 0, walks_out, walk_len_out, d->reps); if (rc) return rc; }
+    { const int rc = p2_batch_ready(d, ln, ln.d_words.p, ln.d_off.p, ln.d_lens.p, n_reads, q, 0, walks_out, walk_len_out, d->reps); if (rc) return rc; }
     if (d->route) { P2_HIP(hipSetDevice(ln.device)); P2_HIP(hipEventSynchronize(ln.copied)); }
     else if (d->reps && walks_out && walk_len_out) {
         const int rc = p2_download_walks(d, ln, n_reads, walks_out, walk_len_out);
@@ -782,35 +766,29 @@ int p2_add_packed_device_segments(P2Device* d, const uint64_t* const* d_segs, co
         return PG_OK;
     }
     P2Lane& ln = d->lanes[0];
+    P2BackOn back{d->device};
     P2_HIP(hipSetDevice(ln.device));
-    int rc = PG_OK;
-    uint32_t *keys = nullptr, *keys2 = nullptr, *idx = nullptr, *perm = nullptr;
-    const uint64_t** d_table = nullptr;
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
+    DevArr<const uint64_t*> table;                                  // (on the lane's device, all of them)
+    DevArr<uint32_t> keys, keys2, idx, perm;
+    DevArr<unsigned char> tmp;
     hipStream_t st = ln.stream;
     const unsigned grid = (unsigned)((total + 255) / 256);
-    P2_HIP_GOTO(pg::arena_malloc((void**)&d_table, (size_t)n_segs * sizeof(uint64_t*)));
-    P2_HIP_GOTO(hipMemcpyAsync(d_table, d_segs, (size_t)n_segs * sizeof(uint64_t*), hipMemcpyHostToDevice, st));
-    P2_HIP_GOTO(pg::arena_malloc((void**)&keys, total * 4)); P2_HIP_GOTO(pg::arena_malloc((void**)&keys2, total * 4));
-    P2_HIP_GOTO(pg::arena_malloc((void**)&idx, total * 4)); P2_HIP_GOTO(pg::arena_malloc((void**)&perm, total * 4));
-    P2_HIP_GOTO((rocprim::radix_sort_pairs<rocprim::default_config, uint32_t*, uint32_t*, uint32_t*, uint32_t*, size_t>(nullptr, tmp_bytes, keys, keys2, idx, perm, (size_t)total, 0u, 32u, st)));
-    P2_HIP_GOTO(pg::arena_malloc(&tmp, tmp_bytes));
-    hipLaunchKernelGGL(p2_read_place_keys, dim3(grid), dim3(256), 0, st, (const uint64_t* const*)d_table, (uint32_t)seg_reads[0], total, read_len, keys, idx);
-    P2_HIP_GOTO(hipGetLastError());
-    P2_HIP_GOTO((rocprim::radix_sort_pairs<rocprim::default_config, uint32_t*, uint32_t*, uint32_t*, uint32_t*, size_t>(tmp, tmp_bytes, keys, keys2, idx, perm, (size_t)total, 0u, 32u, st)));
+    EB_HIP(table.alloc((size_t)n_segs));
+    EB_HIP(hipMemcpyAsync(table.p, d_segs, (size_t)n_segs * sizeof(uint64_t*), hipMemcpyHostToDevice, st));
+    EB_HIP(keys.alloc(total)); EB_HIP(keys2.alloc(total));
+    EB_HIP(idx.alloc(total)); EB_HIP(perm.alloc(total));
+    EB_HIP(tmp.alloc(dev_sort_pairs_bytes(keys.p, keys2.p, idx.p, perm.p, (size_t)total, 32u, st)));
+    hipLaunchKernelGGL(p2_read_place_keys, dim3(grid), dim3(256), 0, st, (const uint64_t* const*)table.p, (uint32_t)seg_reads[0], total, read_len, keys.p, idx.p);
+    EB_HIP(hipGetLastError());
+    EB_HIP(dev_sort_pairs(tmp, keys.p, keys2.p, idx.p, perm.p, (size_t)total, 32u, st));
     {
         P2Params p = ln.prm;
         p.stage = nullptr; p.walk_len = nullptr;
-        p2_launch_thread_kernel(d->nw, dim3(grid), st, p, nullptr, nullptr, nullptr, total, d->ordinal, read_len, P2Order{perm, (const uint64_t* const*)d_table, (uint32_t)seg_reads[0]});
-        P2_HIP_GOTO(hipGetLastError());
+        p2_launch_thread_kernel(d->nw, dim3(grid), st, p, nullptr, nullptr, nullptr, total, d->ordinal, read_len, P2Order{perm.p, (const uint64_t* const*)table.p, (uint32_t)seg_reads[0]});
+        EB_HIP(hipGetLastError());
     }
-    P2_HIP_GOTO(hipStreamSynchronize(st));
+    EB_HIP(hipStreamSynchronize(st));
     if (pg::env_user("PG_HOST_VERBOSE")) fprintf(stderr, "pass 2: %llu read(s) of %d segment(s) threaded in one launch, sorted by their smallest hashed 16-mer\n", (unsigned long long)total, n_segs);
-done:
-    if (rc) (void)hipStreamSynchronize(st);
-    pg::arena_free(tmp); pg::arena_free(keys); pg::arena_free(keys2); pg::arena_free(idx); pg::arena_free(perm); pg::arena_free((void*)d_table);      // (on the lane's device)
-    if (rc) { P2_HIP(hipSetDevice(d->device)); return rc; }
     return p2_batch_done(d, ln, total, (uint64_t)n_segs);
 }
 
@@ -830,17 +808,11 @@ int p2_add_packed_device_ragged(P2Device* d, const uint64_t* d_words, const uint
     if (!ln) return PG_EINVAL;
     if (d->route && ln->pend.have) { const int rc = p2_route_round(d); if (rc) return rc; }      // (its length row still serves a batch that waits for its round)
     P2_HIP(hipSetDevice(ln->device));
-    if (n_reads > ln->cap_reads) {
-        P2_HIP(hipStreamSynchronize(ln->stream));
-        pg::arena_free(ln->d_off); pg::arena_free(ln->d_lens);
-        ln->d_off = nullptr; ln->d_lens = nullptr;
-        ln->cap_reads = n_reads * 5 / 4;
-        P2_HIP(pg::arena_malloc((void**)&ln->d_off, ln->cap_reads * sizeof(uint64_t)));
-        P2_HIP(pg::arena_malloc((void**)&ln->d_lens, ln->cap_reads * sizeof(int32_t)));
-    }
-    hipLaunchKernelGGL(p2_lens_from_kbase, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, ln->stream, d_kmer_base, n_reads, d->K, ln->d_lens);
+    if (n_reads > ln->d_off.n) P2_HIP(hipStreamSynchronize(ln->stream));
+    P2_HIP(p2_reserve_read_rows(*ln, n_reads));
+    hipLaunchKernelGGL(p2_lens_from_kbase, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, ln->stream, d_kmer_base, n_reads, d->K, ln->d_lens.p);
     P2_HIP(hipGetLastError());
-    { const int rc = p2_batch_ready(d, *ln, d_words, d_word_off, ln->d_lens, n_reads, n_kmers, 0, nullptr, nullptr, true); if (rc) return rc; }
+    { const int rc = p2_batch_ready(d, *ln, d_words, d_word_off, ln->d_lens.p, n_reads, n_kmers, 0, nullptr, nullptr, true); if (rc) return rc; }
     P2_HIP(hipSetDevice(ln->device));
     P2_HIP(hipStreamSynchronize(ln->stream));
     return p2_batch_done(d, *ln, n_reads);

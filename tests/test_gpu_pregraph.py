@@ -307,6 +307,30 @@ def test_cli_tip_listing_short_of_room_lists_again(golden, tmp_path, name):
         assert md5_file(pre + ".preArc") == want["preArc"], t
 
 
+@pytest.mark.parametrize("name,devices", [("t6k_k31", None), ("d8k_k63", None), ("m60k_k63", "0,0")])
+def test_cli_edge_listings_short_of_room_list_again(golden, tmp_path, name, devices):
+    """The vertex lists of the lanes, the waypoint list and the lanes' kept-walk records are listed into capped arrays that count everything and
+    come again when the room was short (csrc/dev_scratch.hpp: DevListing) -- which no input of test size ever is.  PG_EB_LIST_ROOM=1 leaves
+    room for one: every golden case has far more than one vertex, one waypoint at period 4 and one kept walk, so each listing must say that it
+    came again (with two ranks on GPU 0: two lanes, each with lists of its own).  The files, the -R pair included, stay the reference's."""
+    c = golden["cases"][name]
+    cfg = case_config(c, str(tmp_path), name)
+    env = {"PG_EB_LIST_ROOM": "1", "SOAPDENOVO2_AMD_EB_WAYPOINTS": "4", "PG_HOST_VERBOSE": "1"}
+    if devices:
+        env["SOAPDENOVO2_AMD_DEVICES"] = devices
+    for run in c["runs"]:
+        P, D, a, m = run
+        t = case_tag(name, run)
+        pre = str(tmp_path / t)
+        log = _run_cli(cfg, c["K"], pre, P, D, a, m, R=True, extra_env=env)
+        for what in ("vertices listed again", "waypoints listed again", "walk records listed again"):
+            assert what in log, (t, what)
+        want = golden["md5"][t]
+        for ext in ("kmerFreq", "preGraphBasic", "vertex", "preArc", "path", "markOnEdge"):
+            assert md5_file(pre + "." + ext) == want[ext], (t, ext)
+        assert md5_gz_text(pre + ".edge.gz") == want["edge"], t
+
+
 @pytest.mark.parametrize("form,says", [("SOAPDENOVO2_AMD_P2_SORT", "sorted by their smallest hashed 16-mer"),
                                        ("SOAPDENOVO2_AMD_P2_PARTITIONED", "through the partition engine"),
                                        ("SOAPDENOVO2_AMD_P2_LOOK", "pass 2: lookup table of")])
