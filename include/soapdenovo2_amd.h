@@ -885,6 +885,14 @@ int pg_device_emu_clip_tips(int device, const uint64_t *records, uint64_t n_reco
  * (every hit, also those beyond cap).  PG_ESTATE when the kernel wrote behind cap. */
 #define PG_EMU_APPEND_BASE 0x9E3779B900000000ULL
 int pg_device_emu_append(int device, const unsigned char *flags, uint64_t n, uint64_t cap, uint64_t *list_out, uint64_t *count_out);
+/* Pass 2's pre-arc path on n caller-given triples (from[i], to[i], seq[i]), seq = read ordinal << 16 | position, (0, 0) is no pair:
+ * `lanes` tables of `room` entries each (a power of two >= 2) are made by p2_arc_init, triple i goes to table i mod lanes through the
+ * product's add_prearc (csrc/p2_kernels.hpp), one device lane a triple, and the tables are counted, read out into one array and folded
+ * as a run's are (p2_count_arcs, p2_compact_arcs, p2_fold_arcs; the lanes' copies of a pair are merged when lanes > 1).  out3 (room for
+ * 3 n words) = (from, to, multiplicity) of every pair in .preArc order, *count_out = how many, *overflow_out = the triples that found
+ * their table full, over all lanes.  With an overflow nothing is folded and the call fails (PG_ENOMEM, "pre-arc table overflow"). */
+int pg_device_emu_prearcs(int device, const uint32_t *from, const uint32_t *to, const uint64_t *seq, uint64_t n, uint64_t room, int lanes,
+                          uint32_t *out3, uint64_t *count_out, uint64_t *overflow_out);
 
 /* The `map` stage's two operators on caller-owned host arrays, for tests: the contig k-mer index of n_ctg contigs (each of K + 2 bases
  * or more, packed with pg_pack_read, contig i at ctg_words + ctg_off[i], ctg_off[n_ctg] = words in all; its k-mers carry ctg_ids[i])

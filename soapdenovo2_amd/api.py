@@ -176,6 +176,7 @@ def lib() -> C.CDLL:
     L.pg_device_emu_home_slots.argtypes = [C.c_int, u64p, C.c_uint64, C.c_int, C.c_uint64, u64p]
     L.pg_device_emu_append.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, u64p, u64p]
     L.pg_device_emu_clip_tips.argtypes = [C.c_int, u64p, C.c_uint64, u64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u64p]
+    L.pg_device_emu_prearcs.argtypes = [C.c_int, u64p, u64p, u64p, C.c_uint64, C.c_uint64, C.c_int, u64p, u64p, u64p]
     # the k-mer index (include/soapdenovo2_amd.h, section 3)
     L.pg_kindex_build.restype = C.c_void_p
     L.pg_kindex_build.argtypes = [C.c_int, C.c_int, C.c_int, u64p, C.c_uint64, C.c_void_p]
@@ -234,6 +235,7 @@ EXPORTED_SYMBOLS = [
     "pg_kindex_walk", "pg_kindex_unitigs", "pg_kindex_unitigs_ranked", "pg_kindex_clip_tips", "pg_kindex_pop_bubbles", "pg_kindex_drop_weak_arcs", "pg_kindex_pop_bulges",
     "pg_kindex_drop_isolated",
     "pg_device_emu_layout_static", "pg_device_emu_layout_growable", "pg_device_emu_home_slots", "pg_device_emu_append", "pg_device_emu_clip_tips",
+    "pg_device_emu_prearcs",
 ]
 
 
@@ -493,19 +495,43 @@ def host_pregraph_files(records: np.ndarray, set_last_put, codes: np.ndarray, le
     if lens is not None:
         lens = np.ascontiguousarray(lens, dtype=np.int32)
     bounds = np.linspace(0, n, batches + 1).astype(int)
-    for b in range(batches):
-        lo, hi = int(bounds[b]), int(bounds[b + 1])
-        if hi > lo and packed:           # the reads as pass 1 packs them (pg_pack_read), back to back
-            ls = lens[lo:hi] if lens is not None else np.full(hi - lo, stride, dtype=np.int32)
-            words, _, _ = pack_reads_ragged([codes[i, :ls[i - lo]] for i in range(lo, hi)], K)
-            ls = np.ascontiguousarray(ls, dtype=np.int32)
-            _check(lib().pg_host_graph_add_packed(h, words.ctypes.data, ls.ctypes.data, hi - lo, n_threads), "pg_host_graph_add_packed")
-        elif hi > lo:
-            _check(lib().pg_host_graph_add_reads(h, codes[lo:].ctypes.data, lens[lo:].ctypes.data if lens is not None else None,
-                                                 hi - lo, stride, n_threads), "pg_host_graph_add_reads")
     nv, ne, na = C.c_int(0), C.c_int(0), C.c_longlong(0)
+    try:
+        for b in range(batches):
+            lo, hi = int(bounds[b]), int(bounds[b + 1])
+            if hi > lo and packed:           # the reads as pass 1 packs them (pg_pack_read), back to back
+                ls = lens[lo:hi] if lens is not None else np.full(hi - lo, stride, dtype=np.int32)
+                words, _, _ = pack_reads_ragged([codes[i, :ls[i - lo]] for i in range(lo, hi)], K)
+                ls = np.ascontiguousarray(ls, dtype=np.int32)
+                _check(lib().pg_host_graph_add_packed(h, words.ctypes.data, ls.ctypes.data, hi - lo, n_threads), "pg_host_graph_add_packed")
+            elif hi > lo:
+                _check(lib().pg_host_graph_add_reads(h, codes[lo:].ctypes.data, lens[lo:].ctypes.data if lens is not None else None,
+                                                     hi - lo, stride, n_threads), "pg_host_graph_add_reads")
+    except PgError:                          # (pg_host_graph_finish releases the graph however it ends; the batch's error is the one to report)
+        lib().pg_host_graph_finish(h, C.byref(nv), C.byref(ne), C.byref(na))
+        raise
     _check(lib().pg_host_graph_finish(h, C.byref(nv), C.byref(ne), C.byref(na)), "pg_host_graph_finish")
     return nv.value, ne.value, na.value
+
+
+def device_emu_prearcs(frm, to, seq, room: int, lanes: int = 1, device: int = 0) -> np.ndarray:
+    """pg_device_emu_prearcs: the triples (frm[i], to[i], seq[i]) through pass 2's own pre-arc path on HIP device `device` -- `lanes` tables of `room`
+    entries, triple i into table i mod lanes by add_prearc, read out and folded as a run's.  Returns the (from, to, multiplicity) rows in .preArc
+    order.  A table that overflows raises PgError ("pre-arc table overflow") whose `overflow` is the number of triples that found no entry."""
+    frm = np.ascontiguousarray(frm, dtype=np.uint32)
+    to = np.ascontiguousarray(to, dtype=np.uint32)
+    seq = np.ascontiguousarray(seq, dtype=np.uint64)
+    assert frm.shape == to.shape == seq.shape and frm.ndim == 1
+    n = len(frm)
+    out3 = np.zeros((max(n, 1), 3), dtype=np.uint32)
+    cnt = np.zeros(2, dtype=np.uint64)
+    rc = lib().pg_device_emu_prearcs(device, frm.ctypes.data, to.ctypes.data, seq.ctypes.data, n, room, lanes, out3.ctypes.data, cnt[0:].ctypes.data,
+                                     cnt[1:].ctypes.data)
+    if rc != 0:
+        err = PgError(f"pg_device_emu_prearcs failed ({rc}): {lib().pg_last_error().decode()}")
+        err.overflow = int(cnt[1])
+        raise err
+    return out3[:int(cnt[0])]
 
 
 def host_read_all(config: str, K: int):

@@ -1249,6 +1249,13 @@ int p2_begin_reads(P2Device* d, uint32_t num_ed, bool reps) {
         P2_HIP(hipMemGetInfo(&free_b, &total_b));
         arc_cap = pg::cmd_prearc_entries((uint64_t)d->num_ed, (uint64_t)total_b);      // (cmd_plan.hpp: the rule pg_host_plan_memory plans by)
     }
+    // PG_P2_ARC_ROOM=n (test hook): every lane's table has n entries -- the loads of 50 - 100 % the rule above reaches when device memory is short
+    if (const char* v = pg::env_test("PG_P2_ARC_ROOM")) {
+        const long long room = atoll(v);
+        if (room < 1 || (room & (room - 1))) { pg_set_error("pass 2: pre-arc table size must be a power of two"); return PG_EINVAL; }
+        arc_cap = (uint64_t)room;
+        if (pg::env_user("PG_HOST_VERBOSE")) fprintf(stderr, "pass 2: pre-arc tables of %llu entries a lane (PG_P2_ARC_ROOM)\n", (unsigned long long)arc_cap);
+    }
     const uint64_t patch_cap = d->prm.patch_mask + 1;
     for (size_t l = 0; l < d->lanes.size(); l++) {
         P2Lane& ln = d->lanes[l];
@@ -1724,7 +1731,13 @@ int p2_build_edges(P2Device* d, P2Edges& out) {
     }
     if ((rc = eb_waypoint_table(d, b)) != PG_OK) return rc;
     if ((rc = eb_first_walks(d, b)) != PG_OK) return rc;
-    // the (K+1)-mer table the length-1 edges enter (eb_apply)
+    // the (K+1)-mer table the length-1 edges enter (eb_apply).  PG_EB_PATCH_ROOM=n (test hook): its first size is n, so that the rule below decides the
+    // size at test sizes as well -- loads of 25 - 50 %
+    if (const char* v = pg::env_test("PG_EB_PATCH_ROOM")) {
+        const long long room = atoll(v);
+        if (room < 1 || (room & (room - 1))) { pg_set_error("pass 2: patch table size must be a power of two"); return PG_EINVAL; }
+        b.patch_cap = (uint64_t)room;
+    }
     while (b.patch_cap < 2 * b.n_len1 + 2) b.patch_cap <<= 1;
     {
         DevArr<uint64_t> keys; DevArr<uint32_t> val;
@@ -2043,6 +2056,82 @@ extern "C" int pg_device_emu_append(int device, const unsigned char* flags, uint
     }
     if (st) (void)hipStreamDestroy(st);
     return rc;
+}
+
+// Pass 2's pre-arc path on caller-given triples: triple `first + t * stride` goes into the table of p through the product's add_prearc (p carries arc,
+// arc_mask and counters, nothing else), one lane a triple -- neighbours in the input are neighbours in a wave.
+__global__ __launch_bounds__(256) void emu_prearc_insert(P2Params p, const uint32_t* __restrict__ from, const uint32_t* __restrict__ to, const unsigned long long* __restrict__ seq,
+                                                         uint64_t first, uint64_t stride, uint64_t n) {
+    const uint64_t i = first + ((uint64_t)blockIdx.x * 256 + threadIdx.x) * stride;
+    if (i < n) add_prearc(p, from[i], to[i], seq[i]);
+}
+// the tables of `lanes` lanes filled, then read out, gathered and folded as p2_finish does it (count, compact into one array, p2_fold_arcs)
+static int emu_prearcs_on(const uint32_t* d_from, const uint32_t* d_to, const unsigned long long* d_seq, uint64_t n, uint64_t room, int lanes, hipStream_t st,
+                          std::vector<uint32_t>& out3, unsigned long long* overflow) {
+    std::vector<DevArr<unsigned long long>> arc((size_t)lanes), counters((size_t)lanes);
+    std::vector<unsigned long long> lane_arcs((size_t)lanes, 0);
+    unsigned long long n_arcs = 0;
+    *overflow = 0;
+    for (int l = 0; l < lanes; l++) {
+        P2_HIP(arc[l].alloc(room * ARC_WORDS)); P2_HIP(counters[l].alloc(8));
+        hipLaunchKernelGGL(p2_arc_init, dim3(2048), dim3(256), 0, st, arc[l].p, room);
+        P2_HIP(hipMemsetAsync(counters[l].p, 0, 8 * sizeof(unsigned long long), st));
+        P2Params p{};
+        p.arc = arc[l].p; p.arc_mask = room - 1; p.counters = counters[l].p;
+        const uint64_t mine = n > (uint64_t)l ? (n - l + lanes - 1) / lanes : 0;
+        if (mine) hipLaunchKernelGGL(emu_prearc_insert, dim3((unsigned)((mine + 255) / 256)), dim3(256), 0, st, p, d_from, d_to, d_seq, (uint64_t)l, (uint64_t)lanes, n);
+        hipLaunchKernelGGL(p2_count_arcs, dim3(2048), dim3(256), 0, st, arc[l].p, room, counters[l].p + 3);
+        P2_HIP(hipGetLastError());
+        unsigned long long cl[8];
+        P2_HIP(hipMemcpyAsync(cl, counters[l].p, sizeof(cl), hipMemcpyDeviceToHost, st));
+        P2_HIP(hipStreamSynchronize(st));
+        *overflow += cl[2];
+        lane_arcs[l] = cl[3];
+        n_arcs += cl[3];
+    }
+    out3.clear();
+    if (*overflow || !n_arcs) return PG_OK;
+    DevArr<P2Arc> d_all;
+    P2_HIP(d_all.alloc((size_t)n_arcs));
+    size_t at = 0;
+    for (int l = 0; l < lanes; l++) {
+        const unsigned long long n_l = lane_arcs[l];
+        if (!n_l) continue;
+        hipLaunchKernelGGL(p2_compact_arcs, dim3(2048), dim3(256), 0, st, arc[l].p, room, d_all.p + at, counters[l].p + 6, n_l);
+        unsigned long long got = 0;
+        P2_HIP(hipMemcpyAsync(&got, counters[l].p + 6, sizeof(got), hipMemcpyDeviceToHost, st));
+        P2_HIP(hipStreamSynchronize(st));
+        if (got != n_l) { pg_set_error("pg_device_emu_prearcs: pre-arc table is inconsistent"); return PG_EINVAL; }
+        at += (size_t)n_l;
+        arc[l].reset(); counters[l].reset();
+    }
+    return p2_fold_arcs(std::move(d_all), n_arcs, lanes > 1, st, out3);
+}
+extern "C" int pg_device_emu_prearcs(int device, const uint32_t* from, const uint32_t* to, const uint64_t* seq, uint64_t n, uint64_t room, int lanes,
+                                     uint32_t* out3, uint64_t* count_out, uint64_t* overflow_out) {
+    if ((n && (!from || !to || !seq || !out3)) || !count_out || !overflow_out || room < 2 || (room & (room - 1)) || room > (1ULL << 32) || lanes < 1 ||
+        n >= 0xFFFFFFFFull) { pg_set_error("pg_device_emu_prearcs: bad argument"); return PG_EINVAL; }
+    for (uint64_t i = 0; i < n; i++) if (!from[i] && !to[i]) { pg_set_error("pg_device_emu_prearcs: the pair (0, 0) is the table's empty key"); return PG_EINVAL; }
+    *count_out = 0; *overflow_out = 0;
+    int rc = emu_device(device, "pg_device_emu_prearcs");
+    if (rc || !n) return rc;
+    pg::ArenaPin pin(device);                                          // (one life of the arena for the call's blocks, not one for every block)
+    DevArr<uint32_t> d_from, d_to; DevArr<unsigned long long> d_seq;
+    if ((rc = emu_upload(from, n, d_from)) != PG_OK || (rc = emu_upload(to, n, d_to)) != PG_OK || (rc = emu_upload((const unsigned long long*)seq, n, d_seq)) != PG_OK) return rc;
+    hipStream_t st = nullptr;
+    if (hipStreamCreate(&st) != hipSuccess) { pg_set_error("test hook: no stream"); return PG_ENODEV; }
+    std::vector<uint32_t> folded;
+    unsigned long long overflow = 0;
+    rc = emu_prearcs_on(d_from.p, d_to.p, d_seq.p, n, room, lanes, st, folded, &overflow);
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    if (rc) return rc;
+    *overflow_out = overflow;
+    if (overflow) { pg_set_error("pg_device_emu_prearcs: pre-arc table overflow"); return PG_ENOMEM; }
+    if (folded.size() > 3 * n) { pg_set_error("pg_device_emu_prearcs: more pre-arcs than triples"); return PG_ESTATE; }
+    std::copy(folded.begin(), folded.end(), out3);
+    *count_out = folded.size() / 3;
+    return PG_OK;
 }
 
 // pg_host_emu_clip_tips on the HipBackend: the layout is replayed on the host (host_graph.cpp: emu_tip_sets), the sets go up as a run without a

@@ -1157,15 +1157,17 @@ def test_suite_subset_on_poisoned_arena_blocks():
     """Every device allocation of the library is a recycled arena block that holds whatever its last user left (a fresh hipMalloc hands out zeroes in
     practice): PG_ARENA_POISON=1 fills every block with 0xA5 as it is cut, so code that counts on zeroes fails every time instead of once in a
     while.  The counting kernels, the executable on uniform and trimmed reads (growable sets and -a pools, -R), the sharded run and the
-    device layouts, again, in a process of their own with the hook on."""
+    device layouts, again, in a process of their own with the hook on -- and the small designed cases of pass 2's pre-arc path (tests/test_gpu_prearc.py: 16
+    cases and the three overflows), whose tables rely on p2_arc_init, not on zeroed memory."""
     import sys
     sel = ("(test_count_matches_oracle and (t6k_k127 or t8k_k63-2-False or t6k_k31-16)) or (test_cli_matches_reference_files and (t6k_k31-2 or t8k_k63-2 or g60k_k31-2 or g40k_k127-2))"
            " or (test_cli_sharded_matches_reference_files and t5k_k24) or test_cli_layout_on_the_device_and_on_the_host or test_ragged_tiles_match_oracle and g60k and exact"
-           " or test_cli_reader_corner_cases")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_pregraph.py"), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider", "-k", sel],
+           " or test_cli_reader_corner_cases or test_prearc_emu_case_equals_the_model or test_prearc_emu_overflow_is_counted_exactly")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_pregraph.py"), os.path.join(ROOT, "tests", "test_gpu_prearc.py"),
+                        "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider", "-k", sel],
                        capture_output=True, text=True, env=dict(os.environ, PG_ARENA_POISON="1"), cwd=ROOT)
     tail = (r.stdout + r.stderr)[-3000:]
     assert r.returncode == 0, tail
     import re
     m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) >= 15, tail
+    assert m and int(m.group(1)) >= 15 + 19, tail
